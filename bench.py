@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- images/sec encoded + top-k retrieved, VLAD K=256 RootSIFT (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -100,12 +100,21 @@ def parse():
     ap.add_argument("--retrieval", choices=["exact", "filtered", "f16", "f64"], default=None,
                     help="f64 (--workload fisher only) = float64 encodings scored and ranked in float64 on the f64 matrix pipe, the "
                          "reference's dtype for Fisher vectors.  exact = f32 MFMA GEMM over all pairs (the headline). filtered = the same top-k lists, bit for bit, "
-                         "through the fp16 prefilter + exact re-scoring (pvs_cosine_topk_filtered_dev); single GPU only. The "
-                         "default run also times the filtered variant and reports it under 'filtered_retrieval'.")
+                         "through the fp16 prefilter + exact re-scoring (pvs_cosine_topk_filtered_dev); single GPU only. With "
+                         "--full, a single-GPU config2 run also times the other variant and reports it under 'filtered_retrieval'.")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)   # the child process of cpu_baseline_subprocess()
     ap.add_argument("--pcie", action="store_true", help="also time one step with host-resident inputs (H2D included)")
+    ap.add_argument("--full", action="store_true",
+                    help="config2 / corpus1m: everything beyond the headline -- the CPU baseline, the other retrieval variant timed and "
+                         "compared list for list, the self-retrieval and self-checks, PMC traffic from the committed profiles, the "
+                         "strong-scaling base.  A plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config2 / corpus1m: after the timed steps write what the last step computed (rank 0's top-k lists and a "
+                         "seeded sample of its encodings) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     # defaults that depend on the GPU count: the driver types `bench.py --gpus N --steps K --warmup W` and nothing else
     args.workload_defaulted = args.workload is None
     if args.workload is None:
@@ -118,6 +127,8 @@ def parse():
         args.total_queries = 65536
     if args.retrieval == "f64" and args.workload != "fisher":
         ap.error("--retrieval f64 belongs to --workload fisher")
+    if args.dump_outputs and args.workload not in ("config2", "corpus1m"):
+        ap.error("--dump-outputs belongs to --workload config2 / corpus1m")
     return args
 
 
@@ -170,6 +181,24 @@ def rootsift_torch(raw_u8):
         x = raw_u8[s:s + step].float()
         out[s:s + step] = torch.sqrt(x / (x.sum(dim=1, keepdim=True) + 1e-7))
     return out
+
+
+def dump_outputs(path, idx, val, enc, inv, lo, max_queries=65536, enc_rows=128):
+    """--dump-outputs: what the timed path hands its caller after the last step, as path/<name>.npy.  The top-k lists of (a
+    seeded sample of at most max_queries of) the query rows, indices as float64 (exact below 2**53), and a seeded sample of
+    enc_rows VLAD encodings with their inverse norms; row numbers are global image indices.  At most ~26 MB in all."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    nq, n = idx.shape[0], enc.shape[0]
+    q = np.arange(nq) if nq <= max_queries else np.sort(np.random.default_rng(1).choice(nq, max_queries, replace=False))
+    e = np.sort(np.random.default_rng(2).choice(n, min(enc_rows, n), replace=False))
+    q_t, e_t = torch.from_numpy(q).to(idx.device), torch.from_numpy(e).to(enc.device)
+    out = {"topk_indices": idx[q_t].cpu().numpy().astype(np.float64), "topk_scores": val[q_t].cpu().numpy().astype(np.float32),
+           "query_rows": (q + lo).astype(np.float64), "encodings_sample": enc[e_t].cpu().numpy().astype(np.float32),
+           "inv_norms_sample": inv[e_t].cpu().numpy().astype(np.float32), "encoding_rows": (e + lo).astype(np.float64)}
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def side_workload(args):
@@ -525,7 +554,7 @@ def main():
         sys.exit(self_launch(args))                      # no GPU call has happened in this process
     corpus1m = args.workload == "corpus1m"
     cpu = None
-    if (not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0 and os.environ.get("PVS_BENCH_FORCE_DIST") != "1"
+    if (args.full and not args.no_cpu_baseline and int(os.environ.get("RANK", "0")) == 0 and os.environ.get("PVS_BENCH_FORCE_DIST") != "1"
             and os.environ.get("PVS_BENCH_BACKEND", "rccl") != "gloo"):
         # rank 0 only, before anything touches the GPU (the child forks worker processes); the other ranks wait for it at the
         # communicator bootstrap
@@ -816,7 +845,7 @@ def main():
 
     filtered = retr == "filtered"
     other = None
-    if not multi and not corpus1m:
+    if args.full and not multi and not corpus1m:
         # the variant that is NOT the headline of this run is timed first, its lists kept for the bit-for-bit comparison
         o_dt, o_tm, _ = timed_steps(not filtered)
         other = {"dt": o_dt, "timers": o_tm, "idx": idx.clone(), "val": val.clone(), "was_filtered": not filtered, "stats": filt_stats[0]}
@@ -825,12 +854,15 @@ def main():
         dt = float(comm.max_over_ranks([dt])[0])
     ms_per_step = dt / args.steps * 1e3
     value = N / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, idx[:nq], val[:nq], enc_loc[:n_loc], inv_loc[:n_loc], lo)
 
-    # ---- sanity inside the bench: self-retrieval must return the image itself first
-    got = idx[:nq, 0].cpu().numpy()
-    assert np.array_equal(got, np.arange(lo, lo + nq)), "self-retrieval failed: top-1 is not the query image"
+    # ---- sanity inside the bench (--full): self-retrieval must return the image itself first
+    if args.full:
+        got = idx[:nq, 0].cpu().numpy()
+        assert np.array_equal(got, np.arange(lo, lo + nq)), "self-retrieval failed: top-1 is not the query image"
     check = None
-    if (multi and (staged or forced)) or (corpus1m and retr != "exact"):
+    if args.full and ((multi and (staged or forced)) or (corpus1m and retr != "exact")):
         # self-check: the multi-rank / filtered / fp16 result against the plain exact ranking of (a sample of) this rank's queries
         nchk = nq if retr != "f16" and (staged or forced) else min(nq, 256)
         ri = torch.empty((nchk, k_top), dtype=torch.int64, device=dev)
@@ -911,7 +943,7 @@ def main():
     gemm_avg_ms = gemm_ms / max(gemm_n, 1)
     achieved = flop_per_launch / (gemm_avg_ms * 1e-3) / 1e12 if gemm_n else 0.0
     peak = 2500.0 if f16_gemm else FP32_MFMA_PEAK_TFLOPS
-    default_line = not multi and not corpus1m and N == 8189 and not filtered
+    default_line = args.full and not multi and not corpus1m and N == 8189 and not filtered     # figures of the committed PMC passes
     traffic, traffic_src = pmc_traffic("pvs::gemm_mfma_kernel", keep=lambda nm: not _gemm_is_f16(nm)) if default_line else (None, None)
     stages = {k: {"ms_total": round(v[0], 3), "launches": int(v[1]),
                   "ms_avg": round(v[0] / v[1], 4) if v[1] else None} for k, v in timers.items() if v[1]}
@@ -985,7 +1017,7 @@ def main():
 
     if cpu is not None:
         out["cpu_baseline"] = cpu       # single-process baseline of the same workload, timed on rank 0's host cores
-    if multi and not (staged or forced):
+    if args.full and multi and not (staged or forced):
         base = strong_scaling_base(args, retr)
         if base is not None:
             out["strong_scaling_base_1gpu"] = base

@@ -19,12 +19,17 @@ helpers expected here stops the reader with an error.  Output: plain `.npz` file
 
     python tests/golden/extract_reference_tables.py            # writes python-visual-similarity_amd/pvsim/res/model_files/*.npz
     python tests/golden/extract_reference_tables.py --check    # re-reads the .pkl files and compares with the committed .npz
+    python tests/golden/extract_reference_tables.py --check --src DIR    # the same, for the .pkl files in DIR
+    python tests/golden/extract_reference_tables.py --digest   # writes tests/golden/reference_tables_digest.json: a sha256 per
+                                                               # array of the read, which the tests check the committed .npz against
 
 Runs in the build container only (it reads /root/reference); the GPU box gets the .npz files.
 """
 from __future__ import annotations
 
+import hashlib
 import io
+import json
 import os
 import pickletools
 import sys
@@ -34,6 +39,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = "/root/reference/pyvisim/res/model_files"
 DST = os.path.join(REPO, "python-visual-similarity_amd", "pvsim", "res", "model_files")
+DIGESTS = os.path.join(REPO, "tests", "golden", "reference_tables_digest.json")
 
 ALLOWED_GLOBALS = {
     ("sklearn.mixture._gaussian_mixture", "GaussianMixture"),
@@ -217,14 +223,45 @@ def tables_of(path: str) -> dict:
     return out
 
 
-def main():
-    check = "--check" in sys.argv
-    os.makedirs(DST, exist_ok=True)
-    ok = True
-    for name in sorted(os.listdir(SRC)):
+def codebook_of(name: str, t: dict) -> dict:
+    """The k-means codebook derived from the mixture gmm_<name>.pkl (see main())."""
+    kname = "k_means_" + name[len("gmm_"):-4] + ".npz"
+    return {"kind": np.array("kmeans"), "cluster_centers": np.ascontiguousarray(t["means"], dtype=np.float32),
+            "derived_from": np.array(name + " means_ (the reference's own " + kname[:-4] + ".pkl is absent from its checkout)")}
+
+
+def array_digest(a: np.ndarray) -> dict:
+    return {"dtype": a.dtype.str, "shape": list(a.shape), "sha256": hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()}
+
+
+def digests_of(src: str) -> dict:
+    """{.npz name: {array name: digest}} of every table main() writes, from the .pkl files in src."""
+    out = {}
+    for name in sorted(os.listdir(src)):
         if not name.endswith(".pkl"):
             continue
-        t = tables_of(os.path.join(SRC, name))
+        t = tables_of(os.path.join(src, name))
+        out[name[:-4] + ".npz"] = {k: array_digest(v) for k, v in t.items()}
+        if name.startswith("gmm_"):
+            out["k_means_" + name[len("gmm_"):-4] + ".npz"] = {k: array_digest(v) for k, v in codebook_of(name, t).items()}
+    return out
+
+
+def main():
+    check = "--check" in sys.argv
+    src = sys.argv[sys.argv.index("--src") + 1] if "--src" in sys.argv else SRC     # another directory of the same .pkl files
+    if "--digest" in sys.argv:
+        with open(DIGESTS, "w") as f:
+            json.dump(digests_of(src), f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"wrote {os.path.relpath(DIGESTS, REPO)}")
+        return
+    os.makedirs(DST, exist_ok=True)
+    ok = True
+    for name in sorted(os.listdir(src)):
+        if not name.endswith(".pkl"):
+            continue
+        t = tables_of(os.path.join(src, name))
         dst = os.path.join(DST, name[:-4] + ".npz")
         desc = ", ".join(f"{k}{tuple(v.shape)}:{v.dtype}" for k, v in t.items() if v.ndim)
         if check:
@@ -240,14 +277,13 @@ def main():
     # The reference's own KMeans codebooks (k_means_k256_*.pkl) are absent from its checkout (.MISSING_LARGE_BLOBS:3-8).  Each
     # shipped mixture was k-means-initialised (init_params='kmeans'), so its float32 means_ are the stand-in codebook SURVEY.md
     # section 0.3 / 8c names; the file says what it is (`derived_from`), and KMeansWeights.load() warns about it.
-    for name in sorted(os.listdir(SRC)):
+    for name in sorted(os.listdir(src)):
         if not (name.startswith("gmm_") and name.endswith(".pkl")):
             continue
-        t = tables_of(os.path.join(SRC, name))
+        t = tables_of(os.path.join(src, name))
         kname = "k_means_" + name[len("gmm_"):-4] + ".npz"
         dst = os.path.join(DST, kname)
-        arrays = {"kind": np.array("kmeans"), "cluster_centers": np.ascontiguousarray(t["means"], dtype=np.float32),
-                  "derived_from": np.array(name + " means_ (the reference's own " + kname[:-4] + ".pkl is absent from its checkout)")}
+        arrays = codebook_of(name, t)
         if check:
             old = np.load(dst, allow_pickle=False)
             same = all(np.array_equal(old[k], arrays[k]) for k in arrays)

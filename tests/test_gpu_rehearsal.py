@@ -25,7 +25,7 @@ def _run_bench(ranks, env_extra, extra_args, timeout=900):
     if "PVS_BENCH_BACKEND" not in env_extra:
         env.pop("PVS_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--no-cpu-baseline"] + extra_args
+           "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--full", "--no-cpu-baseline"] + extra_args
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=timeout)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -82,7 +82,7 @@ def test_bounded_query_block_travels_instead_of_the_database(ranks, env):
 def test_corpus1m_single_gpu_filtered_equals_exact():
     """Single GPU, no launcher: the chunked corpus build + filtered retrieval, lists bit-identical to the all-pairs f32 GEMM."""
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--workload", "corpus1m", "--images", "30000", "--steps", "1",
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--workload", "corpus1m", "--images", "30000", "--steps", "1",
                         "--warmup", "0", "--retrieval", "filtered", "--queries", "2048"], cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -98,7 +98,7 @@ def test_corpus1m_at_its_stated_size_on_one_gpu(retrieval, qflag, nq):
     dense one-pass row kernel over all 10^6 rows (what a single query against a resident index takes).  Size-independent
     properties at full size: every query retrieves itself first with score 1 (asserted inside bench.py for both paths)."""
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--workload", "corpus1m", "--retrieval", retrieval,
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--full", "--workload", "corpus1m", "--retrieval", retrieval,
                         qflag, str(nq), "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -118,7 +118,7 @@ def test_bench_starts_its_own_ranks_when_typed_without_a_launcher():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PVS_BENCH_BACKEND="gloo")
     for k_ in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k_, None)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "1", "--warmup", "0", "--images", "20000",
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--full", "--steps", "1", "--warmup", "0", "--images", "20000",
                         "--total-queries", "4096"], env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

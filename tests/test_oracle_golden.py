@@ -316,16 +316,54 @@ def test_oracle_on_the_reference_shipped_tables():
     np.testing.assert_allclose(orc.vlad_encode(imgs, C), g["vlad_rootsift"], rtol=0, atol=2e-7)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/pyvisim/res/model_files"), reason="the reference checkout is only present in the build container")
 def test_shipped_table_files_equal_a_fresh_non_executing_read_of_the_reference():
-    """tests/golden/extract_reference_tables.py --check: the committed pvsim/res/model_files/*.npz are what the opcode walk
-    (no unpickling, no class lookups) reads out of the reference's own files today; a class record outside its allow-list
-    or an opcode outside its subset would stop it."""
+    """The committed pvsim/res/model_files/*.npz are what the opcode walk (no unpickling, no class lookups) read out of the
+    reference's own .pkl files: tests/golden/reference_tables_digest.json holds, per table and array, the dtype, shape and
+    sha256 of that read (extract_reference_tables.py --digest), and every committed array -- 8 shipped files + 5 derived
+    codebooks -- must match it bit for bit, with no array missing or added."""
+    import json
+    from conftest import GOLDEN
+    from shipped_inputs import MODELS
+    with open(os.path.join(GOLDEN, "reference_tables_digest.json")) as f:
+        want = json.load(f)
+    assert len(want) == 13 and sorted(want) == sorted(os.listdir(MODELS))
+    import extract_reference_tables as ext
+    for name, arrays in want.items():
+        t = np.load(os.path.join(MODELS, name), allow_pickle=False)
+        assert sorted(t.files) == sorted(arrays), name
+        for k, d in arrays.items():
+            assert ext.array_digest(t[k]) == d, f"{name}: {k} differs from the read of the reference's file"
+
+
+def test_the_table_reader_reads_back_joblib_pickles_of_the_estimators(tmp_path, monkeypatch):
+    """tests/golden/extract_reference_tables.py --check --src: the opcode walk reads joblib pickles of fitted scikit-learn
+    GaussianMixture / PCA estimators (written here by joblib.dump from the committed tables, with the version string the
+    reference's files carry) back to exactly those tables, derived codebooks included; a class record outside its allow-list
+    or an opcode outside its subset would stop it.  Which values the tables hold is pinned by the digest test above."""
     import subprocess
     import sys
+    import joblib
+    import sklearn.base
+    from sklearn.decomposition import PCA
+    from sklearn.mixture import GaussianMixture
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "golden", "extract_reference_tables.py"), "--check"],
-                       capture_output=True, text=True, timeout=300)
+    from shipped_inputs import MODELS
+    for name in sorted(os.listdir(MODELS)):
+        if name.startswith("k_means_"):                   # derived from the mixtures' means by the extractor
+            continue
+        t = np.load(os.path.join(MODELS, name), allow_pickle=False)
+        monkeypatch.setattr(sklearn.base, "__version__", str(t["sklearn_version"]))     # what __getstate__ records
+        if str(t["kind"]) == "gmm":
+            m = GaussianMixture(n_components=t["weights"].shape[0], covariance_type="diag", reg_covar=float(t["reg_covar"]))
+            m.weights_, m.means_, m.covariances_ = t["weights"], t["means"], t["covariances"]
+            m.precisions_cholesky_, m.converged_, m.n_iter_ = t["precisions_cholesky"], bool(t["converged"]), int(t["n_iter"])
+        else:
+            m = PCA(n_components=t["components"].shape[0], whiten=bool(t["whiten"]))
+            m.components_, m.mean_, m.explained_variance_ = t["components"], t["mean"], t["explained_variance"]
+            m.n_samples_ = int(t["n_samples"])
+        joblib.dump(m, str(tmp_path / (name[:-4] + ".pkl")))
+    r = subprocess.run([sys.executable, os.path.join(REPO, "tests", "golden", "extract_reference_tables.py"), "--check",
+                        "--src", str(tmp_path)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert r.stdout.count("same") == 13 and "DIFFERS" not in r.stdout          # 8 shipped files + 5 derived codebooks
 
