@@ -286,6 +286,35 @@ int pvs_min_update_dev(pvs_ctx* ctx, float* d_mind, const float* d_dist, int64_t
 int pvs_kmeanspp_run_dev(pvs_ctx* ctx, const float* d_x, int D, int64_t total_desc, int n_clusters, int trials,
                          const double* h_uniform, int64_t* h_indices);
 
+/* ---------------------------------------------------------------- image clustering: pyvisim/_utils.py:128-162
+ * (cluster_and_return_labels -> sklearn SpectralClustering / DBSCAN).  Their cost is an exact Euclidean neighbour search over the
+ * encodings, brute force as sklearn does it: float32 rows are upcast to float64 (sklearn/metrics/_pairwise_distances_reduction),
+ * and the value ranked or thresholded is  d = max(0, (|x|^2 + (-2 x.y)) + |y|^2)  in float64.  is_f64 != 0: rows are double,
+ * otherwise float.  Rows are C-contiguous [n][L].  Q == X with nq == N is the self graph; the GEMM computes only the
+ * upper triangle when one panel covers the whole problem (nq <= 8192 and N <= 32768 for float32 rows).
+ *
+ * pvs_l2_knn_dev: per query the k rows with the smallest d, order (d ascending, index ascending); d_idx int64 [nq][k],
+ * d_sqdist float64 [nq][k] = d.  float32 rows: f32 MFMA prefilter with a proven margin + float64 re-score (neighbors.hip);
+ * float64 rows, k > 256 or candidate lists that overflow: a full float64 pass.  Synchronises the stream (it reads the largest row
+ * norm).  h_stats (optional, int64[4]): [0] 1 if the prefilter ran, [1] queries that overflowed their candidate slots (the call
+ * then redid everything in float64), [2] candidates re-scored, [3] candidate slots per query. */
+int pvs_l2_knn_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_X, int64_t N, int64_t L, int is_f64, int k,
+                   int64_t* d_idx, double* d_sqdist, int64_t* h_stats);
+/* Radius neighbours (DBSCAN): all rows with d <= r_sq, decided in float64.  Pass 1 writes the counts (int64 [nq]); the caller
+ * forms indptr (int64 [nq + 1], exclusive prefix sum) and pass 2 writes d_indices (int64) and optionally d_sqdist (float64) in
+ * index order per query (CSR). */
+int pvs_l2_radius_count_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_X, int64_t N, int64_t L, int is_f64,
+                            double r_sq, int64_t* d_counts);
+int pvs_l2_radius_fill_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_X, int64_t N, int64_t L, int is_f64,
+                           double r_sq, const int64_t* d_indptr, int64_t* d_indices, double* d_sqdist);
+/* Y = alpha S X + X diag(beta) + gamma Z, float64, for the block eigensolver of the spectral embedding.  S: n x n CSR (indptr int64
+ * [n + 1], indices int64, data float64); X, Z, Y: [n][m] row-major; d_beta [m] may be NULL (0), d_Z may be NULL (0).  Y must not
+ * alias X or Z. */
+int pvs_csr_spmm_f64_dev(pvs_ctx* ctx, int64_t n, const int64_t* d_indptr, const int64_t* d_indices, const double* d_data,
+                         const double* d_X, int m, double alpha, const double* d_beta, const double* d_Z, double gamma, double* d_Y);
+/* dst[c][r] = src[r][c], float64 (block Gram matrices through pvs_cosine_f64_dev with unit inverse norms). */
+int pvs_transpose_f64_dev(pvs_ctx* ctx, const double* d_src, int64_t rows, int64_t cols, double* d_dst);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm, 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

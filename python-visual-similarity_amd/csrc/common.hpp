@@ -61,7 +61,8 @@ struct pvs_ctx {
   // 0 host-API input staging, 1 scratch (labels, tables, responsibilities), 2 host-API outputs / score panel,
   // 3 PCA projections, 4 materialised RootSIFT rows
   // 5 fp16 row copies (filtered top-k), 6 filtered top-k lists / candidates
-  static constexpr int NWS = 7;
+  // 7 row norms of the neighbour search, 8 float64 row copies of the neighbour search (neighbors.hip)
+  static constexpr int NWS = 9;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
   // cached tile lists of the similarity GEMM, one per GEMM model (cosine.hip): a context is one device + one stream, so the

@@ -86,6 +86,39 @@ __global__ __launch_bounds__(256) void learn_sqdist_kernel(const float* __restri
 //   d_stats[K*D .. +K)     member counts
 //   d_stats[K*D+K]         inertia  sum_i |x_i - c_label|^2
 //   d_stats[K*D+K+1]       number of labels that differ from d_prev_labels (0 when that is null)
+// Rows longer than the VLAD aggregate kernel takes (D > AGG_D_MAX, e.g. image encodings being clustered): out[k][d] = sum over the
+// rows labelled k of (x_id - c_kd) (square = 0) or of fl32(x_id^2) - c_kd (square = 1), in fp64, rows in index order.  One thread
+// per (column, label): a workgroup scans the labels (broadcast reads) and reads the columns of its members' rows coalesced, so
+// every row is read once per 256 columns.
+constexpr int AGG_D_MAX = 1024;
+
+__global__ __launch_bounds__(256) void learn_label_residual_kernel(const float* __restrict__ x, int64_t total, int D,
+                                                                   const int32_t* __restrict__ labels, const float* __restrict__ cent,
+                                                                   int square, double* __restrict__ out) {
+  const int k = blockIdx.y;
+  const int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const float c = (d < D && cent) ? cent[(int64_t)k * D + d] : 0.f;
+  double s = 0.0;
+  for (int64_t i = 0; i < total; ++i) {
+    if (labels[i] != k) continue;
+    if (d < D) {
+      float v = x[i * D + d];
+      if (square) v = v * v;
+      s += (double)(v - c);
+    }
+  }
+  if (d < D) out[(int64_t)k * D + d] = s;
+}
+
+static int launch_label_residual(pvs_ctx* ctx, const float* x, int64_t total, int D, const int32_t* d_labels, int K,
+                                 const float* d_cent, int square, double* d_out) {
+  if ((D + 255) / 256 > 0x7fffffff || K > 65535) PVS_FAIL(PVS_ERR_UNSUPPORTED, "label sums: shape too large");
+  hipLaunchKernelGGL(learn_label_residual_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)K), dim3(256), 0, ctx->stream, x, total,
+                     D, d_labels, d_cent, square, d_out);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
 int launch_kmeans_step(pvs_ctx* ctx, const pvs_codebook* cb, const float* x, int64_t total, int32_t* d_labels,
                        const int32_t* d_prev_labels, double* d_stats, float* d_sqdist) {
   const int K = cb->K, D = cb->D;
@@ -95,7 +128,11 @@ int launch_kmeans_step(pvs_ctx* ctx, const pvs_codebook* cb, const float* x, int
   const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4));
   pvs_norm_params prm{1.0, 2.0, 0.0};
   int first = 1;
-  for (int64_t t0 = 0; t0 < total; t0 += rows_per_batch) {
+  if (D > AGG_D_MAX) {   // long rows: labels, then the per-label residual sums directly in fp64
+    PVS_TRY(launch_assign(ctx, cb, x, PVS_DESC_F32, total, D, d_labels));
+    PVS_TRY(launch_label_residual(ctx, x, total, D, d_labels, K, cb->d_cent, 0, d_stats));
+  }
+  for (int64_t t0 = 0; D <= AGG_D_MAX && t0 < total; t0 += rows_per_batch) {
     const int64_t tn = std::min(rows_per_batch, total - t0);
     const int64_t nch = (tn + LEARN_CHUNK - 1) / LEARN_CHUNK;
     const size_t off_b = ((size_t)(nch + 1) * 8 + 255) / 256 * 256;
@@ -143,6 +180,7 @@ __global__ void learn_square_kernel(const float* __restrict__ x, int64_t n, floa
 int launch_label_sums(pvs_ctx* ctx, const float* x, int64_t total, int D, const int32_t* d_labels, int K, int square, double* d_out) {
   if (total <= 0) PVS_FAIL(PVS_ERR_INVALID, "empty input");
   if (K > 2048) PVS_FAIL(PVS_ERR_UNSUPPORTED, "K = %d exceeds the device limit (2048)", K);
+  if (D > AGG_D_MAX) return launch_label_residual(ctx, x, total, D, d_labels, K, nullptr, square, d_out);
   const int64_t len = (int64_t)K * D;
   const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4));
   float* zero = nullptr;
@@ -278,15 +316,21 @@ constexpr int SEED_ROWS = 256;   // descriptors per block (8 rounds of 32): at 1
 // Eight lanes share a descriptor (each takes dims 4 l, 4 l + 32, ... as float4: a row's lanes read 128 contiguous bytes per
 // step), every lane keeps its partial |x - cand_j|^2 for all candidates in registers, and one 3-step butterfly per candidate
 // folds the eight lanes -- 3 cross-lane steps per descriptor and candidate instead of 6 per wave-wide reduction.
+// GC (rows whose candidates do not fit in LDS, nc * D > SEED_LDS_FLOATS): the candidates are read from global memory (they stay in
+// L2: at most 8 rows); the arithmetic and its order are the same, only the operand's address space differs.
+template <bool GC>
 __global__ __launch_bounds__(256) void learn_seed_kernel(const float* __restrict__ X, int64_t total, int D, const float* __restrict__ cand,
                                                          int nc, const float* __restrict__ mind, float* __restrict__ dist,
                                                          double* __restrict__ block_pot /*[SEED_MAX][nblk]*/) {
-  extern __shared__ float sc[];  // [nc][D] candidates, then [32][SEED_MAX] row results
-  float* res = sc + ((nc * D + 1) & ~1);     // 8-B aligned: it holds doubles at the end
-  for (int i = threadIdx.x; i < nc * D; i += 256) sc[i] = cand[i];
-  __syncthreads();
+  extern __shared__ float lds_[];  // [nc][D] candidates (not GC), then [32][SEED_MAX] row results
+  const float* sc = GC ? cand : lds_;
+  float* res = GC ? lds_ : lds_ + ((nc * D + 1) & ~1);     // 8-B aligned: it holds doubles at the end
+  if (!GC) {
+    for (int i = threadIdx.x; i < nc * D; i += 256) lds_[i] = cand[i];
+    __syncthreads();
+  }
   const int l8 = threadIdx.x & 7, grp = threadIdx.x >> 3;   // 32 descriptors per round
-  const bool vec = (D % 4 == 0) && (reinterpret_cast<uintptr_t>(X) % 16 == 0);
+  const bool vec = (D % 4 == 0) && (reinterpret_cast<uintptr_t>(X) % 16 == 0) && (!GC || reinterpret_cast<uintptr_t>(cand) % 16 == 0);
   // every 8-lane group keeps the fp64 potentials of ITS rows (one row per round) in registers: no barrier and no serial sum
   // per round (the loop was bound by them: 156 -> see DESIGN 6b); the 32 group sums are added in group order at the end
   double gp[SEED_MAX];
@@ -354,6 +398,13 @@ __global__ __launch_bounds__(256) void learn_seed_kernel(const float* __restrict
   }
 }
 
+// the candidates live in LDS while they fit next to the row results (every shape the kernel took before); longer rows read them
+// from global memory
+static bool seed_global_cand(int nc, int D) { return ((size_t)nc * D + 2 + 64 * SEED_MAX) * 4 > 64 * 1024; }
+static size_t seed_lds_bytes(int nc, int D) {
+  return seed_global_cand(nc, D) ? (size_t)(2 + 64 * SEED_MAX) * 4 : ((size_t)nc * D + 2 + 64 * SEED_MAX) * 4;
+}
+
 // block c: d_pot[c] = sum of block_pot[c][0..nblk)  (strided partial sums, fixed tree)
 __global__ __launch_bounds__(256) void learn_seed_reduce_kernel(const double* __restrict__ block_pot, int64_t nblk, double* __restrict__ pot) {
   __shared__ double sh[256];
@@ -373,12 +424,15 @@ int launch_seed_distances(pvs_ctx* ctx, const float* x, int64_t total, int D, co
                           const float* d_mind, float* d_dist, double* d_pot) {
   if (n_cand < 1 || n_cand > SEED_MAX) PVS_FAIL(PVS_ERR_INVALID, "1..%d seeding candidates per call (got %d)", SEED_MAX, n_cand);
   if (total <= 0) PVS_FAIL(PVS_ERR_INVALID, "seeding needs at least one descriptor");
-  const size_t lds = ((size_t)n_cand * D + 2 + 64 * SEED_MAX) * 4;
-  if (lds > 64 * 1024) PVS_FAIL(PVS_ERR_UNSUPPORTED, "descriptor dimension %d too large for the seeding kernel", D);
+  const bool gc = seed_global_cand(n_cand, D);
+  const size_t lds = seed_lds_bytes(n_cand, D);
   const int64_t nblk = (total + SEED_ROWS - 1) / SEED_ROWS;
   double* bp = nullptr;
   PVS_TRY(ws_reserve(ctx, 1, (size_t)nblk * SEED_MAX * 8, reinterpret_cast<void**>(&bp)));
-  hipLaunchKernelGGL(learn_seed_kernel, dim3((unsigned)nblk), dim3(256), lds, ctx->stream, x, total, D, d_cand, n_cand, d_mind, d_dist, bp);
+  if (gc)
+    hipLaunchKernelGGL(learn_seed_kernel<true>, dim3((unsigned)nblk), dim3(256), lds, ctx->stream, x, total, D, d_cand, n_cand, d_mind, d_dist, bp);
+  else
+    hipLaunchKernelGGL(learn_seed_kernel<false>, dim3((unsigned)nblk), dim3(256), lds, ctx->stream, x, total, D, d_cand, n_cand, d_mind, d_dist, bp);
   hipLaunchKernelGGL(learn_seed_reduce_kernel, dim3(SEED_MAX), dim3(256), 0, ctx->stream, bp, nblk, d_pot);
   PVS_HIP(hipGetLastError());
   return PVS_OK;
@@ -534,8 +588,8 @@ int launch_kmeanspp_run(pvs_ctx* ctx, const float* x, int64_t total, int D, int 
   double* d_pot = d_pots + 8;
   int64_t* d_idx = reinterpret_cast<int64_t*>(d_pot + 1);
   const int64_t nblk = (total + LEARN_CHUNK - 1) / LEARN_CHUNK, nblk_seed = (total + SEED_ROWS - 1) / SEED_ROWS;
-  const size_t lds = ((size_t)trials * D + 2 + 64 * SEED_MAX) * 4;
-  if (lds > 64 * 1024) PVS_FAIL(PVS_ERR_UNSUPPORTED, "descriptor dimension %d too large for the seeding kernel", D);
+  const bool gc = seed_global_cand(trials, D);
+  const size_t lds = seed_lds_bytes(trials, D);
   double* bp = nullptr;
   PVS_TRY(ws_reserve(ctx, 1, (size_t)nblk_seed * SEED_MAX * 8, reinterpret_cast<void**>(&bp)));
   // first centre: its distances are the running minima
@@ -547,7 +601,10 @@ int launch_kmeanspp_run(pvs_ctx* ctx, const float* x, int64_t total, int D, int 
     hipLaunchKernelGGL(learn_pick_kernel, dim3((unsigned)trials), dim3(64), 0, ctx->stream, x, total, D, d_mind, static_cast<const int64_t*>(nullptr),
                        static_cast<const double*>(nullptr), static_cast<const double*>(nullptr), d_idx, d_cand,
                        d_uniform + (size_t)(c - 1) * trials, d_pot, d_block_sums, nblk);
-    hipLaunchKernelGGL(learn_seed_kernel, dim3((unsigned)nblk_seed), dim3(256), lds, ctx->stream, x, total, D, d_cand, trials, d_mind, d_dist, bp);
+    if (gc)
+      hipLaunchKernelGGL(learn_seed_kernel<true>, dim3((unsigned)nblk_seed), dim3(256), lds, ctx->stream, x, total, D, d_cand, trials, d_mind, d_dist, bp);
+    else
+      hipLaunchKernelGGL(learn_seed_kernel<false>, dim3((unsigned)nblk_seed), dim3(256), lds, ctx->stream, x, total, D, d_cand, trials, d_mind, d_dist, bp);
     hipLaunchKernelGGL(learn_min_update_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_mind, d_dist, total, d_block_sums, bp,
                        nblk_seed, trials, d_idx, d_pot, d_indices, c);
   }

@@ -99,6 +99,11 @@ SIGNATURES = {
     "pvs_seed_pick_dev": [_vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "pvs_min_update_dev": [_vp, _vp, _vp, _i64, _vp],
     "pvs_kmeanspp_run_dev": [_vp, _vp, _int, _i64, _int, _int, _vp, _vp],
+    "pvs_l2_knn_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _vp, _vp],
+    "pvs_l2_radius_count_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _int, C.c_double, _vp],
+    "pvs_l2_radius_fill_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _int, C.c_double, _vp, _vp, _vp],
+    "pvs_csr_spmm_f64_dev": [_vp, _i64, _vp, _vp, _vp, _vp, _int, C.c_double, _vp, _vp, C.c_double, _vp],
+    "pvs_transpose_f64_dev": [_vp, _vp, _i64, _i64, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

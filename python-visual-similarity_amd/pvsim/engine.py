@@ -412,6 +412,34 @@ class Context:
         check(_ffi.lib().pvs_topk_merge_dev(self.handle, ptr(d_idx_lists), ptr(d_val_lists), n_lists, nq, k, ptr(d_idx),
                                             ptr(d_val)))
 
+    # ------------------------------------------------------------------ image clustering (neighbors.hip)
+    def l2_knn_dev(self, d_q, nq, d_x, N, L, is_f64, k, d_idx, d_sqdist, stats=False):
+        """Exact Euclidean k nearest rows: d_idx int64 [nq][k], d_sqdist float64 [nq][k] (squared distances, sklearn's
+        float64 value and order).  Synchronises.  stats=True -> dict(filtered, overflowed, candidates, slots) (one more host
+        synchronisation per query tile to count the candidates); otherwise None."""
+        st = (C.c_int64 * 4)() if stats else None
+        check(_ffi.lib().pvs_l2_knn_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, L, int(is_f64), int(k), ptr(d_idx),
+                                        ptr(d_sqdist), st))
+        if not stats:
+            return None
+        return {"filtered": bool(st[0]), "overflowed": int(st[1]), "candidates": int(st[2]), "slots": int(st[3])}
+
+    def l2_radius_count_dev(self, d_q, nq, d_x, N, L, is_f64, r_sq, d_counts):
+        check(_ffi.lib().pvs_l2_radius_count_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, L, int(is_f64), float(r_sq),
+                                                 ptr(d_counts)))
+
+    def l2_radius_fill_dev(self, d_q, nq, d_x, N, L, is_f64, r_sq, d_indptr, d_indices, d_sqdist=None):
+        check(_ffi.lib().pvs_l2_radius_fill_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, L, int(is_f64), float(r_sq),
+                                                ptr(d_indptr), ptr(d_indices), ptr(d_sqdist)))
+
+    def csr_spmm_f64_dev(self, n, d_indptr, d_indices, d_data, d_x, m, d_y, alpha=1.0, d_beta=None, d_z=None, gamma=0.0):
+        """Y = alpha S X + X diag(beta) + gamma Z (float64; S n x n CSR, X / Z / Y (n, m))"""
+        check(_ffi.lib().pvs_csr_spmm_f64_dev(self.handle, n, ptr(d_indptr), ptr(d_indices), ptr(d_data), ptr(d_x), int(m),
+                                              float(alpha), ptr(d_beta), ptr(d_z), float(gamma), ptr(d_y)))
+
+    def transpose_f64_dev(self, d_src, rows, cols, d_dst):
+        check(_ffi.lib().pvs_transpose_f64_dev(self.handle, ptr(d_src), rows, cols, ptr(d_dst)))
+
     # ------------------------------------------------------------------ vocabulary training (one device pass each)
     def buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)

@@ -266,6 +266,26 @@ def _lloyd(rows, centers, max_iter, tol_abs, verbose):
         sqd.free()
 
 
+_GRAM_D_MAX = 2048   # the tolerance's column variances come from the D x D Gram pass up to here (bit-stable for these shapes)
+
+
+def _column_moments(rows: DeviceRows) -> np.ndarray:
+    """per-column variance of the rows (sklearn _tolerance: mean(var(X, axis=0)) * tol).  Up to D = 2048 from the diagonal of the
+    Gram pass; longer rows (encodings) from per-column sums and sums of squares (pvs_label_sums_dev, one label), which need O(D)
+    memory instead of O(D^2)."""
+    n, D = rows.n, rows.D
+    if D <= _GRAM_D_MAX:
+        s, g = rows.ctx.gram_dev(rows.ptr, D, n)
+        return np.diag(g) / n - (s / n) ** 2
+    lab = rows.ctx.buffer(n * 4).fill_bytes(0)
+    try:
+        s = rows.ctx.label_sums_dev(rows.ptr, D, n, lab.ptr, 1, square=False)[0]
+        s2 = rows.ctx.label_sums_dev(rows.ptr, D, n, lab.ptr, 1, square=True)[0]
+    finally:
+        lab.free()
+    return s2 / n - (s / n) ** 2
+
+
 def fit_kmeans(rows: DeviceRows, n_clusters: int, *, init="k-means++", n_init="auto", max_iter: int = 300,
                tol: float = 1e-4, random_state=None, verbose: int = 0, algorithm: str = "lloyd",
                copy_x: bool = True) -> KMeansModel:
@@ -290,8 +310,7 @@ def fit_kmeans(rows: DeviceRows, n_clusters: int, *, init="k-means++", n_init="a
     else:
         raise ValueError(f"init should be 'k-means++', 'random' or an array, got {init!r}")
     # tolerance relative to the data scale (sklearn _tolerance: mean of the per-feature variances * tol)
-    s, g = rows.ctx.gram_dev(rows.ptr, D, n)
-    var = np.maximum(np.diag(g) / n - (s / n) ** 2, 0.0)
+    var = np.maximum(_column_moments(rows), 0.0)
     tol_abs = float(var.mean() * tol)
     best = None
     for _ in range(max(runs, 1)):
