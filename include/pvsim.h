@@ -315,6 +315,40 @@ int pvs_csr_spmm_f64_dev(pvs_ctx* ctx, int64_t n, const int64_t* d_indptr, const
 /* dst[c][r] = src[r][c], float64 (block Gram matrices through pvs_cosine_f64_dev with unit inverse norms). */
 int pvs_transpose_f64_dev(pvs_ctx* ctx, const double* d_src, int64_t rows, int64_t cols, double* d_dst);
 
+/* ---------------------------------------------------------------- dense SIFT: pixels -> local descriptors
+ * SIFT descriptors on a regular grid at fixed bin sizes, no detector and no orientation assignment (the dense descriptor of the
+ * Fisher-vector / VLAD literature; the reference extracts keypoint SIFT with OpenCV on the CPU, pyvisim/features/_features.py:54-115).
+ * Per bin size s (pixels): gray = 0.299 R + 0.587 G + 0.114 B; separable Gaussian, sigma = s/6, radius ceil(4 sigma), replicated
+ * borders; central-difference gradient (one-sided at the borders); magnitude split linearly between the two nearest of 8
+ * orientation planes; 4 x 4 spatial bins with centres s apart and the triangular window w(d) = 1 - |d|/s; then
+ * L2-normalise, clamp at 0.2, renormalise.  Descriptor origins x0 = s - 1 + a*step <= W - 4s (likewise y0); rows are ordered by
+ * (size, y0, x0), elements by (j*4 + i)*8 + o; the frame of a row is (x0 + 1.5 s, y0 + 1.5 s, s).
+ * pvs_dsift_count / pvs_dsift_frames are host arithmetic (no device needed): rows of one H x W image and their frames float32 [n][3]. */
+typedef enum {
+  PVS_PIX_U8_RGB = 0,  /* uint8 [H][W][3]   */
+  PVS_PIX_U8_GRAY = 1, /* uint8 [H][W]      */
+  PVS_PIX_F32_RGB = 2, /* float32 [H][W][3], 0..255 */
+  PVS_PIX_F32_GRAY = 3 /* float32 [H][W],    0..255 */
+} pvs_pixel_kind;
+typedef enum {
+  PVS_DSIFT_U8 = 0,     /* uint8 rows min(255, floor(512 v + 0.5)): OpenCV's scale, feeds PVS_DESC_U8_ROOTSIFT */
+  PVS_DSIFT_F32 = 1,    /* float32 rows v (normalised, clamped, renormalised) */
+  PVS_DSIFT_F32_RAW = 2, /* float32 accumulators before normalisation */
+  PVS_DSIFT_F32_QUANT = 3 /* the integers of PVS_DSIFT_U8 stored as float32 (plain SIFT rows for PVS_DESC_F32) */
+} pvs_dsift_out;
+int pvs_dsift_count(int H, int W, int step, const int32_t* sizes, int n_sizes, int64_t* count);
+int pvs_dsift_frames(int H, int W, int step, const int32_t* sizes, int n_sizes, float* frames /*[capacity][3]*/, int64_t capacity);
+/* A batch of images of mixed sizes in one device buffer.  h_hw: HOST int32 [n_images][2] = (H, W); h_pix_offsets: HOST int64
+ * [n_images], the first element of each image in d_pixels counted in elements of the pixel type (NULL: images packed back to back).
+ * d_out: [out_rows][128] of the output kind (16-byte aligned); d_row_offsets: DEVICE int64 [n_images + 1], written by the call
+ * (CSR over the rows, the `d_offsets` of the encode entry points).  A row whose norm is <= contrast_threshold is all zeros.  An
+ * image too small for a size contributes no rows for it.  Bin sizes whose tile does not fit the LDS (s > 18) -> PVS_ERR_UNSUPPORTED.
+ * n_images == 0 is a no-op: nothing is written, d_row_offsets included.  step may be any positive int (beyond the image: one origin
+ * per axis).  Enqueues on the context's stream and does not wait for it. */
+int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, const int32_t* h_hw, const int64_t* h_pix_offsets,
+                  int64_t n_images, int step, const int32_t* sizes, int n_sizes, double contrast_threshold, int out_kind,
+                  void* d_out, int64_t out_rows, int64_t* d_row_offsets);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm, 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

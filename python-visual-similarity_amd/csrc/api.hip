@@ -186,6 +186,10 @@ PVS_EXPORT int pvs_destroy(pvs_ctx* ctx) {
   for (auto& kv : ctx->block_cache) (void)hipFree(kv.second);
   ctx->block_cache.clear();
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
+  for (int i = 0; i < pvs_ctx::DSIFT_RING; ++i) {
+    if (ctx->dsift_h[i]) (void)hipHostFree(ctx->dsift_h[i]);
+    if (ctx->dsift_ev[i]) (void)hipEventDestroy(ctx->dsift_ev[i]);
+  }
   for (int i = 0; i < pvs_ctx::NWS; ++i)
     if (ctx->ws[i]) hipFree(ctx->ws[i]);
   for (auto& p : ctx->gemm_plan)

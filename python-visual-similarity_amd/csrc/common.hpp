@@ -62,7 +62,8 @@ struct pvs_ctx {
   // 3 PCA projections, 4 materialised RootSIFT rows
   // 5 fp16 row copies (filtered top-k), 6 filtered top-k lists / candidates
   // 7 row norms of the neighbour search, 8 float64 row copies of the neighbour search (neighbors.hip)
-  static constexpr int NWS = 9;
+  // 9 per-image table of the dense SIFT extractor (dsift.hip)
+  static constexpr int NWS = 10;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
   // cached tile lists of the similarity GEMM, one per GEMM model (cosine.hip): a context is one device + one stream, so the
@@ -90,6 +91,13 @@ struct pvs_ctx {
   size_t block_cache_bytes = 0;
   void* h_stage = nullptr;                        // pinned host staging block for small device -> host results (training statistics)
   size_t h_stage_bytes = 0;
+  // pinned blocks the dense SIFT entry point builds its per-image table in (dsift.hip): a ring, each block guarded by the event
+  // recorded behind the copies that read it, so the entry point never waits for the stream in steady state
+  static constexpr int DSIFT_RING = 4;
+  void* dsift_h[DSIFT_RING] = {};
+  size_t dsift_h_bytes[DSIFT_RING] = {};
+  hipEvent_t dsift_ev[DSIFT_RING] = {};
+  int dsift_next = 0;
   double t_total[PVS_TIMER_SLOTS] = {0};
   int64_t t_count[PVS_TIMER_SLOTS] = {0};
 };

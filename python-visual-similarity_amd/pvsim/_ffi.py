@@ -21,6 +21,8 @@ _EXC = {PVS_ERR_INVALID: ValueError, PVS_ERR_NO_DEVICE: RuntimeError, PVS_ERR_OO
 
 DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT = 0, 1, 2
 OPT_ASSIGN_PREFILTER, OPT_VLAD_PATH, OPT_TOPK_SELECT_ONLY, OPT_AGG_VARIANT, OPT_FISHER_SCALE = 0, 1, 2, 3, 4      # pvs_option
+PIX_U8_RGB, PIX_U8_GRAY, PIX_F32_RGB, PIX_F32_GRAY = 0, 1, 2, 3          # pvs_pixel_kind
+DSIFT_U8, DSIFT_F32, DSIFT_F32_RAW, DSIFT_F32_QUANT = 0, 1, 2, 3                         # pvs_dsift_out
 VLAD_PATH_AUTO, VLAD_PATH_GATHER, VLAD_PATH_STREAM, VLAD_PATH_FUSED = 0, 1, 2, 3
 TIMER_NAMES = ("assign", "aggregate", "cosine_gemm", "topk", "fisher_posterior", "fisher_moments", "misc", "rescore")
 
@@ -104,6 +106,9 @@ SIGNATURES = {
     "pvs_l2_radius_fill_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _int, C.c_double, _vp, _vp, _vp],
     "pvs_csr_spmm_f64_dev": [_vp, _i64, _vp, _vp, _vp, _vp, _int, C.c_double, _vp, _vp, C.c_double, _vp],
     "pvs_transpose_f64_dev": [_vp, _vp, _i64, _i64, _vp],
+    "pvs_dsift_count": [_int, _int, _int, _vp, _int, _vp],
+    "pvs_dsift_frames": [_int, _int, _int, _vp, _int, _vp, _i64],
+    "pvs_dsift_dev": [_vp, _vp, _int, _vp, _vp, _i64, _int, _vp, _int, C.c_double, _int, _vp, _i64, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

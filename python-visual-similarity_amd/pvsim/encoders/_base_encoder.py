@@ -122,6 +122,17 @@ _CLUSTERING_TO_PCA_MAPPING = {
 }
 
 
+def _read_rgb(path: str) -> np.ndarray:
+    """(H, W, 3) uint8 RGB pixels of an image file: OpenCV when present, Pillow otherwise."""
+    try:
+        import cv2
+    except ImportError:
+        from PIL import Image
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB"))
+    return cv2.cvtColor(cv2.imread(path), cv2.COLOR_BGR2RGB)
+
+
 def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and type(x).__name__ == "Tensor"
 
@@ -336,8 +347,60 @@ class ImageEncoderBase(SimilarityMetric):
             outs.append(self._encode_device(feats.data_ptr(), offsets.data_ptr(), b, b * n))
         return np.vstack(outs)
 
-    def _encode_device(self, d_desc: int, d_offsets: int, n_images: int, total_desc: int) -> np.ndarray:
+    def _encode_device(self, d_desc: int, d_offsets: int, n_images: int, total_desc: int, kind: int = DESC_F32) -> np.ndarray:
         raise NotImplementedError
+
+    def _device_descriptors(self, images):
+        """Extractors that compute their descriptors on the GPU (`device_descriptors(images, ctx)`, e.g. DenseSIFT /
+        DenseRootSIFT) leave the packed rows and their CSR offsets on the device; the encoder kernels read them there (uint8
+        rows with the RootSIFT tail fused into the load for DESC_U8_ROOTSIFT; a PCA table takes either kind).  Descriptors
+        never visit the host.  None when the extractor has no such method or lives on another context."""
+        fx = self.feature_extractor
+        if not hasattr(fx, "device_descriptors"):
+            return None
+        fx_ctx = getattr(fx, "_ctx", None)
+        if fx_ctx is not None and fx_ctx is not self.context:
+            return None
+        if _is_torch_tensor(images):
+            raise RuntimeError("Torch images are not supported yet.")
+        if isinstance(images, np.ndarray) and images.ndim == 3:
+            images = [images]
+        outs, empty = [], False
+        for chunk in self._image_chunks(images):
+            # strict_compat: one image without rows turns the whole result into the reference's single zero vector
+            empty = empty or (self.strict_compat and any(fx.count(*im.shape[:2]) == 0 for im in chunk))
+            if empty:
+                continue                      # keep draining the input, encode nothing more
+            rows, offs, n_images, total, kind, _ = fx.device_descriptors(chunk, self.context)
+            try:
+                outs.append(self._encode_device(rows.ptr, offs.ptr, n_images, total, kind))
+            finally:
+                rows.free()
+                offs.free()
+        if empty:
+            return self._empty_quirk()
+        if not outs:
+            raise ValueError("need at least one array to concatenate")
+        return self._shape_output(np.vstack(outs))
+
+    _CHUNK_IMAGES, _CHUNK_PIXEL_BYTES = 256, 256 << 20
+
+    @classmethod
+    def _image_chunks(cls, images):
+        """Consecutive runs of the input, pulled lazily (a generator of decoded files is never held as a whole): at most
+        _CHUNK_IMAGES images and _CHUNK_PIXEL_BYTES of pixels (as float32) per run, and a run never mixes gray (H, W) with
+        colour (H, W, 3) images, which one extraction launch cannot.  Rows do not depend on how the input is cut."""
+        chunk, nbytes = [], 0
+        for im in images:
+            size = int(np.prod(np.shape(im))) * 4
+            if chunk and (len(chunk) >= cls._CHUNK_IMAGES or nbytes + size > cls._CHUNK_PIXEL_BYTES
+                          or np.ndim(im) != np.ndim(chunk[0])):
+                yield chunk
+                chunk, nbytes = [], 0
+            chunk.append(im)
+            nbytes += size
+        if chunk:
+            yield chunk
 
     def encode(self, images: Iterable[np.ndarray] | np.ndarray) -> np.ndarray:
         """(N, L) encodings of one image (H, W, 3) or an iterable of images."""
@@ -346,6 +409,9 @@ class ImageEncoderBase(SimilarityMetric):
             out = self._device_features(images)
             if out is not None:
                 return self._shape_output(out)
+        out = self._device_descriptors(images)
+        if out is not None:
+            return out
         descs, kind = self._gather_descriptors(images)
         if not descs:
             raise ValueError("need at least one array to concatenate")   # np.vstack([]) in the reference
@@ -411,9 +477,13 @@ class ImageEncoderBase(SimilarityMetric):
 
     @_tupleize_first_arg
     def generate_encoding_map(self, image_paths: Iterable[str], /) -> dict[str, np.ndarray]:
-        """{image_path: encoded_vector} in input order (duplicates collapse, as in a dict)."""
-        import cv2  # image decoding is OpenCV's job in the reference too (_base_encoder.py:358)
-        images = (cv2.cvtColor(cv2.imread(path), cv2.COLOR_BGR2RGB) for path in image_paths)
+        """{image_path: encoded_vector} in input order (duplicates collapse, as in a dict).
+
+        The files are decoded by OpenCV when it is installed (as in the reference, _base_encoder.py:358) and by Pillow
+        otherwise: `Image.open(p).convert("RGB")` gives the pixels of `cvtColor(imread(p), COLOR_BGR2RGB)` for lossless
+        formats (PNG, BMP, ...); JPEG decoders may differ in rounding, so encodings of JPEG files can differ slightly between
+        the two."""
+        images = (_read_rgb(path) for path in image_paths)
         return dict(zip(image_paths, self.encode(images)))
 
     def similarity_score(self, images1, images2) -> np.ndarray:

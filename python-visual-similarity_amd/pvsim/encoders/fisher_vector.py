@@ -67,13 +67,13 @@ class FisherVectorEncoder(ImageEncoderBase):
         return self.context.fisher_encode(g, packed, offsets, kind, self.power_norm_weight, self.norm_order,
                                           self.epsilon, pca)
 
-    def _encode_device(self, d_desc, d_offsets, n_images, total_desc):
+    def _encode_device(self, d_desc, d_offsets, n_images, total_desc, kind=DESC_F32):
         g, pca = self._device_tables()
         ctx = self.context
         L = g.K + 2 * g.K * g.D
         buf = ctx.buffer(n_images * L * 8)
         try:
-            ctx.fisher_encode_dev(g, d_desc, DESC_F32, d_offsets, n_images, total_desc, buf.ptr, 1, self.power_norm_weight,
+            ctx.fisher_encode_dev(g, d_desc, kind, d_offsets, n_images, total_desc, buf.ptr, 1, self.power_norm_weight,
                                   self.norm_order, self.epsilon, pca)
             return buf.download((n_images, L), np.float64)      # blocks until the result is on the host
         finally:

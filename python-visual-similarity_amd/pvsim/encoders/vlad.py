@@ -59,13 +59,13 @@ class VLADEncoder(ImageEncoderBase):
         return self.context.vlad_encode(cb, packed, offsets, kind, self.power_norm_weight, self.norm_order,
                                         self.epsilon, pca)
 
-    def _encode_device(self, d_desc, d_offsets, n_images, total_desc):
+    def _encode_device(self, d_desc, d_offsets, n_images, total_desc, kind=DESC_F32):
         cb, pca = self._device_tables()
         ctx = self.context
         L = cb.K * cb.D
         buf = ctx.buffer(n_images * L * 4)
         try:
-            ctx.vlad_encode_dev(cb, d_desc, DESC_F32, d_offsets, n_images, total_desc, buf.ptr, self.power_norm_weight,
+            ctx.vlad_encode_dev(cb, d_desc, kind, d_offsets, n_images, total_desc, buf.ptr, self.power_norm_weight,
                                 self.norm_order, self.epsilon, pca)
             return buf.download((n_images, L), np.float32)
         finally:

@@ -12,7 +12,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT, check, norm_params, ptr
 
-__all__ = ["Context", "default_context", "pack_descriptors", "DESC_F32", "DESC_F32_ROOTSIFT", "DESC_U8_ROOTSIFT"]
+__all__ = ["Context", "default_context", "pack_descriptors", "dsift_count", "dsift_frames", "DESC_F32", "DESC_F32_ROOTSIFT", "DESC_U8_ROOTSIFT"]
 
 
 def pack_descriptors(desc_list, dim: int, dtype=np.float32):
@@ -27,6 +27,22 @@ def pack_descriptors(desc_list, dim: int, dtype=np.float32):
                 raise RuntimeError(f"descriptor dimension {d.shape[1]} does not match the model input dimension {dim}")
             packed[o:o + d.shape[0]] = d
     return packed, offsets
+
+
+def dsift_count(h: int, w: int, step: int, sizes) -> int:
+    """pvs_dsift_count: descriptor rows of one h x w image (host arithmetic, no device)."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1)
+    n = C.c_int64()
+    check(_ffi.lib().pvs_dsift_count(int(h), int(w), int(step), ptr(sizes) if sizes.size else None, sizes.size, C.byref(n)))
+    return int(n.value)
+
+
+def dsift_frames(h: int, w: int, step: int, sizes) -> np.ndarray:
+    """pvs_dsift_frames: (n, 3) float32 rows (x centre, y centre, bin size), in descriptor order."""
+    sizes = np.ascontiguousarray(sizes, dtype=np.int32).reshape(-1)
+    out = np.empty((dsift_count(h, w, step, sizes), 3), dtype=np.float32)
+    check(_ffi.lib().pvs_dsift_frames(int(h), int(w), int(step), ptr(sizes), sizes.size, ptr(out), out.shape[0]))
+    return out
 
 
 class _Handle:
@@ -439,6 +455,17 @@ class Context:
 
     def transpose_f64_dev(self, d_src, rows, cols, d_dst):
         check(_ffi.lib().pvs_transpose_f64_dev(self.handle, ptr(d_src), rows, cols, ptr(d_dst)))
+
+    # ------------------------------------------------------------------ dense SIFT (dsift.hip)
+    def dsift_dev(self, d_pixels, pixel_kind, hw, pix_offsets, step, sizes, contrast_threshold, out_kind, d_out, out_rows,
+                  d_row_offsets):
+        """pvs_dsift_dev: hw host int32 (B, 2), pix_offsets host int64 (B,) or None, sizes host int32; everything else device."""
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        po = None if pix_offsets is None else np.ascontiguousarray(pix_offsets, dtype=np.int64)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int32)
+        check(_ffi.lib().pvs_dsift_dev(self.handle, ptr(d_pixels), int(pixel_kind), ptr(hw), ptr(po), hw.shape[0], int(step),
+                                       ptr(sizes), sizes.shape[0], float(contrast_threshold), int(out_kind), ptr(d_out),
+                                       int(out_rows), ptr(d_row_offsets)))
 
     # ------------------------------------------------------------------ vocabulary training (one device pass each)
     def buffer(self, nbytes: int) -> "DeviceBuffer":

@@ -5,6 +5,10 @@ float descriptors plus `.output_dim`.
                     is imported lazily, so the classes exist without cv2 and fail only when called.  RootSIFT
                     additionally exposes `raw(image)` so that the encoders can hand the *raw* uint8 SIFT rows
                     to the GPU and fuse the RootSIFT tail (d /= sum+1e-7; sqrt, _features.py:112-114) there.
+  DenseSIFT /       SIFT descriptors on a regular grid at fixed bin sizes, computed from the pixels by the HIP kernel of
+  DenseRootSIFT     csrc/dsift.hip: no detector, no OpenCV.  They mirror SIFT / RootSIFT (integer valued
+                    float32 rows 0..255; `raw(image)` + `fused_rootsift`), and `device_descriptors(images, ctx)` leaves a
+                    whole batch's rows on the device for the encoders.
   Lambda            any user function (the descriptor-level door used by tests and synthetic benchmarks).
   DeepConvFeature   conv feature maps of a torch model on PyTorch-ROCm (torch is plumbing here).  torchvision
                     is absent offline, so the default network is an own VGG16 `features` stack with RANDOM
@@ -103,6 +107,154 @@ class RootSIFT(FeatureExtractorBase):
 
     def __repr__(self):
         return f"RootSIFT(output_dim={self.output_dim})"
+
+
+class DenseSIFT(FeatureExtractorBase):
+    """Dense SIFT (n, 128): descriptors at every `step` pixels for each bin size in `sizes` (pixels per spatial bin), integer
+    valued float32 rows on OpenCV's 0..255 scale like `SIFT`.  The definition is DESIGN.md section 9; the work is done by
+    pvs_dsift_dev on the GPU.  Rows are ordered by (size, y, x); `frames(h, w)` gives their (x, y, size)."""
+
+    def __init__(self, step: int = 16, sizes=(4, 8), contrast_threshold: float = 0.0, ctx=None):
+        super().__init__()
+        if isinstance(step, bool) or int(step) != step or step < 1:
+            raise ValueError(f"step must be a positive integer, got {step!r}")
+        sizes = tuple(sizes)
+        if not sizes:
+            raise ValueError("sizes must hold at least one bin size")
+        for s in sizes:
+            if isinstance(s, bool) or int(s) != s or s < 1:
+                raise ValueError(f"bin sizes must be positive integers, got {s!r}")
+        if not contrast_threshold >= 0:
+            raise ValueError(f"contrast_threshold must be >= 0, got {contrast_threshold!r}")
+        self.step = int(step)
+        self.sizes = tuple(int(s) for s in sizes)
+        self.contrast_threshold = float(contrast_threshold)
+        self._ctx = ctx
+        self._output_dim = 128
+
+    @property
+    def output_dim(self) -> int:
+        return self._output_dim
+
+    @property
+    def context(self):
+        if self._ctx is None:
+            from ..engine import default_context
+            self._ctx = default_context()
+        return self._ctx
+
+    def count(self, h: int, w: int) -> int:
+        """Descriptor rows of an h x w image."""
+        from ..engine import dsift_count
+        return dsift_count(h, w, self.step, self.sizes)
+
+    def frames(self, h: int, w: int) -> np.ndarray:
+        """(n, 3) float32: x centre, y centre and bin size of every row of an h x w image."""
+        from ..engine import dsift_frames
+        return dsift_frames(h, w, self.step, self.sizes)
+
+    @staticmethod
+    def _pixel_kind(images):
+        """uint8 images are uploaded as they are, everything else as float32; one kind per batch."""
+        from .._ffi import PIX_F32_GRAY, PIX_F32_RGB, PIX_U8_GRAY, PIX_U8_RGB
+        gray = {im.ndim == 2 for im in images}
+        if len(gray) != 1:
+            raise ValueError("a batch must be all gray (H, W) or all colour (H, W, 3) images")
+        u8 = all(im.dtype == np.uint8 for im in images)
+        if gray.pop():
+            return (PIX_U8_GRAY if u8 else PIX_F32_GRAY), (np.uint8 if u8 else np.float32)
+        return (PIX_U8_RGB if u8 else PIX_F32_RGB), (np.uint8 if u8 else np.float32)
+
+    def device_descriptors(self, images, ctx=None, out_kind=None, _validated=False):
+        """Descriptors of a batch of images (mixed sizes allowed), left on the device:
+        -> (rows DeviceBuffer, offsets DeviceBuffer (int64, B+1), n_images, total rows, descriptor kind, host offsets).
+        The rows are uint8 (kind DESC_U8_ROOTSIFT for DenseRootSIFT: the encoders fuse the RootSIFT tail into their load) or,
+        for DenseSIFT, the same integers as float32 (kind DESC_F32); `out_kind` (a pvs_dsift_out value) overrides the row format.
+        All images of one call must be gray (H, W) or all colour (H, W, 3): the kernel reads one pixel format per launch
+        (the encoders cut their input into such runs).  The caller owns both buffers (`.free()`)."""
+        from .._ffi import DSIFT_F32_QUANT, DSIFT_U8
+        from .._utils import is_numpy_image
+        from ..engine import DESC_F32, DESC_U8_ROOTSIFT
+        images = [images] if isinstance(images, np.ndarray) and images.ndim in (2, 3) and not (
+            images.ndim == 3 and images.shape[2] != 3) else list(images)
+        if not images:
+            raise ValueError("need at least one image")
+        for pos, im in enumerate(() if _validated else images):
+            if type(im).__module__.startswith("torch"):
+                raise TypeError("Torch images are not supported yet. Please convert to NumPy.")
+            is_numpy_image(im, pos)
+        ctx = ctx if ctx is not None else self.context          # images are refused before anything touches the device
+        pix_kind, dt = self._pixel_kind(images)
+        fused = getattr(self, "fused_rootsift", False)
+        kind = DESC_U8_ROOTSIFT if fused else DESC_F32
+        if out_kind is None:            # what the encoders read: uint8 rows, or the same integers as float32 for plain SIFT
+            out_kind = DSIFT_U8 if fused else DSIFT_F32_QUANT
+        hw = np.array([im.shape[:2] for im in images], dtype=np.int32).reshape(-1, 2)
+        counts = np.array([self.count(h, w) for h, w in hw], dtype=np.int64)
+        h_off = np.zeros(len(images) + 1, dtype=np.int64)
+        np.cumsum(counts, out=h_off[1:])
+        total = int(h_off[-1])
+        flat = np.concatenate([np.ascontiguousarray(im, dtype=dt).reshape(-1) for im in images])
+        pix = ctx.buffer(flat.nbytes).upload(flat)
+        rows = offs = None
+        try:
+            rows = ctx.buffer(max(total, 1) * 128 * (1 if out_kind == DSIFT_U8 else 4))
+            offs = ctx.buffer(h_off.nbytes)
+            ctx.dsift_dev(pix.ptr, pix_kind, hw, None, self.step, self.sizes, self.contrast_threshold, out_kind, rows.ptr,
+                          total, offs.ptr)
+            ctx.sync()                      # the pixel block goes back to the context's cache: its readers must be done
+        except Exception:
+            for b in (rows, offs):
+                if b is not None:
+                    b.free()
+            raise
+        finally:
+            pix.free()
+        return rows, offs, len(images), total, kind, h_off
+
+    def _rows(self, image, out_kind, dtype, validated=False):
+        rows, offs, _, total, _, _ = self.device_descriptors([image], None, out_kind, _validated=validated)
+        try:
+            return rows.download((total, 128), dtype)
+        finally:
+            rows.free()
+            offs.free()
+
+    def raw(self, image: np.ndarray) -> np.ndarray:
+        """The uint8 rows (n, 128) as the kernel writes them."""
+        from .._ffi import DSIFT_U8
+        return self._rows(image, DSIFT_U8, np.uint8)          # device_descriptors validates the image
+
+    def descriptors(self, image: np.ndarray, normalised: bool = True) -> np.ndarray:
+        """float32 rows before quantisation: the normalised v (default) or the raw accumulators."""
+        from .._ffi import DSIFT_F32, DSIFT_F32_RAW
+        return self._rows(image, DSIFT_F32 if normalised else DSIFT_F32_RAW, np.float32)
+
+    @_check_output_shape
+    def __call__(self, image: np.ndarray, /) -> np.ndarray:
+        from .._ffi import DSIFT_U8
+        super().__call__(image)
+        return self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
+
+    def __repr__(self):
+        return (f"{type(self).__name__}(step={self.step}, sizes={self.sizes}, contrast_threshold={self.contrast_threshold}, "
+                f"output_dim={self.output_dim})")
+
+
+class DenseRootSIFT(DenseSIFT):
+    """Dense SIFT + Hellinger normalisation (d /= sum + 1e-7; sqrt), the dense counterpart of `RootSIFT`.  The encoders take
+    its uint8 rows on the device and fuse the RootSIFT tail into their load (kind DESC_U8_ROOTSIFT)."""
+    fused_rootsift = True
+
+    @_check_output_shape
+    def __call__(self, image: np.ndarray, /) -> np.ndarray:
+        from .._ffi import DSIFT_U8
+        FeatureExtractorBase.__call__(self, image)
+        descriptors = self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
+        if descriptors.shape[0]:
+            descriptors /= (descriptors.sum(axis=1, keepdims=True) + 1e-7)
+            descriptors = np.sqrt(descriptors)
+        return descriptors
 
 
 class Lambda(FeatureExtractorBase):
