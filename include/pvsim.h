@@ -38,7 +38,8 @@ typedef enum {
   PVS_ERR_NO_DEVICE = 2,   /* no HIP device / HIP runtime error -> RuntimeError */
   PVS_ERR_OOM = 3,         /* device allocation failed          -> MemoryError  */
   PVS_ERR_UNSUPPORTED = 4, /* shape / option not implemented    -> NotImplementedError */
-  PVS_ERR_DIM = 5          /* dimension mismatch                -> RuntimeError (as the reference raises) */
+  PVS_ERR_DIM = 5,         /* dimension mismatch                -> RuntimeError (as the reference raises) */
+  PVS_ERR_CAPACITY = 6     /* a data-dependent output does not fit; the true size was returned -> pvsim.CapacityError */
 } pvs_status;
 
 /* How descriptor rows are stored, and whether the RootSIFT tail
@@ -348,6 +349,29 @@ int pvs_dsift_frames(int H, int W, int step, const int32_t* sizes, int n_sizes, 
 int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, const int32_t* h_hw, const int64_t* h_pix_offsets,
                   int64_t n_images, int step, const int32_t* sizes, int n_sizes, double contrast_threshold, int out_kind,
                   void* d_out, int64_t out_rows, int64_t* d_row_offsets);
+
+/* ---------------------------------------------------------------- keypoint SIFT: pixels -> detected, oriented descriptors
+ * Lowe's scale-space SIFT (IJCV 2004) with OpenCV's parameter names and defaults -- not a bit-for-bit clone of cv2.SIFT.  Gray and
+ * pixel kinds as for dense SIFT; first octave = the 2x bilinearly enlarged image when `upsample`; octaves while min(H_o, W_o) >= 16;
+ * n_octave_layers + 3 Gaussian images per octave by incremental blur (radius ceil(4 sigma), replicated borders); strict 3 x 3 x 3
+ * extrema of the DoG above 0.5 * contrast_threshold / n_octave_layers * 255, five pixels off the border; up to five steps of the 3-D
+ * quadratic; |interpolated value| >= 255 * contrast_threshold / n_octave_layers; edge test with edge_threshold; 36-bin orientation
+ * histogram, one row per peak >= 0.8 max; 4 x 4 x 8 descriptor in the rotated frame, then the tail of dense SIFT.  Rows are ordered
+ * by (image, octave, layer, y, x of the integer extremum, orientation peak ascending); frames are float32
+ * (x, y, size = diameter, angle in degrees from +x towards +y, |response|, octave) in input-image coordinates.  nfeatures > 0 keeps
+ * the nfeatures strongest rows of each image by |response| (ties by row order), in the same order.
+ * pvs_sift_workspace is host arithmetic: bytes of one image's Gaussian pyramid and a (very loose) upper bound of its rows.
+ * pvs_sift_dev: arguments as pvs_dsift_dev; the row count is data dependent, so the call writes at most capacity_rows rows (and
+ * frames, when d_frames is not NULL) but always the true CSR d_row_offsets (DEVICE int64 [n_images + 1]) and *h_total_rows (HOST).
+ * If the total exceeds the capacity it returns PVS_ERR_CAPACITY with both valid: the rows below the capacity are written, nothing
+ * beyond it; call again with a larger buffer.  Unlike the other _dev entry points this one WAITS for the stream (it returns the
+ * total).  Batches are processed in chunks whose pyramids stay under 256 MiB; a row's bits and place do not depend on the batch.
+ * n_images == 0 is a no-op: nothing is written, *h_total_rows included. */
+int pvs_sift_workspace(int H, int W, int n_octave_layers, int upsample, size_t* bytes, int64_t* max_rows);
+int pvs_sift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, const int32_t* h_hw, const int64_t* h_pix_offsets,
+                 int64_t n_images, int nfeatures, int n_octave_layers, double contrast_threshold, double edge_threshold, double sigma,
+                 int upsample, int out_kind, void* d_rows, int64_t capacity_rows, float* d_frames /*[capacity_rows][6] or NULL*/,
+                 int64_t* d_row_offsets, int64_t* h_total_rows);
 
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,

@@ -63,7 +63,8 @@ struct pvs_ctx {
   // 5 fp16 row copies (filtered top-k), 6 filtered top-k lists / candidates
   // 7 row norms of the neighbour search, 8 float64 row copies of the neighbour search (neighbors.hip)
   // 9 per-image table of the dense SIFT extractor (dsift.hip)
-  static constexpr int NWS = 10;
+  // 10 Gaussian pyramids of one chunk, 11 image table / block counts, 12 candidates and keypoints of the keypoint SIFT extractor (sift.hip)
+  static constexpr int NWS = 13;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
   // cached tile lists of the similarity GEMM, one per GEMM model (cosine.hip): a context is one device + one stream, so the

@@ -10,6 +10,7 @@ fallback.  Importing the package does not touch the GPU; the first computation d
 """
 from .engine import Context, default_context, pack_descriptors
 from . import models
+from ._errors import CapacityError
 
 __version__ = "0.1.0"
-__all__ = ["encoders", "features", "eval", "models", "Context", "default_context", "pack_descriptors"]
+__all__ = ["encoders", "features", "eval", "models", "Context", "default_context", "pack_descriptors", "CapacityError"]

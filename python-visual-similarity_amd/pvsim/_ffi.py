@@ -11,13 +11,15 @@ import threading
 
 import numpy as np
 
+from ._errors import CapacityError
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PVSIM_LIB", os.path.join(_HERE, "libpvsim_hip.so"))
 
 # pvs_status -> Python exception (same exception classes as the reference raises)
-PVS_OK, PVS_ERR_INVALID, PVS_ERR_NO_DEVICE, PVS_ERR_OOM, PVS_ERR_UNSUPPORTED, PVS_ERR_DIM = range(6)
+PVS_OK, PVS_ERR_INVALID, PVS_ERR_NO_DEVICE, PVS_ERR_OOM, PVS_ERR_UNSUPPORTED, PVS_ERR_DIM, PVS_ERR_CAPACITY = range(7)
 _EXC = {PVS_ERR_INVALID: ValueError, PVS_ERR_NO_DEVICE: RuntimeError, PVS_ERR_OOM: MemoryError,
-        PVS_ERR_UNSUPPORTED: NotImplementedError, PVS_ERR_DIM: RuntimeError}
+        PVS_ERR_UNSUPPORTED: NotImplementedError, PVS_ERR_DIM: RuntimeError, PVS_ERR_CAPACITY: CapacityError}
 
 DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT = 0, 1, 2
 OPT_ASSIGN_PREFILTER, OPT_VLAD_PATH, OPT_TOPK_SELECT_ONLY, OPT_AGG_VARIANT, OPT_FISHER_SCALE = 0, 1, 2, 3, 4      # pvs_option
@@ -109,6 +111,9 @@ SIGNATURES = {
     "pvs_dsift_count": [_int, _int, _int, _vp, _int, _vp],
     "pvs_dsift_frames": [_int, _int, _int, _vp, _int, _vp, _i64],
     "pvs_dsift_dev": [_vp, _vp, _int, _vp, _vp, _i64, _int, _vp, _int, C.c_double, _int, _vp, _i64, _vp],
+    "pvs_sift_workspace": [_int, _int, _int, _int, C.POINTER(_sz), C.POINTER(_i64)],
+    "pvs_sift_dev": [_vp, _vp, _int, _vp, _vp, _i64, _int, _int, C.c_double, C.c_double, C.c_double, _int, _int, _vp, _i64, _vp,
+                     _vp, C.POINTER(_i64)],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

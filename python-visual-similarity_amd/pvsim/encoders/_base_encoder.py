@@ -368,11 +368,15 @@ class ImageEncoderBase(SimilarityMetric):
         outs, empty = [], False
         for chunk in self._image_chunks(images):
             # strict_compat: one image without rows turns the whole result into the reference's single zero vector
-            empty = empty or (self.strict_compat and any(fx.count(*im.shape[:2]) == 0 for im in chunk))
+            counted = hasattr(fx, "count")    # a detector's row count is known only after the extraction (h_off)
+            empty = empty or (self.strict_compat and counted and any(fx.count(*im.shape[:2]) == 0 for im in chunk))
             if empty:
                 continue                      # keep draining the input, encode nothing more
-            rows, offs, n_images, total, kind, _ = fx.device_descriptors(chunk, self.context)
+            rows, offs, n_images, total, kind, h_off = fx.device_descriptors(chunk, self.context)
             try:
+                if self.strict_compat and not counted and (np.diff(h_off) == 0).any():
+                    empty = True
+                    continue
                 outs.append(self._encode_device(rows.ptr, offs.ptr, n_images, total, kind))
             finally:
                 rows.free()

@@ -12,7 +12,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT, check, norm_params, ptr
 
-__all__ = ["Context", "default_context", "pack_descriptors", "dsift_count", "dsift_frames", "DESC_F32", "DESC_F32_ROOTSIFT", "DESC_U8_ROOTSIFT"]
+__all__ = ["Context", "default_context", "pack_descriptors", "dsift_count", "dsift_frames", "sift_workspace", "DESC_F32", "DESC_F32_ROOTSIFT", "DESC_U8_ROOTSIFT"]
 
 
 def pack_descriptors(desc_list, dim: int, dtype=np.float32):
@@ -43,6 +43,13 @@ def dsift_frames(h: int, w: int, step: int, sizes) -> np.ndarray:
     out = np.empty((dsift_count(h, w, step, sizes), 3), dtype=np.float32)
     check(_ffi.lib().pvs_dsift_frames(int(h), int(w), int(step), ptr(sizes), sizes.size, ptr(out), out.shape[0]))
     return out
+
+
+def sift_workspace(h: int, w: int, n_octave_layers: int = 3, upsample: bool = True):
+    """pvs_sift_workspace: (bytes of one h x w image's Gaussian pyramid, loose upper bound of its rows); host arithmetic."""
+    nbytes, rows = C.c_size_t(), C.c_int64()
+    check(_ffi.lib().pvs_sift_workspace(int(h), int(w), int(n_octave_layers), int(bool(upsample)), C.byref(nbytes), C.byref(rows)))
+    return int(nbytes.value), int(rows.value)
 
 
 class _Handle:
@@ -466,6 +473,23 @@ class Context:
         check(_ffi.lib().pvs_dsift_dev(self.handle, ptr(d_pixels), int(pixel_kind), ptr(hw), ptr(po), hw.shape[0], int(step),
                                        ptr(sizes), sizes.shape[0], float(contrast_threshold), int(out_kind), ptr(d_out),
                                        int(out_rows), ptr(d_row_offsets)))
+
+    # ------------------------------------------------------------------ keypoint SIFT (sift.hip)
+    def sift_dev(self, d_pixels, pixel_kind, hw, pix_offsets, nfeatures, n_octave_layers, contrast_threshold, edge_threshold, sigma,
+                 upsample, out_kind, d_rows, capacity_rows, d_frames, d_row_offsets) -> int:
+        """pvs_sift_dev: hw host int32 (B, 2), pix_offsets host int64 (B,) or None; rows, frames (or None) and row offsets on the
+        device.  Waits for the stream.  -> total rows; raises CapacityError (args[1] = the total) when they exceed capacity_rows."""
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        po = None if pix_offsets is None else np.ascontiguousarray(pix_offsets, dtype=np.int64)
+        total = C.c_int64(0)
+        status = _ffi.lib().pvs_sift_dev(self.handle, ptr(d_pixels), int(pixel_kind), ptr(hw), ptr(po), hw.shape[0], int(nfeatures),
+                                         int(n_octave_layers), float(contrast_threshold), float(edge_threshold), float(sigma),
+                                         int(bool(upsample)), int(out_kind), ptr(d_rows), int(capacity_rows), ptr(d_frames),
+                                         ptr(d_row_offsets), C.byref(total))
+        if status == _ffi.PVS_ERR_CAPACITY:
+            raise _ffi.CapacityError(_ffi.lib().pvs_last_error().decode("utf-8", "replace"), int(total.value))
+        check(status)
+        return int(total.value)
 
     # ------------------------------------------------------------------ vocabulary training (one device pass each)
     def buffer(self, nbytes: int) -> "DeviceBuffer":

@@ -1,3 +1,3 @@
-from ._features import SIFT, RootSIFT, DenseSIFT, DenseRootSIFT, DeepConvFeature, Lambda
+from ._features import SIFT, RootSIFT, DenseSIFT, DenseRootSIFT, KeypointSIFT, KeypointRootSIFT, DeepConvFeature, Lambda
 
-__all__ = ["SIFT", "RootSIFT", "DenseSIFT", "DenseRootSIFT", "DeepConvFeature", "Lambda"]
+__all__ = ["SIFT", "RootSIFT", "DenseSIFT", "DenseRootSIFT", "KeypointSIFT", "KeypointRootSIFT", "DeepConvFeature", "Lambda"]

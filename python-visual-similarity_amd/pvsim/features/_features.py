@@ -9,6 +9,9 @@ float descriptors plus `.output_dim`.
   DenseRootSIFT     csrc/dsift.hip: no detector, no OpenCV.  They mirror SIFT / RootSIFT (integer valued
                     float32 rows 0..255; `raw(image)` + `fused_rootsift`), and `device_descriptors(images, ctx)` leaves a
                     whole batch's rows on the device for the encoders.
+  KeypointSIFT /    keypoint SIFT computed from the pixels by csrc/sift.hip: Lowe's scale-space detector,
+  KeypointRootSIFT  orientation assignment and rotated descriptors with OpenCV's parameter names and defaults, without OpenCV (and
+                    not a bit-for-bit clone of it).  Same interface and device hand-off as the dense pair.
   Lambda            any user function (the descriptor-level door used by tests and synthetic benchmarks).
   DeepConvFeature   conv feature maps of a torch model on PyTorch-ROCm (torch is plumbing here).  torchvision
                     is absent offline, so the default network is an own VGG16 `features` stack with RANDOM
@@ -244,6 +247,175 @@ class DenseSIFT(FeatureExtractorBase):
 class DenseRootSIFT(DenseSIFT):
     """Dense SIFT + Hellinger normalisation (d /= sum + 1e-7; sqrt), the dense counterpart of `RootSIFT`.  The encoders take
     its uint8 rows on the device and fuse the RootSIFT tail into their load (kind DESC_U8_ROOTSIFT)."""
+    fused_rootsift = True
+
+    @_check_output_shape
+    def __call__(self, image: np.ndarray, /) -> np.ndarray:
+        from .._ffi import DSIFT_U8
+        FeatureExtractorBase.__call__(self, image)
+        descriptors = self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
+        if descriptors.shape[0]:
+            descriptors /= (descriptors.sum(axis=1, keepdims=True) + 1e-7)
+            descriptors = np.sqrt(descriptors)
+        return descriptors
+
+
+class KeypointSIFT(FeatureExtractorBase):
+    """Keypoint SIFT (n, 128) on the GPU: Lowe's scale-space detector (Gaussian pyramid, DoG extrema, sub-pixel refinement,
+    contrast and edge tests), orientation assignment and rotated 4 x 4 x 8 descriptors, integer valued float32 rows on OpenCV's
+    0..255 scale like `SIFT`.  OpenCV's parameter names and defaults, but NOT a bit-for-bit clone of cv2.SIFT: the definition is
+    DESIGN.md section 10 and the work is done by pvs_sift_dev.  Rows are ordered by (octave, layer, y, x of the extremum,
+    orientation); `keypoints(image)` gives their frames (x, y, size, angle, response, octave)."""
+
+    def __init__(self, nfeatures: int = 0, n_octave_layers: int = 3, contrast_threshold: float = 0.04, edge_threshold: float = 10,
+                 sigma: float = 1.6, upsample: bool = True, ctx=None):
+        super().__init__()
+        if isinstance(nfeatures, bool) or int(nfeatures) != nfeatures or nfeatures < 0:
+            raise ValueError(f"nfeatures must be a non-negative integer, got {nfeatures!r}")
+        if isinstance(n_octave_layers, bool) or int(n_octave_layers) != n_octave_layers or n_octave_layers < 1:
+            raise ValueError(f"n_octave_layers must be a positive integer, got {n_octave_layers!r}")
+        if not contrast_threshold >= 0:
+            raise ValueError(f"contrast_threshold must be >= 0, got {contrast_threshold!r}")
+        if not edge_threshold > 0:
+            raise ValueError(f"edge_threshold must be > 0, got {edge_threshold!r}")
+        if not (sigma > 0 and np.isfinite(sigma)):
+            raise ValueError(f"sigma must be a positive number, got {sigma!r}")
+        if not isinstance(upsample, (bool, np.bool_)):
+            raise ValueError(f"upsample must be a bool, got {upsample!r}")
+        self.nfeatures = int(nfeatures)
+        self.n_octave_layers = int(n_octave_layers)
+        self.contrast_threshold = float(contrast_threshold)
+        self.edge_threshold = float(edge_threshold)
+        self.sigma = float(sigma)
+        self.upsample = bool(upsample)
+        self._ctx = ctx
+        self._output_dim = 128
+        self._rows_per_pixel = 1.0 / 64.0        # capacity guess of the first call; grows with what the images gave
+
+    @property
+    def output_dim(self) -> int:
+        return self._output_dim
+
+    @property
+    def context(self):
+        if self._ctx is None:
+            from ..engine import default_context
+            self._ctx = default_context()
+        return self._ctx
+
+    _pixel_kind = staticmethod(DenseSIFT._pixel_kind)
+
+    def device_descriptors(self, images, ctx=None, out_kind=None, _validated=False, frames=False):
+        """Descriptors of a batch of images (mixed sizes allowed), left on the device:
+        -> (rows DeviceBuffer, offsets DeviceBuffer (int64, B+1), n_images, total rows, descriptor kind, host offsets), the tuple
+        of `DenseSIFT.device_descriptors`; with frames=True a seventh item, the DeviceBuffer of the (total, 6) float32 frames.
+        The row count depends on the images: the first call guesses a capacity and, when the rows do not fit, one retry with
+        the exact total follows (pvs_sift_dev reports it).  The caller owns the buffers (`.free()`)."""
+        from .._errors import CapacityError
+        from .._ffi import DSIFT_F32_QUANT, DSIFT_U8
+        from .._utils import is_numpy_image
+        from ..engine import DESC_F32, DESC_U8_ROOTSIFT
+        images = [images] if isinstance(images, np.ndarray) and images.ndim in (2, 3) and not (
+            images.ndim == 3 and images.shape[2] != 3) else list(images)
+        if not images:
+            raise ValueError("need at least one image")
+        for pos, im in enumerate(() if _validated else images):
+            if type(im).__module__.startswith("torch"):
+                raise TypeError("Torch images are not supported yet. Please convert to NumPy.")
+            is_numpy_image(im, pos)
+        ctx = ctx if ctx is not None else self.context
+        pix_kind, dt = self._pixel_kind(images)
+        fused = getattr(self, "fused_rootsift", False)
+        kind = DESC_U8_ROOTSIFT if fused else DESC_F32
+        if out_kind is None:
+            out_kind = DSIFT_U8 if fused else DSIFT_F32_QUANT
+        width = 128 * (1 if out_kind == DSIFT_U8 else 4)
+        hw = np.array([im.shape[:2] for im in images], dtype=np.int32).reshape(-1, 2)
+        n_pix = int((hw[:, 0].astype(np.int64) * hw[:, 1]).sum())
+        capacity = max(256, int(n_pix * self._rows_per_pixel))
+        if self.nfeatures:
+            capacity = min(capacity, self.nfeatures * len(images))
+        flat = np.concatenate([np.ascontiguousarray(im, dtype=dt).reshape(-1) for im in images])
+        pix = ctx.buffer(flat.nbytes).upload(flat)
+        rows = offs = frm = None
+        try:
+            offs = ctx.buffer((len(images) + 1) * 8)
+            for attempt in (0, 1):
+                rows = ctx.buffer(max(capacity, 1) * width)
+                frm = ctx.buffer(max(capacity, 1) * 24) if frames else None
+                try:
+                    total = ctx.sift_dev(pix.ptr, pix_kind, hw, None, self.nfeatures, self.n_octave_layers, self.contrast_threshold,
+                                         self.edge_threshold, self.sigma, self.upsample, out_kind, rows.ptr, capacity,
+                                         None if frm is None else frm.ptr, offs.ptr)
+                    break
+                except CapacityError as e:
+                    if attempt:
+                        raise
+                    rows.free()
+                    if frm is not None:
+                        frm.free()
+                    rows = frm = None
+                    capacity = int(e.args[1])
+            h_off = offs.download((len(images) + 1,), np.int64)
+        except Exception:
+            for b in (rows, offs, frm):
+                if b is not None:
+                    b.free()
+            raise
+        finally:
+            pix.free()                      # pvs_sift_dev has waited for the stream: nothing reads the pixels any more
+        self._rows_per_pixel = max(self._rows_per_pixel, 1.25 * total / max(n_pix, 1))
+        out = (rows, offs, len(images), total, kind, h_off)
+        return out + (frm,) if frames else out
+
+    def _rows(self, image, out_kind, dtype, validated=False, frames=False):
+        got = self.device_descriptors([image], None, out_kind, _validated=validated, frames=frames)
+        rows, offs, total = got[0], got[1], got[3]
+        try:
+            out = rows.download((total, 128), dtype)
+            return (got[6].download((total, 6), np.float32), out) if frames else out
+        finally:
+            rows.free()
+            offs.free()
+            if frames:
+                got[6].free()
+
+    def raw(self, image: np.ndarray) -> np.ndarray:
+        """The uint8 rows (n, 128) as the kernel writes them."""
+        from .._ffi import DSIFT_U8
+        return self._rows(image, DSIFT_U8, np.uint8)
+
+    def descriptors(self, image: np.ndarray, normalised: bool = True) -> np.ndarray:
+        """float32 rows before quantisation: the normalised v (default) or the raw accumulators."""
+        from .._ffi import DSIFT_F32, DSIFT_F32_RAW
+        return self._rows(image, DSIFT_F32 if normalised else DSIFT_F32_RAW, np.float32)
+
+    def detect_and_compute(self, image: np.ndarray):
+        """-> (frames (n, 6) float32: x, y, size, angle, response, octave; uint8 rows (n, 128))"""
+        from .._ffi import DSIFT_U8
+        return self._rows(image, DSIFT_U8, np.uint8, frames=True)
+
+    def keypoints(self, image: np.ndarray) -> np.ndarray:
+        """(n, 6) float32 frames in input-image coordinates: x, y, size (diameter), angle (degrees, from +x towards +y),
+        response (|interpolated DoG|), octave (0 = the first octave, which is the enlarged image when `upsample`)."""
+        return self.detect_and_compute(image)[0]
+
+    @_check_output_shape
+    def __call__(self, image: np.ndarray, /) -> np.ndarray:
+        from .._ffi import DSIFT_U8
+        super().__call__(image)
+        return self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
+
+    def __repr__(self):
+        return (f"{type(self).__name__}(nfeatures={self.nfeatures}, n_octave_layers={self.n_octave_layers}, "
+                f"contrast_threshold={self.contrast_threshold}, edge_threshold={self.edge_threshold}, sigma={self.sigma}, "
+                f"upsample={self.upsample}, output_dim={self.output_dim})")
+
+
+class KeypointRootSIFT(KeypointSIFT):
+    """Keypoint SIFT + Hellinger normalisation (d /= sum + 1e-7; sqrt): the OpenCV-free counterpart of `RootSIFT`, the extractor
+    the shipped vocabularies were trained with up to the differences between this definition and cv2.SIFT.
+    The encoders take its uint8 rows on the device and fuse the RootSIFT tail into their load (kind DESC_U8_ROOTSIFT)."""
     fused_rootsift = True
 
     @_check_output_shape
