@@ -373,6 +373,44 @@ int pvs_sift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, const int32
                  int upsample, int out_kind, void* d_rows, int64_t capacity_rows, float* d_frames /*[capacity_rows][6] or NULL*/,
                  int64_t* d_row_offsets, int64_t* h_total_rows);
 
+/* ---------------------------------------------------------------- spatial re-ranking: local matching + geometric verification
+ * The second stage of instance retrieval (Lowe 2004 section 7; Philbin et al. 2007): match the local descriptors of a query against
+ * each image of a shortlist, fit a transform to the matches, count the inliers.  The operands are what pvs_sift_dev / pvs_dsift_dev
+ * leave on the device: uint8 rows [rows][128] (PVS_DSIFT_U8, 16-byte aligned), float32 frames [rows][6] and the HOST int64 CSR
+ * offsets [n_images + 1] over the images of a set.  h_pairs: HOST int32 [n_pairs][2] = (image of set A, image of set B); repeats are
+ * allowed and the two sets may be one buffer.  The per-row results and the matches of pair p start at entry sum_{q<p} nA(q); one
+ * call covers every pair with a fixed number of launches.  n_pairs == 0 is a no-op.  All three enqueue on the context's stream and
+ * do not wait for it; what is written for a pair does not depend on the other pairs of the call.
+ *
+ * pvs_match_u8_dev: for row i of the A image  d_d1 = min_j |a_i - b_j|^2 over the rows of the B image (exact int32, at most
+ * 128 * 255^2), d_idx = that j (local to the image; ties: the lowest j), d_d2 = the smallest distance over j != d_idx (it may equal
+ * d_d1).  A B image with one row: d_d2 = INT32_MAX; with none: d_idx = -1, d_d1 = d_d2 = INT32_MAX.  An A image without rows writes
+ * nothing.  Dot products of the bytes re-centred by 128 on v_mfma_i32_32x32x32_i8; no rounding anywhere. */
+int pvs_match_u8_dev(pvs_ctx* ctx, const void* d_rows_a, const int64_t* h_off_a, int64_t n_images_a, const void* d_rows_b,
+                     const int64_t* h_off_b, int64_t n_images_b, const int32_t* h_pairs, int64_t n_pairs, int32_t* d_idx, int32_t* d_d1,
+                     int32_t* d_d2);
+/* Lowe's ratio test, the mutual check and the compaction.  Row i of pair p is kept iff d_idx >= 0, (double)d1 < ratio_sq * (double)d2
+ * (one float64 product and comparison; ratio_sq >= 0 comes from the caller) and, with mutual != 0, d_idx_rev[row d_idx of the B image]
+ * == i, where d_idx_rev is the d_idx of pvs_match_u8_dev called with A and B exchanged and the pair list transposed (entries at
+ * sum_{q<p} nB(q); NULL without mutual).  d_matches: int32 [sum nA][2] = (i, j) in ascending i from the pair's first entry;
+ * d_match_counts: int32 [n_pairs].  The order comes from a prefix sum, not from atomics. */
+int pvs_match_filter_dev(pvs_ctx* ctx, const int64_t* h_off_a, int64_t n_images_a, const int64_t* h_off_b, int64_t n_images_b,
+                         const int32_t* h_pairs, int64_t n_pairs, const int32_t* d_idx, const int32_t* d_d1, const int32_t* d_d2,
+                         const int32_t* d_idx_rev, double ratio_sq, int mutual, int32_t* d_matches, int32_t* d_match_counts);
+/* Exhaustive verification in float64.  A match g joins frame (x, y, size, angle) of A to one of B.  Match h is a hypothesis:
+ * sigma = size_b / size_a, phi = (angle_b - angle_a) pi / 180, A_h = sigma [[cos phi, -sin phi], [sin phi, cos phi]] anchored at its
+ * own points, r^2(h, g) = |A_h (p_a(g) - p_a(h)) - (p_b(g) - p_b(h))|^2; g is an inlier iff r^2 <= tol^2 (tol in pixels of the B image).
+ * Non-finite frames or size_a <= 0 give a hypothesis that counts 0.  The best hypothesis h* has the largest count (ties: the lowest
+ * h).  Then up to refine_rounds rounds on the inlier set S (|S| >= 3): centre both point sets on their means over S, C = sum a~ a~^T,
+ * stop if det C <= 1e-12 (tr C)^2, M = (sum b~ a~^T) C^-1, recount with r = M (p_a - mean_a) - (p_b - mean_b); the new model and set
+ * are adopted unless the count fell; stop when it fell or the set did not change.  Per pair: d_inliers int32, d_models float64 [6] =
+ * (M00, M01, t_x, M10, M11, t_y) with p_b ~ M p_a + t, d_best = h*, d_mask uint8 per match (at the pair's first entry; the entries
+ * beyond the pair's match count are not written).  No matches or no valid hypothesis: count 0, a zero model, h* = -1. */
+int pvs_verify_dev(pvs_ctx* ctx, const float* d_frames_a, const int64_t* h_off_a, int64_t n_images_a, const float* d_frames_b,
+                   const int64_t* h_off_b, int64_t n_images_b, const int32_t* h_pairs, int64_t n_pairs, const int32_t* d_matches,
+                   const int32_t* d_match_counts, double tol, int refine_rounds, int32_t* d_inliers, double* d_models, int32_t* d_best,
+                   uint8_t* d_mask);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm, 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

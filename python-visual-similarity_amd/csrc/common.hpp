@@ -64,7 +64,8 @@ struct pvs_ctx {
   // 7 row norms of the neighbour search, 8 float64 row copies of the neighbour search (neighbors.hip)
   // 9 per-image table of the dense SIFT extractor (dsift.hip)
   // 10 Gaussian pyramids of one chunk, 11 image table / block counts, 12 candidates and keypoints of the keypoint SIFT extractor (sift.hip)
-  static constexpr int NWS = 13;
+  // 13 tile / pair table, 14 float64 match points, 15 hypothesis counts and the trial mask of the spatial verification (match.hip)
+  static constexpr int NWS = 16;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
   // cached tile lists of the similarity GEMM, one per GEMM model (cosine.hip): a context is one device + one stream, so the

@@ -2,7 +2,8 @@
 
     from pvsim.encoders import VLADEncoder, FisherVectorEncoder, Pipeline, KMeansWeights, GMMWeights
     from pvsim.features import RootSIFT, SIFT, Lambda, DeepConvFeature
-    from pvsim import eval                     # retrieve_top_k_similar, top_k_map, top_k_accuracy
+    from pvsim import eval                     # retrieve_top_k_similar, top_k_map, top_k_accuracy, rerank_spatial
+    from pvsim import verify                   # LocalFeatureIndex, SpatialVerifier, match (spatial re-ranking)
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -13,4 +14,4 @@ from . import models
 from ._errors import CapacityError
 
 __version__ = "0.1.0"
-__all__ = ["encoders", "features", "eval", "models", "Context", "default_context", "pack_descriptors", "CapacityError"]
+__all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError"]

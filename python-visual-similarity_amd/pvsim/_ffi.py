@@ -114,6 +114,9 @@ SIGNATURES = {
     "pvs_sift_workspace": [_int, _int, _int, _int, C.POINTER(_sz), C.POINTER(_i64)],
     "pvs_sift_dev": [_vp, _vp, _int, _vp, _vp, _i64, _int, _int, C.c_double, C.c_double, C.c_double, _int, _int, _vp, _i64, _vp,
                      _vp, C.POINTER(_i64)],
+    "pvs_match_u8_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
+    "pvs_match_filter_dev": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_double, _int, _vp, _vp],
+    "pvs_verify_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, C.c_double, _int, _vp, _vp, _vp, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

@@ -491,6 +491,37 @@ class Context:
         check(status)
         return int(total.value)
 
+    # ------------------------------------------------------------------ spatial re-ranking (match.hip)
+    @staticmethod
+    def _pair_args(off_a, off_b, pairs):
+        off_a = np.ascontiguousarray(off_a, dtype=np.int64).reshape(-1)
+        off_b = np.ascontiguousarray(off_b, dtype=np.int64).reshape(-1)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        if off_a.size < 1 or off_b.size < 1:
+            raise ValueError("CSR offsets need at least one entry")
+        return off_a, off_b, pairs
+
+    def match_u8_dev(self, d_rows_a, off_a, d_rows_b, off_b, pairs, d_idx, d_d1, d_d2):
+        """pvs_match_u8_dev: uint8 rows on the device, host int64 CSR offsets, host int32 pairs (P, 2); int32 results per A row."""
+        off_a, off_b, pairs = self._pair_args(off_a, off_b, pairs)
+        check(_ffi.lib().pvs_match_u8_dev(self.handle, ptr(d_rows_a), ptr(off_a), off_a.size - 1, ptr(d_rows_b), ptr(off_b),
+                                          off_b.size - 1, ptr(pairs), pairs.shape[0], ptr(d_idx), ptr(d_d1), ptr(d_d2)))
+
+    def match_filter_dev(self, off_a, off_b, pairs, d_idx, d_d1, d_d2, d_idx_rev, ratio_sq, mutual, d_matches, d_match_counts):
+        """pvs_match_filter_dev: ratio test (d1 < ratio_sq d2 in float64), mutual check against the transposed matching, compaction."""
+        off_a, off_b, pairs = self._pair_args(off_a, off_b, pairs)
+        check(_ffi.lib().pvs_match_filter_dev(self.handle, ptr(off_a), off_a.size - 1, ptr(off_b), off_b.size - 1, ptr(pairs),
+                                              pairs.shape[0], ptr(d_idx), ptr(d_d1), ptr(d_d2), ptr(d_idx_rev), float(ratio_sq),
+                                              int(bool(mutual)), ptr(d_matches), ptr(d_match_counts)))
+
+    def verify_dev(self, d_frames_a, off_a, d_frames_b, off_b, pairs, d_matches, d_match_counts, tol, refine_rounds, d_inliers,
+                   d_models, d_best, d_mask):
+        """pvs_verify_dev: exhaustive similarity hypotheses + affine refinement in float64, one result per pair."""
+        off_a, off_b, pairs = self._pair_args(off_a, off_b, pairs)
+        check(_ffi.lib().pvs_verify_dev(self.handle, ptr(d_frames_a), ptr(off_a), off_a.size - 1, ptr(d_frames_b), ptr(off_b),
+                                        off_b.size - 1, ptr(pairs), pairs.shape[0], ptr(d_matches), ptr(d_match_counts), float(tol),
+                                        int(refine_rounds), ptr(d_inliers), ptr(d_models), ptr(d_best), ptr(d_mask)))
+
     # ------------------------------------------------------------------ vocabulary training (one device pass each)
     def buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)

@@ -14,7 +14,7 @@ import numpy as np
 from ._utils import cosine_similarity  # re-exported like the reference's `from ._utils import *`
 from .engine import default_context
 
-__all__ = ["retrieve_top_k_similar", "top_k_map", "top_k_accuracy"]
+__all__ = ["retrieve_top_k_similar", "top_k_map", "top_k_accuracy", "rerank_spatial"]
 
 
 
@@ -68,6 +68,27 @@ def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.nda
         query_vector = query_vector.reshape(1, -1)
     idx, val = _rank(query_vector[:1], all_vectors, k, getattr(encoder, "context", None), resident)
     return [(all_paths[i], s) for i, s in zip(idx[0], val[0])]
+
+
+def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: int | None = None,
+                   min_inliers: int = 4) -> list[tuple[str, float, int]]:
+    """Re-order the shortlist `retrieve_top_k_similar` returned by geometric verification (pvsim.verify):
+    the candidates with at least `min_inliers` inliers first, by inliers descending (ties in their incoming order), the others
+    behind them in their incoming order.  -> [(image_path, similarity, inliers)], the first k (all if None).
+    KeyError if `local_index` does not hold one of the paths."""
+    if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or min_inliers < 0:
+        raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers!r}")
+    if k is not None and (isinstance(k, bool) or int(k) != k or k < 0):
+        raise ValueError(f"k must be a non-negative integer or None, got {k!r}")
+    hits = list(hits)
+    for path, _ in hits:
+        if path not in local_index:
+            raise KeyError(path)
+    results = verifier.verify(uploaded_image, local_index, [path for path, _ in hits]) if hits else []
+    scored = [(path, sim, int(r.inliers)) for (path, sim), r in zip(hits, results)]
+    front = sorted((h for h in scored if h[2] >= min_inliers), key=lambda h: -h[2])        # sorted() is stable
+    back = [h for h in scored if h[2] < min_inliers]
+    return (front + back)[:k]
 
 
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
