@@ -15,7 +15,7 @@
 // depend on the image, the bin size and the step only: not on the batch, the tile it fell into or the run.
 #include <algorithm>
 
-#include "common.hpp"
+#include "sift_common.hpp"
 
 namespace pvs {
 
@@ -25,9 +25,6 @@ constexpr int DS_MAX_RADIUS = 32;
 constexpr int DS_MAX_TILE = 8;                 // descriptors per tile edge
 constexpr size_t DS_LDS_TARGET = 64 * 1024;    // tiles grow while they stay under this (two workgroups per CU)
 constexpr size_t DS_LDS_LIMIT = 160 * 1024;    // one workgroup per CU: the slow path of the large bin sizes
-
-enum { DS_PIX_U8_RGB = 0, DS_PIX_U8_GRAY = 1, DS_PIX_F32_RGB = 2, DS_PIX_F32_GRAY = 3 };
-enum { DS_OUT_U8 = 0, DS_OUT_F32 = 1, DS_OUT_F32_RAW = 2, DS_OUT_F32_QUANT = 3 };
 
 struct DsiftImage {
   int H, W;
@@ -78,24 +75,6 @@ __host__ __device__ inline DsiftLayout ds_layout(int s, int step, int radius, in
   return L;
 }
 
-__device__ inline float ds_gray(const DsiftArgs& a, int64_t base, int W, int y, int x) {
-  const int64_t p = (int64_t)y * W + x;
-  switch (a.pix_kind) {
-    case DS_PIX_U8_RGB: {
-      const unsigned char* q = static_cast<const unsigned char*>(a.pixels) + base + 3 * p;
-      return 0.299f * (float)q[0] + 0.587f * (float)q[1] + 0.114f * (float)q[2];
-    }
-    case DS_PIX_U8_GRAY:
-      return (float)static_cast<const unsigned char*>(a.pixels)[base + p];
-    case DS_PIX_F32_RGB: {
-      const float* q = static_cast<const float*>(a.pixels) + base + 3 * p;
-      return 0.299f * q[0] + 0.587f * q[1] + 0.114f * q[2];
-    }
-    default:
-      return static_cast<const float*>(a.pixels)[base + p];
-  }
-}
-
 __global__ __launch_bounds__(DS_THREADS) void dsift_kernel(const DsiftArgs a, const int img0) {
   extern __shared__ float lds[];
   const DsiftImage im = a.img[img0 + blockIdx.y];
@@ -128,7 +107,7 @@ __global__ __launch_bounds__(DS_THREADS) void dsift_kernel(const DsiftArgs a, co
   for (int idx = tid; idx < L.Hr * L.Wr; idx += DS_THREADS) {
     const int y = idx / L.Wr, x = idx - y * L.Wr;
     const int iy = min(max(py0 - 1 - R + y, 0), H - 1), ix = min(max(px0 - 1 - R + x, 0), W - 1);
-    G[idx] = ds_gray(a, im.pix_off, W, iy, ix);
+    G[idx] = gray_at(a.pixels, a.pix_kind, im.pix_off, W, iy, ix);
   }
   __syncthreads();
   // ---- stage 2: T[y][x] = sum_k taps[k] G[y][x + k]
@@ -210,55 +189,8 @@ __global__ __launch_bounds__(DS_THREADS) void dsift_kernel(const DsiftArgs a, co
     const int da = live ? dsc % cntx : 0, db = live ? dsc / cntx : 0;
     const int j = q >> 1, i0 = (q & 1) * 2;   // cells 2q and 2q + 1 = (j, i0) and (j, i0 + 1): sixteen consecutive floats of Bn
     const float* src = Bn + ((db * 4 + j) * ncx + da * 4 + i0) * 8;
-    float v[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) v[k] = src[k];
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) ss = fmaf(v[k], v[k], ss);
-    ss += __shfl_xor(ss, 1);
-    ss += __shfl_xor(ss, 2);
-    ss += __shfl_xor(ss, 4);
-    const float n1 = sqrtf(ss);
     const int64_t row = row0 + (int64_t)(tb + db) * nx + (ta + da);
-    if (a.out_kind != DS_OUT_F32_RAW) {
-      const bool zero = !(n1 > a.thr);
-#pragma unroll
-      for (int k = 0; k < 16; ++k) v[k] = zero ? 0.f : fminf(v[k] / n1, 0.2f);
-      float s2 = 0.f;
-#pragma unroll
-      for (int k = 0; k < 16; ++k) s2 = fmaf(v[k], v[k], s2);
-      s2 += __shfl_xor(s2, 1);
-      s2 += __shfl_xor(s2, 2);
-      s2 += __shfl_xor(s2, 4);
-      const float n2 = sqrtf(s2);
-#pragma unroll
-      for (int k = 0; k < 16; ++k) v[k] = zero ? 0.f : v[k] / n2;
-    }
-    if (!live) continue;
-    if (a.out_kind == DS_OUT_U8) {
-      unsigned int w[4];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        unsigned int word = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float r = fminf(floorf(fmaf(512.f, v[4 * g + k], 0.5f)), 255.f);
-          word |= (unsigned int)r << (8 * k);
-        }
-        w[g] = word;
-      }
-      uint4* dst = reinterpret_cast<uint4*>(static_cast<unsigned char*>(a.out) + row * 128) + q;
-      *dst = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-      if (a.out_kind == DS_OUT_F32_QUANT) {
-#pragma unroll
-        for (int k = 0; k < 16; ++k) v[k] = fminf(floorf(fmaf(512.f, v[k], 0.5f)), 255.f);
-      }
-      float4* dst = reinterpret_cast<float4*>(static_cast<float*>(a.out) + row * 128) + q * 4;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) dst[g] = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
-    }
+    sift_row_tail(src, a.thr, a.out_kind, a.out, row, q, live);
   }
 }
 
@@ -337,12 +269,10 @@ PVS_EXPORT int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind,
                              void* d_out, int64_t out_rows, int64_t* d_row_offsets) {
   if (!ctx) PVS_FAIL(PVS_ERR_INVALID, "pvs_dsift_dev: null ctx");
   PVS_TRY(ds_check_grid(step, sizes, n_sizes));
-  if (pixel_kind < DS_PIX_U8_RGB || pixel_kind > DS_PIX_F32_GRAY) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: unknown pixel kind %d", pixel_kind);
-  if (out_kind < DS_OUT_U8 || out_kind > DS_OUT_F32_QUANT) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: unknown output kind %d", out_kind);
+  ImageIntake in{"dense SIFT", "pvs_dsift_dev", h_hw, h_pix_offsets};
+  PVS_TRY(in.open(pixel_kind, out_kind, n_images));
   if (!(contrast_threshold >= 0.0)) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: contrast_threshold must be >= 0");
-  if (n_images < 0) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: negative image count");
   if (n_images == 0) return PVS_OK;
-  if (!h_hw) PVS_FAIL(PVS_ERR_INVALID, "pvs_dsift_dev: null image sizes");
   if (!d_row_offsets) PVS_FAIL(PVS_ERR_INVALID, "pvs_dsift_dev: null row offsets");
   PVS_HIP(hipSetDevice(ctx->device));
 
@@ -356,7 +286,6 @@ PVS_EXPORT int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind,
 
   // per-image table and row offsets, built in a pinned block of a small ring (the call does not wait for the stream: a block is
   // reused only after the copies that read it have finished)
-  const int chan = (pixel_kind == DS_PIX_U8_RGB || pixel_kind == DS_PIX_F32_RGB) ? 3 : 1;
   const size_t meta_bytes = (size_t)n_images * sizeof(DsiftImage);
   const size_t off_bytes = (size_t)(n_images + 1) * sizeof(int64_t);
   const size_t need = meta_bytes + off_bytes;
@@ -374,16 +303,14 @@ PVS_EXPORT int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind,
   }
   DsiftImage* h_meta = static_cast<DsiftImage*>(ctx->dsift_h[slot]);
   int64_t* h_off = reinterpret_cast<int64_t*>(static_cast<char*>(ctx->dsift_h[slot]) + meta_bytes);
-  int64_t rows = 0, pix = 0;
+  int64_t rows = 0;
   std::vector<int> max_tiles(n_sizes, 0);
   for (int64_t i = 0; i < n_images; ++i) {
-    const int H = h_hw[2 * i], W = h_hw[2 * i + 1];
-    if (H < 1 || W < 1) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: image %lld has size %d x %d", (long long)i, H, W);
-    const int64_t po = h_pix_offsets ? h_pix_offsets[i] : pix;
-    if (po < 0) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: negative pixel offset");
+    int H, W;
+    int64_t po;
+    PVS_TRY(in.next(i, &H, &W, &po));
     h_meta[i] = DsiftImage{H, W, po, rows};
     h_off[i] = rows;
-    pix += (int64_t)H * W * chan;
     for (int k = 0; k < n_sizes; ++k) {
       const int nx = ds_grid(W, sizes[k], step), ny = ds_grid(H, sizes[k], step);
       rows += (int64_t)nx * ny;
@@ -419,11 +346,7 @@ PVS_EXPORT int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind,
     a.ty = ty[k];
     a.thr = (float)contrast_threshold;
     for (int j = 0; j < n_sizes; ++j) a.sizes[j] = sizes[j];
-    // Gaussian taps exp(-d^2 / 2 sigma^2), sigma = s / 6, normalised to sum 1 in float64
-    const double sigma = (double)a.s / 6.0;
-    double tap[2 * DS_MAX_RADIUS + 1], sum = 0.0;
-    for (int d = -a.radius; d <= a.radius; ++d) sum += tap[d + a.radius] = std::exp(-(double)d * d / (2.0 * sigma * sigma));
-    for (int d = 0; d <= 2 * a.radius; ++d) a.taps[d] = (float)(tap[d] / sum);
+    gaussian_taps((double)a.s / 6.0, a.radius, a.taps);   // sigma = s / 6
     PVS_TRY(ensure_lds(ctx, reinterpret_cast<const void*>(dsift_kernel), lds_bytes[k]));
     for (int64_t i0 = 0; i0 < n_images; i0 += 65535) {
       const dim3 grid((unsigned)max_tiles[k], (unsigned)std::min<int64_t>(65535, n_images - i0));

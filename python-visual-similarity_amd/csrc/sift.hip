@@ -16,7 +16,7 @@
 // parameters only, not on the batch, the chunking or the run.
 #include <algorithm>
 
-#include "common.hpp"
+#include "sift_common.hpp"
 
 namespace pvs {
 
@@ -30,9 +30,6 @@ constexpr int SF_MAX_PEAKS = 18;                 // local maxima of 36 circular 
 constexpr int SF_CHUNK_IMAGES = 1024;
 constexpr size_t SF_PYRAMID_BUDGET = 256u << 20; // bytes of Gaussian pyramids per chunk (a single larger image runs alone)
 constexpr int SF_HSTRIDE = 65;                   // lane-private histogram columns: bin * 65 + lane (conflict-free both ways)
-
-enum { SF_PIX_U8_RGB = 0, SF_PIX_U8_GRAY = 1, SF_PIX_F32_RGB = 2, SF_PIX_F32_GRAY = 3 };
-enum { SF_OUT_U8 = 0, SF_OUT_F32 = 1, SF_OUT_F32_RAW = 2, SF_OUT_F32_QUANT = 3 };
 
 struct SiftImage {
   int H, W;          // input
@@ -68,24 +65,6 @@ struct SiftArgs {
   float pre, thr_c, edge_r, edge_r1sq, sigma;
 };
 
-__device__ inline float sf_gray(const SiftArgs& a, int64_t base, int W, int y, int x) {
-  const int64_t p = (int64_t)y * W + x;
-  switch (a.pix_kind) {
-    case SF_PIX_U8_RGB: {
-      const unsigned char* q = static_cast<const unsigned char*>(a.pixels) + base + 3 * p;
-      return 0.299f * (float)q[0] + 0.587f * (float)q[1] + 0.114f * (float)q[2];
-    }
-    case SF_PIX_U8_GRAY:
-      return (float)static_cast<const unsigned char*>(a.pixels)[base + p];
-    case SF_PIX_F32_RGB: {
-      const float* q = static_cast<const float*>(a.pixels) + base + 3 * p;
-      return 0.299f * q[0] + 0.587f * q[1] + 0.114f * q[2];
-    }
-    default:
-      return static_cast<const float*>(a.pixels)[base + p];
-  }
-}
-
 __device__ inline float* sf_layer(const SiftArgs& a, const SiftImage& im, int o, int layer) {
   const int h = im.H0 >> o, w = im.W0 >> o;
   return a.pyr + im.ws_off + sf_oct_off(im.H0, im.W0, o, a.nl) + (int64_t)layer * h * w;
@@ -98,6 +77,7 @@ __global__ __launch_bounds__(256) void sift_base_kernel(const SiftArgs a) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (int64_t)im.H0 * im.W0) return;
   const int y = (int)(idx / im.W0), x = (int)(idx - (int64_t)y * im.W0);
+  const auto gray = [&](int py, int px) { return gray_at(a.pixels, a.pix_kind, im.pix_off, im.W, py, px); };
   float v;
   if (a.upsample) {
     const float sy = fminf(fmaxf((float)y * 0.5f - 0.25f, 0.f), (float)(im.H - 1));
@@ -105,11 +85,11 @@ __global__ __launch_bounds__(256) void sift_base_kernel(const SiftArgs a) {
     const int y0 = (int)floorf(sy), x0 = (int)floorf(sx);
     const int y1 = min(y0 + 1, im.H - 1), x1 = min(x0 + 1, im.W - 1);
     const float fy = sy - (float)y0, fx = sx - (float)x0;
-    const float top = (1.0f - fx) * sf_gray(a, im.pix_off, im.W, y0, x0) + fx * sf_gray(a, im.pix_off, im.W, y0, x1);
-    const float bot = (1.0f - fx) * sf_gray(a, im.pix_off, im.W, y1, x0) + fx * sf_gray(a, im.pix_off, im.W, y1, x1);
+    const float top = (1.0f - fx) * gray(y0, x0) + fx * gray(y0, x1);
+    const float bot = (1.0f - fx) * gray(y1, x0) + fx * gray(y1, x1);
     v = (1.0f - fy) * top + fy * bot;
   } else {
-    v = sf_gray(a, im.pix_off, im.W, y, x);
+    v = gray(y, x);
   }
   sf_layer(a, im, 0, 1)[idx] = v;
 }
@@ -490,58 +470,10 @@ __global__ __launch_bounds__(64) void sift_desc_kernel(const SiftArgs a, const S
       acc[e] = s;
     }
     __syncthreads();
-    // the tail of dense SIFT (section 9 step 6): eight lanes per row, sixteen consecutive elements per lane; the wave holds eight
-    // identical copies and lanes 0..7 store
+    // the row tail: eight lanes per row, sixteen consecutive elements per lane; the wave holds eight identical copies and lanes
+    // 0..7 store.  A row is zeroed only when its norm is 0
     const int q = lane & 7;
-    float v[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) v[j] = acc[q * 16 + j];
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) ss = fmaf(v[j], v[j], ss);
-    ss += __shfl_xor(ss, 1);
-    ss += __shfl_xor(ss, 2);
-    ss += __shfl_xor(ss, 4);
-    const float n1 = sqrtf(ss);
-    if (d.out_kind != SF_OUT_F32_RAW) {
-      const bool zero = !(n1 > 0.f);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = zero ? 0.f : fminf(v[j] / n1, 0.2f);
-      float s2 = 0.f;
-#pragma unroll
-      for (int j = 0; j < 16; ++j) s2 = fmaf(v[j], v[j], s2);
-      s2 += __shfl_xor(s2, 1);
-      s2 += __shfl_xor(s2, 2);
-      s2 += __shfl_xor(s2, 4);
-      const float n2 = sqrtf(s2);
-#pragma unroll
-      for (int j = 0; j < 16; ++j) v[j] = zero ? 0.f : v[j] / n2;
-    }
-    if (lane < 8) {
-      if (d.out_kind == SF_OUT_U8) {
-        unsigned int wd[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          unsigned int word = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float r = fminf(floorf(fmaf(512.f, v[4 * g + j], 0.5f)), 255.f);
-            word |= (unsigned int)r << (8 * j);
-          }
-          wd[g] = word;
-        }
-        uint4* dst = reinterpret_cast<uint4*>(static_cast<unsigned char*>(d.out) + row * 128) + q;
-        *dst = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-      } else {
-        if (d.out_kind == SF_OUT_F32_QUANT) {
-#pragma unroll
-          for (int j = 0; j < 16; ++j) v[j] = fminf(floorf(fmaf(512.f, v[j], 0.5f)), 255.f);
-        }
-        float4* dst = reinterpret_cast<float4*>(static_cast<float*>(d.out) + row * 128) + q * 4;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) dst[g] = make_float4(v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]);
-      }
-    }
+    sift_row_tail(acc + q * 16, 0.f, d.out_kind, d.out, row, q, lane < 8);
     if (lane == 0 && d.frames) {
       const float scale = (float)(1 << o), u = a.upsample ? 2.0f : 1.0f, off = a.upsample ? 0.25f : 0.0f;
       float* f = d.frames + row * 6;
@@ -559,10 +491,7 @@ __global__ __launch_bounds__(64) void sift_desc_kernel(const SiftArgs a, const S
 static void sf_taps(double sigma, int* R, float* taps) {
   const int r = (int)std::ceil(4.0 * sigma - 1e-12);
   *R = r;
-  if (r > SF_MAX_RADIUS) return;
-  double tap[2 * SF_MAX_RADIUS + 1], sum = 0.0;
-  for (int d = -r; d <= r; ++d) sum += tap[d + r] = std::exp(-(double)d * d / (2.0 * sigma * sigma));
-  for (int d = 0; d <= 2 * r; ++d) taps[d] = (float)(tap[d] / sum);
+  if (r <= SF_MAX_RADIUS) gaussian_taps(sigma, r, taps);
 }
 
 static int sf_check(int nfeatures, int L, double contrast, double edge, double sigma, int upsample, double* base, double* inc) {
@@ -613,27 +542,22 @@ PVS_EXPORT int pvs_sift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, 
   if (!ctx) PVS_FAIL(PVS_ERR_INVALID, "pvs_sift_dev: null ctx");
   double base_sigma = 0.0, inc[SF_MAX_LAYERS + 3] = {0};
   PVS_TRY(sf_check(nfeatures, n_octave_layers, contrast_threshold, edge_threshold, sigma, upsample, &base_sigma, inc));
-  if (pixel_kind < SF_PIX_U8_RGB || pixel_kind > SF_PIX_F32_GRAY) PVS_FAIL(PVS_ERR_INVALID, "SIFT: unknown pixel kind %d", pixel_kind);
-  if (out_kind < SF_OUT_U8 || out_kind > SF_OUT_F32_QUANT) PVS_FAIL(PVS_ERR_INVALID, "SIFT: unknown output kind %d", out_kind);
-  if (n_images < 0) PVS_FAIL(PVS_ERR_INVALID, "SIFT: negative image count");
+  ImageIntake in{"SIFT", "pvs_sift_dev", h_hw, h_pix_offsets};
+  PVS_TRY(in.open(pixel_kind, out_kind, n_images));
   if (capacity_rows < 0) PVS_FAIL(PVS_ERR_INVALID, "SIFT: negative capacity");
   if (n_images == 0) return PVS_OK;
-  if (!h_hw) PVS_FAIL(PVS_ERR_INVALID, "pvs_sift_dev: null image sizes");
   if (!d_row_offsets || !h_total_rows) PVS_FAIL(PVS_ERR_INVALID, "pvs_sift_dev: null row offsets or total");
   if (!d_pixels) PVS_FAIL(PVS_ERR_INVALID, "pvs_sift_dev: null pixels");
   if (capacity_rows > 0 && !d_rows) PVS_FAIL(PVS_ERR_INVALID, "pvs_sift_dev: null rows");
   PVS_HIP(hipSetDevice(ctx->device));
 
   const int L = n_octave_layers, nl = L + 3;
-  const int chan = (pixel_kind == SF_PIX_U8_RGB || pixel_kind == SF_PIX_F32_RGB) ? 3 : 1;
   std::vector<SiftImage> table((size_t)n_images);
-  int64_t pix = 0;
   for (int64_t i = 0; i < n_images; ++i) {
-    const int H = h_hw[2 * i], W = h_hw[2 * i + 1];
-    if (H < 1 || W < 1) PVS_FAIL(PVS_ERR_INVALID, "SIFT: image %lld has size %d x %d", (long long)i, H, W);
+    int H, W;
+    int64_t po;
+    PVS_TRY(in.next(i, &H, &W, &po));
     if (H > 16384 || W > 16384) PVS_FAIL(PVS_ERR_UNSUPPORTED, "SIFT: image %lld is larger than 16384 pixels per side", (long long)i);
-    const int64_t po = h_pix_offsets ? h_pix_offsets[i] : pix;
-    if (po < 0) PVS_FAIL(PVS_ERR_INVALID, "SIFT: negative pixel offset");
     SiftImage& im = table[(size_t)i];
     im.H = H, im.W = W;
     im.H0 = upsample ? 2 * H : H, im.W0 = upsample ? 2 * W : W;
@@ -641,7 +565,6 @@ PVS_EXPORT int pvs_sift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, 
     im.pad = 0;
     im.pix_off = po;
     im.ws_off = 0;
-    pix += (int64_t)H * W * chan;
   }
 
   SiftArgs a;

@@ -137,6 +137,22 @@ def _is_torch_tensor(x) -> bool:
     return type(x).__module__.startswith("torch") and type(x).__name__ == "Tensor"
 
 
+def _image_chunks(images, max_images, max_pixel_bytes):
+    """Consecutive runs of the input, pulled lazily (a generator of decoded files is never held as a whole): at most
+    max_images images and max_pixel_bytes of pixels (as float32) per run, and a run never mixes gray (H, W) with colour
+    (H, W, 3) images, which one extraction launch cannot.  Rows do not depend on how the input is cut."""
+    chunk, nbytes = [], 0
+    for im in images:
+        size = int(np.prod(np.shape(im))) * 4
+        if chunk and (len(chunk) >= max_images or nbytes + size > max_pixel_bytes or np.ndim(im) != np.ndim(chunk[0])):
+            yield chunk
+            chunk, nbytes = [], 0
+        chunk.append(im)
+        nbytes += size
+    if chunk:
+        yield chunk
+
+
 # ----------------------------------------------------------------------------------------- base class
 class ImageEncoderBase(SimilarityMetric):
     """feature extractor -> (PCA) -> clustering model -> aggregated, normalised vector, on the MI355X.
@@ -391,20 +407,7 @@ class ImageEncoderBase(SimilarityMetric):
 
     @classmethod
     def _image_chunks(cls, images):
-        """Consecutive runs of the input, pulled lazily (a generator of decoded files is never held as a whole): at most
-        _CHUNK_IMAGES images and _CHUNK_PIXEL_BYTES of pixels (as float32) per run, and a run never mixes gray (H, W) with
-        colour (H, W, 3) images, which one extraction launch cannot.  Rows do not depend on how the input is cut."""
-        chunk, nbytes = [], 0
-        for im in images:
-            size = int(np.prod(np.shape(im))) * 4
-            if chunk and (len(chunk) >= cls._CHUNK_IMAGES or nbytes + size > cls._CHUNK_PIXEL_BYTES
-                          or np.ndim(im) != np.ndim(chunk[0])):
-                yield chunk
-                chunk, nbytes = [], 0
-            chunk.append(im)
-            nbytes += size
-        if chunk:
-            yield chunk
+        return _image_chunks(images, cls._CHUNK_IMAGES, cls._CHUNK_PIXEL_BYTES)
 
     def encode(self, images: Iterable[np.ndarray] | np.ndarray) -> np.ndarray:
         """(N, L) encodings of one image (H, W, 3) or an iterable of images."""

@@ -464,11 +464,15 @@ class Context:
         check(_ffi.lib().pvs_transpose_f64_dev(self.handle, ptr(d_src), rows, cols, ptr(d_dst)))
 
     # ------------------------------------------------------------------ dense SIFT (dsift.hip)
+    @staticmethod
+    def _image_args(hw, pix_offsets):
+        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
+        return hw, None if pix_offsets is None else np.ascontiguousarray(pix_offsets, dtype=np.int64)
+
     def dsift_dev(self, d_pixels, pixel_kind, hw, pix_offsets, step, sizes, contrast_threshold, out_kind, d_out, out_rows,
                   d_row_offsets):
         """pvs_dsift_dev: hw host int32 (B, 2), pix_offsets host int64 (B,) or None, sizes host int32; everything else device."""
-        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
-        po = None if pix_offsets is None else np.ascontiguousarray(pix_offsets, dtype=np.int64)
+        hw, po = self._image_args(hw, pix_offsets)
         sizes = np.ascontiguousarray(sizes, dtype=np.int32)
         check(_ffi.lib().pvs_dsift_dev(self.handle, ptr(d_pixels), int(pixel_kind), ptr(hw), ptr(po), hw.shape[0], int(step),
                                        ptr(sizes), sizes.shape[0], float(contrast_threshold), int(out_kind), ptr(d_out),
@@ -479,8 +483,7 @@ class Context:
                  upsample, out_kind, d_rows, capacity_rows, d_frames, d_row_offsets) -> int:
         """pvs_sift_dev: hw host int32 (B, 2), pix_offsets host int64 (B,) or None; rows, frames (or None) and row offsets on the
         device.  Waits for the stream.  -> total rows; raises CapacityError (args[1] = the total) when they exceed capacity_rows."""
-        hw = np.ascontiguousarray(hw, dtype=np.int32).reshape(-1, 2)
-        po = None if pix_offsets is None else np.ascontiguousarray(pix_offsets, dtype=np.int64)
+        hw, po = self._image_args(hw, pix_offsets)
         total = C.c_int64(0)
         status = _ffi.lib().pvs_sift_dev(self.handle, ptr(d_pixels), int(pixel_kind), ptr(hw), ptr(po), hw.shape[0], int(nfeatures),
                                          int(n_octave_layers), float(contrast_threshold), float(edge_threshold), float(sigma),

@@ -5,13 +5,16 @@ float descriptors plus `.output_dim`.
                     is imported lazily, so the classes exist without cv2 and fail only when called.  RootSIFT
                     additionally exposes `raw(image)` so that the encoders can hand the *raw* uint8 SIFT rows
                     to the GPU and fuse the RootSIFT tail (d /= sum+1e-7; sqrt, _features.py:112-114) there.
+  _DeviceSIFT       private base of the two GPU extractors below: the context, the intake of a batch (checks, pixel kind, upload),
+                    buffer ownership and the single-image calls (`raw`, `descriptors`, `__call__`).  A subclass adds its parameters
+                    and `device_descriptors(images, ctx)`, which leaves a whole batch's rows on the device for the encoders.
+                    They mirror SIFT / RootSIFT: integer valued float32 rows 0..255; `raw(image)` + `fused_rootsift`.
   DenseSIFT /       SIFT descriptors on a regular grid at fixed bin sizes, computed from the pixels by the HIP kernel of
-  DenseRootSIFT     csrc/dsift.hip: no detector, no OpenCV.  They mirror SIFT / RootSIFT (integer valued
-                    float32 rows 0..255; `raw(image)` + `fused_rootsift`), and `device_descriptors(images, ctx)` leaves a
-                    whole batch's rows on the device for the encoders.
+  DenseRootSIFT     csrc/dsift.hip: no detector, no OpenCV.  The row count is known before the call.
   KeypointSIFT /    keypoint SIFT computed from the pixels by csrc/sift.hip: Lowe's scale-space detector,
   KeypointRootSIFT  orientation assignment and rotated descriptors with OpenCV's parameter names and defaults, without OpenCV (and
-                    not a bit-for-bit clone of it).  Same interface and device hand-off as the dense pair.
+                    not a bit-for-bit clone of it).  The row count depends on the images: a capacity guess and one retry.
+  _hellinger        the RootSIFT tail of all three *RootSIFT classes (the kernels' row tail is csrc/sift_common.hpp).
   Lambda            any user function (the descriptor-level door used by tests and synthetic benchmarks).
   DeepConvFeature   conv feature maps of a torch model on PyTorch-ROCm (torch is plumbing here).  torchvision
                     is absent offline, so the default network is an own VGG16 `features` stack with RANDOM
@@ -20,6 +23,7 @@ float descriptors plus `.output_dim`.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from functools import wraps
 from typing import Callable
 
@@ -49,6 +53,14 @@ def _check_output_shape(func) -> Callable:
         return feats
 
     return wrapper
+
+
+def _hellinger(descriptors):
+    """RootSIFT's tail on float rows (n, 128), in place where it can: d /= sum + 1e-7; sqrt.  None and empty pass through."""
+    if descriptors is not None and descriptors.shape[0]:
+        descriptors /= descriptors.sum(axis=1, keepdims=True) + 1e-7
+        descriptors = np.sqrt(descriptors)
+    return descriptors
 
 
 def _cv2():
@@ -103,35 +115,18 @@ class RootSIFT(FeatureExtractorBase):
     def __call__(self, image: np.ndarray, /) -> np.ndarray:
         super().__call__(image)
         _, descriptors = _cv2().SIFT.create().detectAndCompute(image, None)
-        if descriptors is not None:
-            descriptors /= (descriptors.sum(axis=1, keepdims=True) + 1e-7)
-            descriptors = np.sqrt(descriptors)
-        return descriptors
+        return _hellinger(descriptors)
 
     def __repr__(self):
         return f"RootSIFT(output_dim={self.output_dim})"
 
 
-class DenseSIFT(FeatureExtractorBase):
-    """Dense SIFT (n, 128): descriptors at every `step` pixels for each bin size in `sizes` (pixels per spatial bin), integer
-    valued float32 rows on OpenCV's 0..255 scale like `SIFT`.  The definition is DESIGN.md section 9; the work is done by
-    pvs_dsift_dev on the GPU.  Rows are ordered by (size, y, x); `frames(h, w)` gives their (x, y, size)."""
+class _DeviceSIFT(FeatureExtractorBase):
+    """What DenseSIFT and KeypointSIFT share: the context, the intake of a batch of images up to the pixel upload, and the
+    single-image calls on top of the subclass's `device_descriptors`."""
 
-    def __init__(self, step: int = 16, sizes=(4, 8), contrast_threshold: float = 0.0, ctx=None):
+    def __init__(self, ctx):
         super().__init__()
-        if isinstance(step, bool) or int(step) != step or step < 1:
-            raise ValueError(f"step must be a positive integer, got {step!r}")
-        sizes = tuple(sizes)
-        if not sizes:
-            raise ValueError("sizes must hold at least one bin size")
-        for s in sizes:
-            if isinstance(s, bool) or int(s) != s or s < 1:
-                raise ValueError(f"bin sizes must be positive integers, got {s!r}")
-        if not contrast_threshold >= 0:
-            raise ValueError(f"contrast_threshold must be >= 0, got {contrast_threshold!r}")
-        self.step = int(step)
-        self.sizes = tuple(int(s) for s in sizes)
-        self.contrast_threshold = float(contrast_threshold)
         self._ctx = ctx
         self._output_dim = 128
 
@@ -146,16 +141,6 @@ class DenseSIFT(FeatureExtractorBase):
             self._ctx = default_context()
         return self._ctx
 
-    def count(self, h: int, w: int) -> int:
-        """Descriptor rows of an h x w image."""
-        from ..engine import dsift_count
-        return dsift_count(h, w, self.step, self.sizes)
-
-    def frames(self, h: int, w: int) -> np.ndarray:
-        """(n, 3) float32: x centre, y centre and bin size of every row of an h x w image."""
-        from ..engine import dsift_frames
-        return dsift_frames(h, w, self.step, self.sizes)
-
     @staticmethod
     def _pixel_kind(images):
         """uint8 images are uploaded as they are, everything else as float32; one kind per batch."""
@@ -168,13 +153,9 @@ class DenseSIFT(FeatureExtractorBase):
             return (PIX_U8_GRAY if u8 else PIX_F32_GRAY), (np.uint8 if u8 else np.float32)
         return (PIX_U8_RGB if u8 else PIX_F32_RGB), (np.uint8 if u8 else np.float32)
 
-    def device_descriptors(self, images, ctx=None, out_kind=None, _validated=False):
-        """Descriptors of a batch of images (mixed sizes allowed), left on the device:
-        -> (rows DeviceBuffer, offsets DeviceBuffer (int64, B+1), n_images, total rows, descriptor kind, host offsets).
-        The rows are uint8 (kind DESC_U8_ROOTSIFT for DenseRootSIFT: the encoders fuse the RootSIFT tail into their load) or,
-        for DenseSIFT, the same integers as float32 (kind DESC_F32); `out_kind` (a pvs_dsift_out value) overrides the row format.
-        All images of one call must be gray (H, W) or all colour (H, W, 3): the kernel reads one pixel format per launch
-        (the encoders cut their input into such runs).  The caller owns both buffers (`.free()`)."""
+    def _intake(self, images, ctx, out_kind, _validated):
+        """Check a batch and upload its pixels -> (ctx, pixel DeviceBuffer, pixel kind, hw (B, 2) int32, pixels in all, descriptor
+        kind, out_kind).  The caller frees the pixel buffer once its readers are done."""
         from .._ffi import DSIFT_F32_QUANT, DSIFT_U8
         from .._utils import is_numpy_image
         from ..engine import DESC_F32, DESC_U8_ROOTSIFT
@@ -193,35 +174,33 @@ class DenseSIFT(FeatureExtractorBase):
         if out_kind is None:            # what the encoders read: uint8 rows, or the same integers as float32 for plain SIFT
             out_kind = DSIFT_U8 if fused else DSIFT_F32_QUANT
         hw = np.array([im.shape[:2] for im in images], dtype=np.int32).reshape(-1, 2)
-        counts = np.array([self.count(h, w) for h, w in hw], dtype=np.int64)
-        h_off = np.zeros(len(images) + 1, dtype=np.int64)
-        np.cumsum(counts, out=h_off[1:])
-        total = int(h_off[-1])
+        n_pix = int((hw[:, 0].astype(np.int64) * hw[:, 1]).sum())
         flat = np.concatenate([np.ascontiguousarray(im, dtype=dt).reshape(-1) for im in images])
-        pix = ctx.buffer(flat.nbytes).upload(flat)
-        rows = offs = None
+        return ctx, ctx.buffer(flat.nbytes).upload(flat), pix_kind, hw, n_pix, kind, out_kind
+
+    @staticmethod
+    @contextmanager
+    def _owning(pix, outputs):
+        """The pixel buffer is freed on the way out, whatever happened; the buffers in the list `outputs` only if the block
+        failed (otherwise they are the caller's)."""
         try:
-            rows = ctx.buffer(max(total, 1) * 128 * (1 if out_kind == DSIFT_U8 else 4))
-            offs = ctx.buffer(h_off.nbytes)
-            ctx.dsift_dev(pix.ptr, pix_kind, hw, None, self.step, self.sizes, self.contrast_threshold, out_kind, rows.ptr,
-                          total, offs.ptr)
-            ctx.sync()                      # the pixel block goes back to the context's cache: its readers must be done
+            yield
         except Exception:
-            for b in (rows, offs):
-                if b is not None:
-                    b.free()
+            for b in outputs:
+                b.free()
             raise
         finally:
             pix.free()
-        return rows, offs, len(images), total, kind, h_off
 
-    def _rows(self, image, out_kind, dtype, validated=False):
-        rows, offs, _, total, _, _ = self.device_descriptors([image], None, out_kind, _validated=validated)
+    def _rows(self, image, out_kind, dtype, validated=False, **more):
+        got = self.device_descriptors([image], None, out_kind, _validated=validated, **more)
+        rows, offs, total, frames = got[0], got[1], got[3], got[6:]
         try:
-            return rows.download((total, 128), dtype)
+            out = rows.download((total, 128), dtype)
+            return (frames[0].download((total, 6), np.float32), out) if frames else out
         finally:
-            rows.free()
-            offs.free()
+            for b in (rows, offs) + frames:
+                b.free()
 
     def raw(self, image: np.ndarray) -> np.ndarray:
         """The uint8 rows (n, 128) as the kernel writes them."""
@@ -239,6 +218,61 @@ class DenseSIFT(FeatureExtractorBase):
         super().__call__(image)
         return self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
 
+
+class DenseSIFT(_DeviceSIFT):
+    """Dense SIFT (n, 128): descriptors at every `step` pixels for each bin size in `sizes` (pixels per spatial bin), integer
+    valued float32 rows on OpenCV's 0..255 scale like `SIFT`.  The definition is DESIGN.md section 9; the work is done by
+    pvs_dsift_dev on the GPU.  Rows are ordered by (size, y, x); `frames(h, w)` gives their (x, y, size)."""
+
+    def __init__(self, step: int = 16, sizes=(4, 8), contrast_threshold: float = 0.0, ctx=None):
+        super().__init__(ctx)
+        if isinstance(step, bool) or int(step) != step or step < 1:
+            raise ValueError(f"step must be a positive integer, got {step!r}")
+        sizes = tuple(sizes)
+        if not sizes:
+            raise ValueError("sizes must hold at least one bin size")
+        for s in sizes:
+            if isinstance(s, bool) or int(s) != s or s < 1:
+                raise ValueError(f"bin sizes must be positive integers, got {s!r}")
+        if not contrast_threshold >= 0:
+            raise ValueError(f"contrast_threshold must be >= 0, got {contrast_threshold!r}")
+        self.step = int(step)
+        self.sizes = tuple(int(s) for s in sizes)
+        self.contrast_threshold = float(contrast_threshold)
+
+    def count(self, h: int, w: int) -> int:
+        """Descriptor rows of an h x w image."""
+        from ..engine import dsift_count
+        return dsift_count(h, w, self.step, self.sizes)
+
+    def frames(self, h: int, w: int) -> np.ndarray:
+        """(n, 3) float32: x centre, y centre and bin size of every row of an h x w image."""
+        from ..engine import dsift_frames
+        return dsift_frames(h, w, self.step, self.sizes)
+
+    def device_descriptors(self, images, ctx=None, out_kind=None, _validated=False):
+        """Descriptors of a batch of images (mixed sizes allowed), left on the device:
+        -> (rows DeviceBuffer, offsets DeviceBuffer (int64, B+1), n_images, total rows, descriptor kind, host offsets).
+        The rows are uint8 (kind DESC_U8_ROOTSIFT for DenseRootSIFT: the encoders fuse the RootSIFT tail into their load) or,
+        for DenseSIFT, the same integers as float32 (kind DESC_F32); `out_kind` (a pvs_dsift_out value) overrides the row format.
+        All images of one call must be gray (H, W) or all colour (H, W, 3): the kernel reads one pixel format per launch
+        (the encoders cut their input into such runs).  The caller owns both buffers (`.free()`)."""
+        from .._ffi import DSIFT_U8
+        ctx, pix, pix_kind, hw, _, kind, out_kind = self._intake(images, ctx, out_kind, _validated)
+        held = []
+        with self._owning(pix, held):
+            h_off = np.zeros(len(hw) + 1, dtype=np.int64)
+            np.cumsum([self.count(h, w) for h, w in hw], out=h_off[1:])
+            total = int(h_off[-1])
+            rows = ctx.buffer(max(total, 1) * 128 * (1 if out_kind == DSIFT_U8 else 4))
+            held.append(rows)
+            offs = ctx.buffer(h_off.nbytes)
+            held.append(offs)
+            ctx.dsift_dev(pix.ptr, pix_kind, hw, None, self.step, self.sizes, self.contrast_threshold, out_kind, rows.ptr,
+                          total, offs.ptr)
+            ctx.sync()                      # the pixel block goes back to the context's cache: its readers must be done
+        return rows, offs, len(hw), total, kind, h_off
+
     def __repr__(self):
         return (f"{type(self).__name__}(step={self.step}, sizes={self.sizes}, contrast_threshold={self.contrast_threshold}, "
                 f"output_dim={self.output_dim})")
@@ -249,18 +283,11 @@ class DenseRootSIFT(DenseSIFT):
     its uint8 rows on the device and fuse the RootSIFT tail into their load (kind DESC_U8_ROOTSIFT)."""
     fused_rootsift = True
 
-    @_check_output_shape
     def __call__(self, image: np.ndarray, /) -> np.ndarray:
-        from .._ffi import DSIFT_U8
-        FeatureExtractorBase.__call__(self, image)
-        descriptors = self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
-        if descriptors.shape[0]:
-            descriptors /= (descriptors.sum(axis=1, keepdims=True) + 1e-7)
-            descriptors = np.sqrt(descriptors)
-        return descriptors
+        return _hellinger(super().__call__(image))
 
 
-class KeypointSIFT(FeatureExtractorBase):
+class KeypointSIFT(_DeviceSIFT):
     """Keypoint SIFT (n, 128) on the GPU: Lowe's scale-space detector (Gaussian pyramid, DoG extrema, sub-pixel refinement,
     contrast and edge tests), orientation assignment and rotated 4 x 4 x 8 descriptors, integer valued float32 rows on OpenCV's
     0..255 scale like `SIFT`.  OpenCV's parameter names and defaults, but NOT a bit-for-bit clone of cv2.SIFT: the definition is
@@ -269,7 +296,7 @@ class KeypointSIFT(FeatureExtractorBase):
 
     def __init__(self, nfeatures: int = 0, n_octave_layers: int = 3, contrast_threshold: float = 0.04, edge_threshold: float = 10,
                  sigma: float = 1.6, upsample: bool = True, ctx=None):
-        super().__init__()
+        super().__init__(ctx)
         if isinstance(nfeatures, bool) or int(nfeatures) != nfeatures or nfeatures < 0:
             raise ValueError(f"nfeatures must be a non-negative integer, got {nfeatures!r}")
         if isinstance(n_octave_layers, bool) or int(n_octave_layers) != n_octave_layers or n_octave_layers < 1:
@@ -288,22 +315,7 @@ class KeypointSIFT(FeatureExtractorBase):
         self.edge_threshold = float(edge_threshold)
         self.sigma = float(sigma)
         self.upsample = bool(upsample)
-        self._ctx = ctx
-        self._output_dim = 128
         self._rows_per_pixel = 1.0 / 64.0        # capacity guess of the first call; grows with what the images gave
-
-    @property
-    def output_dim(self) -> int:
-        return self._output_dim
-
-    @property
-    def context(self):
-        if self._ctx is None:
-            from ..engine import default_context
-            self._ctx = default_context()
-        return self._ctx
-
-    _pixel_kind = staticmethod(DenseSIFT._pixel_kind)
 
     def device_descriptors(self, images, ctx=None, out_kind=None, _validated=False, frames=False):
         """Descriptors of a batch of images (mixed sizes allowed), left on the device:
@@ -312,37 +324,22 @@ class KeypointSIFT(FeatureExtractorBase):
         The row count depends on the images: the first call guesses a capacity and, when the rows do not fit, one retry with
         the exact total follows (pvs_sift_dev reports it).  The caller owns the buffers (`.free()`)."""
         from .._errors import CapacityError
-        from .._ffi import DSIFT_F32_QUANT, DSIFT_U8
-        from .._utils import is_numpy_image
-        from ..engine import DESC_F32, DESC_U8_ROOTSIFT
-        images = [images] if isinstance(images, np.ndarray) and images.ndim in (2, 3) and not (
-            images.ndim == 3 and images.shape[2] != 3) else list(images)
-        if not images:
-            raise ValueError("need at least one image")
-        for pos, im in enumerate(() if _validated else images):
-            if type(im).__module__.startswith("torch"):
-                raise TypeError("Torch images are not supported yet. Please convert to NumPy.")
-            is_numpy_image(im, pos)
-        ctx = ctx if ctx is not None else self.context
-        pix_kind, dt = self._pixel_kind(images)
-        fused = getattr(self, "fused_rootsift", False)
-        kind = DESC_U8_ROOTSIFT if fused else DESC_F32
-        if out_kind is None:
-            out_kind = DSIFT_U8 if fused else DSIFT_F32_QUANT
+        from .._ffi import DSIFT_U8
+        ctx, pix, pix_kind, hw, n_pix, kind, out_kind = self._intake(images, ctx, out_kind, _validated)
         width = 128 * (1 if out_kind == DSIFT_U8 else 4)
-        hw = np.array([im.shape[:2] for im in images], dtype=np.int32).reshape(-1, 2)
-        n_pix = int((hw[:, 0].astype(np.int64) * hw[:, 1]).sum())
         capacity = max(256, int(n_pix * self._rows_per_pixel))
         if self.nfeatures:
-            capacity = min(capacity, self.nfeatures * len(images))
-        flat = np.concatenate([np.ascontiguousarray(im, dtype=dt).reshape(-1) for im in images])
-        pix = ctx.buffer(flat.nbytes).upload(flat)
-        rows = offs = frm = None
-        try:
-            offs = ctx.buffer((len(images) + 1) * 8)
+            capacity = min(capacity, self.nfeatures * len(hw))
+        held = []
+        with self._owning(pix, held):       # pvs_sift_dev waits for the stream: nothing reads the pixels after it
+            offs = ctx.buffer((len(hw) + 1) * 8)
+            held.append(offs)
             for attempt in (0, 1):
                 rows = ctx.buffer(max(capacity, 1) * width)
+                held.append(rows)
                 frm = ctx.buffer(max(capacity, 1) * 24) if frames else None
+                if frames:
+                    held.append(frm)
                 try:
                     total = ctx.sift_dev(pix.ptr, pix_kind, hw, None, self.nfeatures, self.n_octave_layers, self.contrast_threshold,
                                          self.edge_threshold, self.sigma, self.upsample, out_kind, rows.ptr, capacity,
@@ -351,44 +348,13 @@ class KeypointSIFT(FeatureExtractorBase):
                 except CapacityError as e:
                     if attempt:
                         raise
-                    rows.free()
-                    if frm is not None:
-                        frm.free()
-                    rows = frm = None
+                    while len(held) > 1:    # everything but the offsets: one retry with the exact total
+                        held.pop().free()
                     capacity = int(e.args[1])
-            h_off = offs.download((len(images) + 1,), np.int64)
-        except Exception:
-            for b in (rows, offs, frm):
-                if b is not None:
-                    b.free()
-            raise
-        finally:
-            pix.free()                      # pvs_sift_dev has waited for the stream: nothing reads the pixels any more
+            h_off = offs.download((len(hw) + 1,), np.int64)
         self._rows_per_pixel = max(self._rows_per_pixel, 1.25 * total / max(n_pix, 1))
-        out = (rows, offs, len(images), total, kind, h_off)
+        out = (rows, offs, len(hw), total, kind, h_off)
         return out + (frm,) if frames else out
-
-    def _rows(self, image, out_kind, dtype, validated=False, frames=False):
-        got = self.device_descriptors([image], None, out_kind, _validated=validated, frames=frames)
-        rows, offs, total = got[0], got[1], got[3]
-        try:
-            out = rows.download((total, 128), dtype)
-            return (got[6].download((total, 6), np.float32), out) if frames else out
-        finally:
-            rows.free()
-            offs.free()
-            if frames:
-                got[6].free()
-
-    def raw(self, image: np.ndarray) -> np.ndarray:
-        """The uint8 rows (n, 128) as the kernel writes them."""
-        from .._ffi import DSIFT_U8
-        return self._rows(image, DSIFT_U8, np.uint8)
-
-    def descriptors(self, image: np.ndarray, normalised: bool = True) -> np.ndarray:
-        """float32 rows before quantisation: the normalised v (default) or the raw accumulators."""
-        from .._ffi import DSIFT_F32, DSIFT_F32_RAW
-        return self._rows(image, DSIFT_F32 if normalised else DSIFT_F32_RAW, np.float32)
 
     def detect_and_compute(self, image: np.ndarray):
         """-> (frames (n, 6) float32: x, y, size, angle, response, octave; uint8 rows (n, 128))"""
@@ -399,12 +365,6 @@ class KeypointSIFT(FeatureExtractorBase):
         """(n, 6) float32 frames in input-image coordinates: x, y, size (diameter), angle (degrees, from +x towards +y),
         response (|interpolated DoG|), octave (0 = the first octave, which is the enlarged image when `upsample`)."""
         return self.detect_and_compute(image)[0]
-
-    @_check_output_shape
-    def __call__(self, image: np.ndarray, /) -> np.ndarray:
-        from .._ffi import DSIFT_U8
-        super().__call__(image)
-        return self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
 
     def __repr__(self):
         return (f"{type(self).__name__}(nfeatures={self.nfeatures}, n_octave_layers={self.n_octave_layers}, "
@@ -418,15 +378,8 @@ class KeypointRootSIFT(KeypointSIFT):
     The encoders take its uint8 rows on the device and fuse the RootSIFT tail into their load (kind DESC_U8_ROOTSIFT)."""
     fused_rootsift = True
 
-    @_check_output_shape
     def __call__(self, image: np.ndarray, /) -> np.ndarray:
-        from .._ffi import DSIFT_U8
-        FeatureExtractorBase.__call__(self, image)
-        descriptors = self._rows(image, DSIFT_U8, np.uint8, validated=True).astype(np.float32)
-        if descriptors.shape[0]:
-            descriptors /= (descriptors.sum(axis=1, keepdims=True) + 1e-7)
-            descriptors = np.sqrt(descriptors)
-        return descriptors
+        return _hellinger(super().__call__(image))
 
 
 class Lambda(FeatureExtractorBase):

@@ -99,6 +99,7 @@ class LocalFeatureIndex:
         KeypointRootSIFT(nfeatures=2000)) and keep everything on the device.  Items may be images (ndarray) or paths; `paths`
         names the images (default: the path strings, or 0..N-1)."""
         from ._ffi import DSIFT_U8
+        from .encoders._base_encoder import _image_chunks
         from .features import KeypointRootSIFT
         if isinstance(batch, bool) or int(batch) != batch or batch < 1:
             raise ValueError(f"batch must be a positive integer, got {batch!r}")
@@ -118,7 +119,7 @@ class LocalFeatureIndex:
         try:
             for s in range(0, len(items), int(batch)):
                 chunk = [_load(it) for it in items[s:s + int(batch)]]
-                for run in _same_kind_runs(chunk):
+                for run in _image_chunks(chunk, int(batch), float("inf")):      # gray and colour runs: one kind per launch
                     got = extractor.device_descriptors(run, ctx, DSIFT_U8, frames=True)
                     got[1].free()
                     parts.append((got[0], got[6], int(got[3])))
@@ -200,17 +201,6 @@ def _load(item):
         from .encoders._base_encoder import _read_rgb
         return _read_rgb(item)
     return item
-
-
-def _same_kind_runs(images):
-    """Consecutive runs of all-gray or all-colour images: the extractor reads one pixel format per launch."""
-    runs = []
-    for im in images:
-        if runs and (runs[-1][-1].ndim == 2) == (im.ndim == 2):
-            runs[-1].append(im)
-        else:
-            runs.append([im])
-    return runs
 
 
 def _match_stage(ctx, rows_a, off_a, rows_b, off_b, pairs, ratio, mutual):
