@@ -411,9 +411,44 @@ int pvs_verify_dev(pvs_ctx* ctx, const float* d_frames_a, const int64_t* h_off_a
                    const int32_t* d_match_counts, double tol, int refine_rounds, int32_t* d_inliers, double* d_models, int32_t* d_best,
                    uint8_t* d_mask);
 
+/* ---------------------------------------------------------------- compact index: product quantisation + ADC search
+ * Jegou, Douze, Schmid, Perez (CVPR 2010; PAMI 2012): an encoding (optionally projected to d dimensions first) is cut into m
+ * sub-vectors of dsub dimensions (d = m dsub), each replaced by the index of its nearest of ksub <= 256 codewords; a query is
+ * scored against the codes through a per-query table (asymmetric distance computation), and a short list may be re-scored exactly.
+ * ALL arithmetic below is float32 with separate roundings -- a multiply, then an add, never an fma -- in the stated order, so that
+ * a restatement with float32 element operations gives the same bits.
+ *   quantiser  codebooks float32 [m][ksub][dsub].
+ *   encode     the code of row x in sub-space s is the j that minimises acc_j; acc_j starts at +0 and, for t = 0 .. dsub-1 ascending,
+ *              acc_j = acc_j + (x[s dsub + t] - c[s][j][t])^2.  Ties go to the lowest j.  Codes are uint8 [n][m].
+ *   table      lut[q][s][j] starts at +0 and adds q[s dsub + t] * c[s][j][t] for t ascending: an inner-product table, because the
+ *              engine's score is a cosine.
+ *   score      sum starts at +0 and adds lut[q][s][code[i][s]] for s = 0 .. m-1 ascending; score = (sum * inv_q[q]) * inv_db[i]
+ *              (the convention of pvs_cosine_dev).  inv_db[i] is 1/||row i|| of the unquantised row, stored when the index is built
+ *              (4 bytes per image).  A NULL inv_* pointer means 1.
+ *   ranking    (score descending, global index ascending), NaN last: the rule of pvs_topk_dev.
+ * n == 0 and nq == 0 are no-ops.  The _dev entry points enqueue on the context's stream and do not wait for it. */
+typedef struct pvs_pq pvs_pq;             /* product quantiser: codebooks [m][ksub][dsub] f32 on the device */
+int pvs_pq_create(pvs_ctx* ctx, const float* codebooks /*[m][ksub][dsub]*/, int m, int ksub, int dsub, pvs_pq** out);
+int pvs_pq_destroy(pvs_ctx* ctx, pvs_pq* pq);
+/* d_x float32 [n][m dsub] -> d_codes uint8 [n][m] */
+int pvs_pq_encode_dev(pvs_ctx* ctx, const pvs_pq* pq, const float* d_x, int64_t n, uint8_t* d_codes);
+/* d_q float32 [nq][m dsub] -> d_lut float32 [nq][m][ksub] */
+int pvs_pq_lut_dev(pvs_ctx* ctx, const pvs_pq* pq, const float* d_q, int64_t nq, float* d_lut);
+/* Scores of nq tables against N code rows and their ranking, with the semantics of pvs_cosine_topk_dev: row 0 has global index
+ * col_offset; merge != 0 merges into the running lists already in d_idx / d_val; 1 <= k <= N (k > 1024 needs merge == 0 and
+ * N <= 2^28, as there).  The nq x N score matrix never exists: scores pass through a bounded workspace panel into the top-k
+ * kernels.  d_idx int64 [nq][k], d_val float32 [nq][k].  Every code must be < ksub (a precondition: it is not checked). */
+int pvs_pq_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t nq, int m, int ksub, const uint8_t* d_codes, int64_t N,
+                         const float* d_inv_q, const float* d_inv_db, int k, int64_t col_offset, int merge, int64_t* d_idx,
+                         float* d_val);
+/* The exact cosine of each query with its R candidate rows, gathered by index: d_val[q][r] = ((sum_t Q[q][t] * X[c][t], t ascending,
+ * separate roundings) * inv_q[q]) * inv_db[c] with c = d_cand[q][r]; c < 0 (an unfilled list slot) or c >= N gives -inf. */
+int pvs_rescore_rows_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_X, int64_t N, int64_t d, const float* d_inv_q,
+                         const float* d_inv_db, const int64_t* d_cand /*[nq][R]*/, int64_t R, float* d_val /*[nq][R]*/);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
- * 2 cosine gemm, 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */
+ * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */
 #define PVS_TIMER_SLOTS 8
 int pvs_timers_enable(pvs_ctx* ctx, int on);
 int pvs_timers_reset(pvs_ctx* ctx);

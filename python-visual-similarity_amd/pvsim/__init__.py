@@ -4,6 +4,7 @@
     from pvsim.features import RootSIFT, SIFT, Lambda, DeepConvFeature
     from pvsim import eval                     # retrieve_top_k_similar, top_k_map, top_k_accuracy, rerank_spatial
     from pvsim import verify                   # LocalFeatureIndex, SpatialVerifier, match (spatial re-ranking)
+    from pvsim import CompactIndex, ProductQuantizer   # product-quantised index, ADC search (m + 4 bytes per image)
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -12,6 +13,8 @@ fallback.  Importing the package does not touch the GPU; the first computation d
 from .engine import Context, default_context, pack_descriptors
 from . import models
 from ._errors import CapacityError
+from .compact import CompactIndex, ProductQuantizer
 
 __version__ = "0.1.0"
-__all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError"]
+__all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
+           "CompactIndex", "ProductQuantizer"]

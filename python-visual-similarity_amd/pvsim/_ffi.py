@@ -117,6 +117,12 @@ SIGNATURES = {
     "pvs_match_u8_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
     "pvs_match_filter_dev": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, C.c_double, _int, _vp, _vp],
     "pvs_verify_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, C.c_double, _int, _vp, _vp, _vp, _vp],
+    "pvs_pq_create": [_vp, _vp, _int, _int, _int, _pp],
+    "pvs_pq_destroy": [_vp, _vp],
+    "pvs_pq_encode_dev": [_vp, _vp, _vp, _i64, _vp],
+    "pvs_pq_lut_dev": [_vp, _vp, _vp, _i64, _vp],
+    "pvs_pq_scan_topk_dev": [_vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _vp, _int, _i64, _int, _vp, _vp],
+    "pvs_rescore_rows_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

@@ -1,0 +1,539 @@
+"""Compact image index: product-quantised encodings searched with asymmetric distance computation.
+
+Jegou, Douze, Schmid, Perez (CVPR 2010; PAMI 2012) introduced VLAD together with its compression: project the encoding to a few
+hundred dimensions, product-quantise it to m bytes, score a query against the codes through a per-query inner-product table, and
+optionally re-rank a short list exactly.  `DeviceIndex` keeps 128 KiB per VLAD row on the device; a `CompactIndex` keeps m + 4
+bytes.  Everything here is float32; the definitions (summation orders, tie rules) are in include/pvsim.h."""
+from __future__ import annotations
+
+import numpy as np
+
+from .models import PCAModel
+
+__all__ = ["ProductQuantizer", "CompactIndex", "fit_projection", "save_arrays", "load_arrays"]
+
+_MAX_PROJECTION_TRAIN = 4096
+_CHUNK_ROWS = 8192
+
+
+def _f32_rows(a, what: str) -> np.ndarray:
+    a = np.asarray(a)
+    if a.dtype == np.float64:
+        raise TypeError(f"{what} is float64: the compact index is a float32 structure, pass float32 {what}")
+    if a.dtype != np.float32:
+        raise TypeError(f"{what} must be float32, got {a.dtype}")
+    if a.ndim != 2:
+        raise ValueError(f"{what} must be a 2-d array, got shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _check_rank_args(k, rerank, n: int, kept: bool):
+    """-> (k, rerank) as ints, validated against an index of n rows."""
+    if isinstance(k, bool) or int(k) != k or not 1 <= k <= n:
+        raise ValueError(f"k must be an integer with 1 <= k <= {n} (the number of indexed rows), got {k!r}")
+    if isinstance(rerank, bool) or int(rerank) != rerank or rerank < 0:
+        raise ValueError(f"rerank must be a non-negative integer, got {rerank!r}")
+    k, rerank = int(k), int(rerank)
+    if rerank:
+        if rerank < k:
+            raise ValueError(f"rerank={rerank} must be >= k={k}: the exact re-ranking orders the ADC top-rerank list")
+        if not kept:
+            raise ValueError("rerank needs the projected rows: build the index with keep_projected=True")
+        rerank = min(rerank, n)
+    return k, rerank
+
+
+# ------------------------------------------------------------------------------------------------ projection
+def fit_projection(vectors: np.ndarray, n_components: int, ctx=None) -> np.ndarray:
+    """W float32 (n_components, L) with orthonormal rows: the top eigenvectors of the UNCENTRED second-moment matrix of the rows.
+
+    No mean is subtracted, deliberately: the projection is there to preserve q.x, and a centred PCA preserves (q - mu).(x - mu),
+    a different similarity.  The fit goes by the n x n route (L is 32768 for VLAD, n at most 4096): G = X X^T on the device
+    (pvs_cosine_dev with NULL norms), eigh on the host, W = Lambda^(-1/2) U^T X on the device.  More than 4096 training rows are
+    subsampled deterministically (evenly spaced).  Rows are sign-fixed as learn.fit_pca does (largest |element| positive)."""
+    from .engine import default_context
+    from .learn import _one_blas_thread
+    x = _f32_rows(vectors, "training vectors")
+    n, L = x.shape
+    if n > _MAX_PROJECTION_TRAIN:
+        x = np.ascontiguousarray(x[(np.arange(_MAX_PROJECTION_TRAIN, dtype=np.int64) * n) // _MAX_PROJECTION_TRAIN])
+        n = _MAX_PROJECTION_TRAIN
+    d = int(n_components)
+    if not 1 <= d <= min(n, L):
+        raise ValueError(f"n_components={n_components} must be between 1 and min(n_train, L)={min(n, L)}")
+    ctx = ctx or default_context()
+    bufs = []
+    try:
+        d_x = ctx.buffer(x.nbytes).upload(x)
+        d_g = ctx.buffer(n * n * 4)
+        bufs += [d_x, d_g]
+        ctx.cosine_dev(d_x.ptr, n, d_x.ptr, n, L, None, None, d_g.ptr, n)
+        g = d_g.download((n, n), np.float32).astype(np.float64)
+        g = 0.5 * (g + g.T)
+        with _one_blas_thread():
+            vals, vecs = np.linalg.eigh(g)
+        vals, vecs = vals[::-1][:d], vecs[:, ::-1][:, :d]
+        if not vals[-1] > vals[0] * 1e-10:
+            raise ValueError(f"the training rows span fewer than n_components={d} dimensions")
+        a = np.ascontiguousarray((vecs / np.sqrt(vals)).T, dtype=np.float32)           # Lambda^(-1/2) U^T, (d, n)
+        xt = np.ascontiguousarray(x.T)                                                 # (L, n): W = a . (X^T)^T
+        d_a = ctx.buffer(a.nbytes).upload(a)
+        d_xt = ctx.buffer(xt.nbytes).upload(xt)
+        d_w = ctx.buffer(d * L * 4)
+        bufs += [d_a, d_xt, d_w]
+        ctx.cosine_dev(d_a.ptr, d, d_xt.ptr, L, n, None, None, d_w.ptr, L)
+        w = d_w.download((d, L), np.float32)
+    finally:
+        for b in bufs:
+            b.free()
+    piv = np.argmax(np.abs(w), axis=1)
+    sign = np.sign(w[np.arange(d), piv])
+    sign[sign == 0] = 1
+    return np.ascontiguousarray(w * sign[:, None].astype(np.float32))
+
+
+def _projection_matrix(projection, L: int):
+    """None | PCAModel | array -> W float32 (d, L) or None."""
+    if projection is None:
+        return None
+    w = projection.components_ if isinstance(projection, PCAModel) or hasattr(projection, "components_") else projection
+    w = np.asarray(w)
+    if w.dtype == np.float64:
+        raise TypeError("projection is float64: the compact index is a float32 structure, pass a float32 projection")
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    if w.ndim != 2 or w.shape[1] != L:
+        raise ValueError(f"projection must be (d, {L}), got {w.shape}")
+    return w
+
+
+# ------------------------------------------------------------------------------------------------ quantiser
+class ProductQuantizer:
+    """m sub-spaces of dsub = d / m dimensions, ksub <= 256 codewords each; codes are uint8 (n, m).
+
+    ProductQuantizer(m, ksub).fit(vectors) trains one k-means per sub-space on the device (learn.fit_kmeans);
+    ProductQuantizer.from_codebooks(codebooks) takes given tables (m, ksub, dsub)."""
+
+    def __init__(self, m: int, ksub: int = 256, ctx=None):
+        if isinstance(m, bool) or int(m) != m or m < 1:
+            raise ValueError(f"m must be a positive integer, got {m!r}")
+        if isinstance(ksub, bool) or int(ksub) != ksub or not 1 <= ksub <= 256:
+            raise ValueError(f"ksub must be between 1 and 256 (codes are one byte per sub-space), got {ksub!r}")
+        self.m, self.ksub = int(m), int(ksub)
+        self.codebooks = None
+        self.projection = None           # optional (d, L) projection that goes with the codebooks (models.save_model kind "pq")
+        self._ctx = ctx
+        self._table = None
+
+    @classmethod
+    def from_codebooks(cls, codebooks, ctx=None) -> "ProductQuantizer":
+        c = np.asarray(codebooks)
+        if c.dtype == np.float64:
+            raise TypeError("codebooks are float64: the compact index is a float32 structure, pass float32 codebooks")
+        c = np.ascontiguousarray(c, dtype=np.float32)
+        if c.ndim != 3:
+            raise ValueError(f"codebooks must be (m, ksub, dsub), got shape {c.shape}")
+        pq = cls(c.shape[0], c.shape[1], ctx)
+        pq.codebooks = c
+        return pq
+
+    @property
+    def dsub(self) -> int:
+        return 0 if self.codebooks is None else self.codebooks.shape[2]
+
+    @property
+    def d(self) -> int:
+        return self.m * self.dsub
+
+    @property
+    def context(self):
+        if self._ctx is None:
+            from .engine import default_context
+            self._ctx = default_context()
+        return self._ctx
+
+    def _check_rows(self, vectors, what="vectors"):
+        x = _f32_rows(vectors, what)
+        if x.shape[1] % self.m:
+            raise ValueError(f"d={x.shape[1]} is not a multiple of m={self.m} (d % m must be 0)")
+        return x
+
+    def fit(self, vectors, random_state=None, max_iter: int = 25) -> "ProductQuantizer":
+        from .learn import DeviceRows, fit_kmeans, _rng
+        x = self._check_rows(vectors, "training vectors")
+        n, d = x.shape
+        if n < self.ksub:
+            raise ValueError(f"n={n} training rows are fewer than ksub={self.ksub} codewords (need n >= ksub)")
+        dsub = d // self.m
+        rng = _rng(random_state)
+        books = np.empty((self.m, self.ksub, dsub), np.float32)
+        import warnings
+        for s in range(self.m):
+            rows = DeviceRows.from_host(self.context, x[:, s * dsub:(s + 1) * dsub])
+            try:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore", UserWarning)         # duplicate points in a sub-space: fewer distinct codewords is fine
+                    books[s] = fit_kmeans(rows, self.ksub, random_state=rng, max_iter=max_iter).cluster_centers_
+            finally:
+                rows.free()
+        self.codebooks = books
+        self._drop_table()
+        return self
+
+    def table(self):
+        """The device table (engine.PQTable), created on first use."""
+        if self.codebooks is None:
+            raise ValueError("the quantiser has no codebooks: call fit() or use from_codebooks()")
+        if self._table is None or self._table.handle is None:
+            self._table = self.context.pq(self.codebooks)
+        return self._table
+
+    def _drop_table(self):
+        if self._table is not None:
+            self._table.close()
+            self._table = None
+
+    def encode(self, vectors) -> np.ndarray:
+        x = self._check_rows(vectors)
+        if self.codebooks is None:
+            raise ValueError("the quantiser has no codebooks: call fit() or use from_codebooks()")
+        if x.shape[1] != self.d:
+            raise ValueError(f"vectors have d={x.shape[1]}, the quantiser d={self.d}")
+        n = x.shape[0]
+        if n == 0:
+            return np.zeros((0, self.m), np.uint8)
+        ctx = self.context
+        d_x = ctx.buffer(x.nbytes).upload(x)
+        d_c = ctx.buffer(n * self.m)
+        try:
+            ctx.pq_encode_dev(self.table(), d_x.ptr, n, d_c.ptr)
+            return d_c.download((n, self.m), np.uint8)
+        finally:
+            d_x.free()
+            d_c.free()
+
+    def decode(self, codes) -> np.ndarray:
+        """codes uint8 (n, m) -> the codewords they name, float32 (n, d)."""
+        if self.codebooks is None:
+            raise ValueError("the quantiser has no codebooks: call fit() or use from_codebooks()")
+        c = np.asarray(codes)
+        if c.ndim != 2 or c.shape[1] != self.m:
+            raise ValueError(f"codes must be (n, {self.m}), got {c.shape}")
+        if c.size and int(c.max()) >= self.ksub:
+            raise ValueError(f"a code exceeds ksub={self.ksub}")
+        return np.concatenate([self.codebooks[s][c[:, s].astype(np.int64)] for s in range(self.m)], axis=1)
+
+    def close(self):
+        self._drop_table()
+
+
+# ------------------------------------------------------------------------------------------------ persistence (no device needed)
+def save_arrays(path: str, paths, codes, inv_norms, codebooks, projection=None, projected=None) -> None:
+    """One plain .npz of arrays (numpy.load(allow_pickle=False)), in the style of pvsim.index."""
+    arrays = dict(kind="compact_index", paths=np.array(list(paths), dtype=np.str_), codes=np.ascontiguousarray(codes, dtype=np.uint8),
+                  inv_norms=np.ascontiguousarray(inv_norms, dtype=np.float32), codebooks=np.ascontiguousarray(codebooks, dtype=np.float32))
+    if projection is not None:
+        arrays["projection"] = np.ascontiguousarray(projection, dtype=np.float32)
+    if projected is not None:
+        arrays["projected"] = np.ascontiguousarray(projected, dtype=np.float32)
+    np.savez(path, **arrays)
+
+
+def load_arrays(path: str) -> dict:
+    with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as z:
+        if "kind" not in z.files or str(z["kind"]) != "compact_index":
+            raise ValueError(f"{path}: not a compact index file")
+        out = dict(paths=[str(p) for p in z["paths"]], codes=z["codes"], inv_norms=z["inv_norms"], codebooks=z["codebooks"],
+                   projection=z["projection"] if "projection" in z.files else None,
+                   projected=z["projected"] if "projected" in z.files else None)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ index
+class CompactIndex:
+    """Paths + uint8 codes (N, m) + float32 1/||row|| (N,) resident on the device, searched by pvs_pq_scan_topk_dev.
+
+    `projection` is None (d = L), a PCAModel (its components_ are used; no mean is subtracted) or an array (d, L);
+    `projected` are the projected float32 rows (N, d), kept only for exact re-ranking (`rank(..., rerank=R)`).
+    The arrays are uploaded on first use."""
+
+    def __init__(self, paths, codes, inv_norms, quantizer, projection=None, projected=None, ctx=None):
+        if not isinstance(quantizer, ProductQuantizer):
+            quantizer = ProductQuantizer.from_codebooks(quantizer, ctx)
+        if quantizer.codebooks is None:
+            raise ValueError("the quantiser has no codebooks")
+        self.quantizer = quantizer
+        self._paths = [str(p) for p in paths]
+        n = len(self._paths)
+        codes = np.asarray(codes)
+        if codes.dtype != np.uint8 or codes.shape != (n, quantizer.m):
+            raise ValueError(f"codes must be uint8 ({n}, {quantizer.m}), got {codes.dtype} {codes.shape}")
+        inv = np.asarray(inv_norms)
+        if inv.dtype == np.float64:
+            raise TypeError("inv_norms are float64: the compact index is a float32 structure, pass float32 inv_norms")
+        if inv.shape != (n,):
+            raise ValueError(f"inv_norms must be ({n},), got {inv.shape}")
+        self._L = None if projection is None else int(np.asarray(getattr(projection, "components_", projection)).shape[1])
+        self._w = _projection_matrix(projection, self._L) if projection is not None else None
+        if self._w is not None and self._w.shape[0] != quantizer.d:
+            raise ValueError(f"the projection gives d={self._w.shape[0]}, the quantiser has d={quantizer.d}")
+        self._keep = projected is not None
+        if self._keep:
+            projected = _f32_rows(projected, "projected rows")
+            if projected.shape != (n, quantizer.d):
+                raise ValueError(f"projected rows must be ({n}, {quantizer.d}), got {projected.shape}")
+        self._ctx = ctx or quantizer._ctx
+        self._host = dict(codes=np.ascontiguousarray(codes), inv=np.ascontiguousarray(inv, dtype=np.float32), projected=projected)
+        self._dev = None
+
+    # ---- building
+    @classmethod
+    def fit(cls, source, m: int = 64, n_components=None, projection=None, ksub: int = 256, keep_projected: bool = False,
+            random_state=None, train=None, ctx=None, max_iter: int = 25) -> "CompactIndex":
+        """Train the projection and the quantiser on `train` (default: the database itself), project the database, record
+        1/||projected row||, encode, and keep codes, norms and paths on the device.  `source` is an encoding map {path: vector}
+        or a DeviceIndex (whose resident rows are read in place)."""
+        from .engine import default_context
+        from .index import DeviceIndex
+        resident = source if isinstance(source, DeviceIndex) else None
+        if resident is not None:
+            paths, mat = list(resident.keys()), resident.matrix
+            ctx = ctx or resident.ctx
+        else:
+            paths = list(source.keys())
+            mat = np.array(list(source.values()))
+        mat = _f32_rows(mat, "database")
+        n, L = mat.shape
+        if n_components is not None and projection is not None:
+            raise ValueError("give n_components or projection, not both")
+        pq = ProductQuantizer(m, ksub, ctx)                                  # validates m, ksub before anything is computed
+        tr = mat if train is None else _f32_rows(np.array(list(train.values())) if hasattr(train, "values") else train, "train")
+        if tr.shape[1] != L:
+            raise ValueError(f"train rows have L={tr.shape[1]}, the database L={L}")
+        d = L if (n_components is None and projection is None) else (
+            int(n_components) if n_components is not None else int(np.asarray(getattr(projection, "components_", projection)).shape[0]))
+        if d % pq.m:
+            raise ValueError(f"d={d} is not a multiple of m={pq.m} (d % m must be 0)")
+        if tr.shape[0] < pq.ksub:
+            raise ValueError(f"n={tr.shape[0]} training rows are fewer than ksub={pq.ksub} codewords (need n >= ksub)")
+        ctx = ctx or default_context()
+        pq._ctx = ctx
+        from .engine import DeviceBuffer
+        w = fit_projection(tr, n_components, ctx) if n_components is not None else _projection_matrix(projection, L)
+        live = []                                    # device buffers of this call: all of them are freed if anything below raises
+
+        def take(nbytes):
+            live.append(ctx.buffer(max(nbytes, 16)))
+            return live[-1]
+
+        def give(b):
+            if b in live:                            # views into the kept rows are not owned
+                live.remove(b)
+                b.free()
+
+        def project_chunks(host, dev_ptr=None, dest=None):
+            """yields (first row, rows, device buffer of the projected rows (rows, d)) over chunks of the matrix; `dest(r0, rn)`
+            names where a chunk goes (a view into the kept rows), otherwise it is a temporary the consumer gives back"""
+            for r0 in range(0, host.shape[0], _CHUNK_ROWS):
+                rn = min(_CHUNK_ROWS, host.shape[0] - r0)
+                out = dest(r0, rn) if dest is not None else take(rn * d * 4)
+                if d_w is None:                      # no projection: the rows themselves
+                    out.upload(host[r0:r0 + rn])
+                elif dev_ptr is not None:            # resident rows are read in place
+                    ctx.cosine_dev(dev_ptr + r0 * L * 4, rn, d_w.ptr, d, L, None, None, out.ptr, d)
+                else:
+                    own = take(rn * L * 4).upload(host[r0:r0 + rn])
+                    ctx.cosine_dev(own.ptr, rn, d_w.ptr, d, L, None, None, out.ptr, d)
+                    ctx.sync()
+                    give(own)
+                yield r0, rn, out
+
+        try:
+            d_w = take(w.nbytes).upload(w) if w is not None else None
+            db_ptr = resident._db.ptr if resident is not None else None
+            # the quantiser is trained on the projected training rows
+            ytr = np.empty((tr.shape[0], d), np.float32)
+            for r0, rn, buf in project_chunks(tr, db_ptr if train is None else None):
+                ytr[r0:r0 + rn] = buf.download((rn, d), np.float32)
+                give(buf)
+            pq.fit(ytr, random_state=random_state, max_iter=max_iter)
+            table = pq.table()
+            d_codes, d_inv = take(n * pq.m), take(n * 4)
+            d_proj = take(n * d * 4) if keep_projected else None
+            # kept rows are written where they stay: a chunk's buffer is then a view into d_proj
+            dest = (lambda r0, rn: DeviceBuffer.view(ctx, d_proj.ptr + r0 * d * 4, rn * d * 4)) if keep_projected else None
+            if train is None:                        # the database was the training set: its projected rows are in ytr
+                def chunks():
+                    for r0 in range(0, n, _CHUNK_ROWS):
+                        rn = min(_CHUNK_ROWS, n - r0)
+                        out = dest(r0, rn) if dest is not None else take(rn * d * 4)
+                        yield r0, rn, out.upload(ytr[r0:r0 + rn])
+                chunks = chunks()
+            else:
+                chunks = project_chunks(mat, db_ptr, dest)
+            for r0, rn, buf in chunks:
+                ctx.row_inv_norms_dev(buf.ptr, rn, d, d_inv.ptr + r0 * 4)
+                ctx.pq_encode_dev(table, buf.ptr, rn, d_codes.ptr + r0 * pq.m)
+                ctx.sync()
+                give(buf)
+            if d_w is not None:
+                give(d_w)
+        except BaseException:
+            for b in live:
+                b.free()
+            pq.close()
+            raise
+        self = cls.__new__(cls)
+        self.quantizer, self._paths, self._ctx = pq, [str(p) for p in paths], ctx
+        self._L, self._w, self._keep, self._host = L, w, bool(keep_projected), None
+        self._dev = dict(codes=d_codes, inv=d_inv, projected=d_proj, w=None)
+        return self
+
+    # ---- device residency
+    @property
+    def context(self):
+        if self._ctx is None:
+            from .engine import default_context
+            self._ctx = default_context()
+        return self._ctx
+
+    def _device(self) -> dict:
+        if self._dev is None:
+            ctx, h = self.context, self._host
+            self._dev = dict(codes=ctx.buffer(max(h["codes"].nbytes, 16)).upload(h["codes"]),
+                             inv=ctx.buffer(max(h["inv"].nbytes, 16)).upload(h["inv"]),
+                             projected=ctx.buffer(max(h["projected"].nbytes, 16)).upload(h["projected"]) if self._keep else None,
+                             w=None)
+            self._host = None
+        if self._w is not None and self._dev["w"] is None:
+            self._dev["w"] = self.context.buffer(self._w.nbytes).upload(self._w)
+        return self._dev
+
+    # ---- the dict-like surface the retrieval functions use
+    def __len__(self):
+        return len(self._paths)
+
+    @property
+    def paths(self) -> list:
+        return list(self._paths)
+
+    def keys(self):
+        return list(self._paths)
+
+    @property
+    def d(self) -> int:
+        return self.quantizer.d
+
+    @property
+    def input_dim(self) -> int:
+        """length of the vectors `rank` takes (L with a projection, d without)"""
+        return self._w.shape[1] if self._w is not None else self.quantizer.d
+
+    @property
+    def projection(self):
+        return self._w
+
+    @property
+    def nbytes_breakdown(self) -> dict:
+        n, q = len(self), self.quantizer
+        return {"codes": n * q.m, "inv_norms": n * 4, "codebooks": q.m * q.ksub * q.dsub * 4,
+                "projection": 0 if self._w is None else self._w.nbytes, "projected": n * q.d * 4 if self._keep else 0}
+
+    @property
+    def nbytes(self) -> int:
+        """device bytes: N (m + 4) for codes and norms, plus the tables (and the projected rows when they are kept)"""
+        return int(sum(self.nbytes_breakdown.values()))
+
+    def _download(self):
+        n, q, dev = len(self), self.quantizer, self._device()
+        return (dev["codes"].download((n, q.m), np.uint8), dev["inv"].download((n,), np.float32),
+                dev["projected"].download((n, q.d), np.float32) if self._keep else None)
+
+    def project(self, vectors) -> np.ndarray:
+        """The device's own projection of float32 rows (n, input_dim) -> (n, d)."""
+        x = _f32_rows(vectors, "vectors")
+        if x.shape[1] != self.input_dim:
+            raise ValueError(f"vectors have {x.shape[1]} dimensions, the index takes {self.input_dim}")
+        if self._w is None or x.shape[0] == 0:
+            return x.copy() if self._w is None else np.zeros((0, self.d), np.float32)
+        ctx, dev = self.context, self._device()
+        d_x = ctx.buffer(x.nbytes).upload(x)
+        d_y = ctx.buffer(x.shape[0] * self.d * 4)
+        try:
+            ctx.cosine_dev(d_x.ptr, x.shape[0], dev["w"].ptr, self.d, x.shape[1], None, None, d_y.ptr, self.d)
+            return d_y.download((x.shape[0], self.d), np.float32)
+        finally:
+            d_x.free()
+            d_y.free()
+
+    # ---- search
+    def rank(self, query_vecs, k: int, rerank: int = 0):
+        """-> (idx (nq, k) int64, val (nq, k) float32): the ADC ranking (score descending, index ascending); with rerank=R >= k
+        the ADC top-R re-scored exactly against the kept projected rows and ordered by (exact score descending, index ascending)."""
+        q = _f32_rows(query_vecs, "query")
+        if q.shape[1] != self.input_dim:
+            raise ValueError(f"query and database dimensions differ: {q.shape[1]} vs {self.input_dim}")
+        n, pq = len(self), self.quantizer
+        k, rerank = _check_rank_args(k, rerank, n, self._keep)
+        nq, d, kk = q.shape[0], pq.d, rerank or k
+        if nq == 0:
+            return np.zeros((0, k), np.int64), np.zeros((0, k), np.float32)
+        ctx, dev = self.context, self._device()
+        bufs = []
+
+        def buf(nbytes):
+            bufs.append(ctx.buffer(max(nbytes, 16)))
+            return bufs[-1]
+
+        try:
+            d_q = buf(q.nbytes).upload(q)
+            if self._w is not None:
+                d_y = buf(nq * d * 4)
+                ctx.cosine_dev(d_q.ptr, nq, dev["w"].ptr, d, q.shape[1], None, None, d_y.ptr, d)
+            else:
+                d_y = d_q
+            d_invq, d_lut = buf(nq * 4), buf(nq * pq.m * pq.ksub * 4)
+            d_idx, d_val = buf(nq * kk * 8), buf(nq * kk * 4)
+            ctx.row_inv_norms_dev(d_y.ptr, nq, d, d_invq.ptr)
+            ctx.pq_lut_dev(pq.table(), d_y.ptr, nq, d_lut.ptr)
+            ctx.pq_scan_topk_dev(d_lut.ptr, nq, pq.m, pq.ksub, dev["codes"].ptr, n, d_invq.ptr, dev["inv"].ptr, kk, 0, False,
+                                 d_idx.ptr, d_val.ptr)
+            if not rerank:
+                return d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
+            d_exact = buf(nq * kk * 4)
+            ctx.rescore_rows_dev(d_y.ptr, nq, dev["projected"].ptr, n, d, d_invq.ptr, dev["inv"].ptr, d_idx.ptr, kk, d_exact.ptr)
+            idx, val = d_idx.download((nq, kk), np.int64), d_exact.download((nq, kk), np.float32)
+        finally:
+            for b in bufs:
+                b.free()
+        return order_exact(idx, val, k)
+
+    # ---- persistence
+    def save(self, path: str) -> None:
+        codes, inv, proj = self._download()
+        save_arrays(path, self._paths, codes, inv, self.quantizer.codebooks, self._w, proj)
+
+    @classmethod
+    def load(cls, path: str, ctx=None) -> "CompactIndex":
+        a = load_arrays(path)
+        return cls(a["paths"], a["codes"], a["inv_norms"], ProductQuantizer.from_codebooks(a["codebooks"], ctx), a["projection"],
+                   a["projected"], ctx)
+
+    def close(self):
+        if self._dev is not None:
+            for b in self._dev.values():
+                if b is not None:
+                    b.free()
+            self._dev = None
+        self.quantizer.close()
+
+
+def order_exact(idx: np.ndarray, val: np.ndarray, k: int):
+    """Rows of candidates -> the first k by (score descending, index ascending), NaN last."""
+    out_i = np.empty((idx.shape[0], k), np.int64)
+    out_v = np.empty((idx.shape[0], k), np.float32)
+    for r in range(idx.shape[0]):
+        nan = np.isnan(val[r])
+        key = np.where(nan, np.float32(-np.inf), val[r])
+        o = np.lexsort((idx[r], -key, nan))[:k]
+        out_i[r], out_v[r] = idx[r][o], val[r][o]
+    return out_i, out_v

@@ -85,6 +85,11 @@ class PCATable(_Handle):
     C = Din = 0
 
 
+class PQTable(_Handle):
+    _destroy = "pvs_pq_destroy"
+    m = ksub = dsub = 0
+
+
 class DeviceBuffer:
     """A block of device memory owned by a Context (pvs_malloc / pvs_free); .ptr is the raw device address."""
 
@@ -274,6 +279,17 @@ class Context:
         p.C, p.Din = comp.shape
         return p
 
+    def pq(self, codebooks) -> PQTable:
+        """Product quantiser table from codebooks (m, ksub, dsub) float32."""
+        c = np.ascontiguousarray(codebooks, dtype=np.float32)
+        if c.ndim != 3:
+            raise ValueError("codebooks must be (m, ksub, dsub)")
+        h = C.c_void_p()
+        check(_ffi.lib().pvs_pq_create(self.handle, ptr(c), c.shape[0], c.shape[1], c.shape[2], C.byref(h)))
+        t = PQTable(self, h)
+        t.m, t.ksub, t.dsub = c.shape
+        return t
+
     # ------------------------------------------------------------------ encoders (host arrays)
     @staticmethod
     def _check_desc(packed, kind, dim):
@@ -408,6 +424,21 @@ class Context:
         check(_ffi.lib().pvs_cosine_topk_filtered_dev(self.handle, ptr(d_q), nq, ptr(d_db), N, L, ptr(d_invq), ptr(d_invdb), k,
                                                       ptr(d_idx), ptr(d_val), st))
         return {"filtered": bool(st[0]), "redone_exact": int(st[1]), "candidates": int(st[2]), "slots": int(st[3])}
+
+    # compact index
+    def pq_encode_dev(self, pq, d_x, n, d_codes):
+        check(_ffi.lib().pvs_pq_encode_dev(self.handle, pq.handle, ptr(d_x), n, ptr(d_codes)))
+
+    def pq_lut_dev(self, pq, d_q, nq, d_lut):
+        check(_ffi.lib().pvs_pq_lut_dev(self.handle, pq.handle, ptr(d_q), nq, ptr(d_lut)))
+
+    def pq_scan_topk_dev(self, d_lut, nq, m, ksub, d_codes, N, d_invq, d_invdb, k, col_offset, merge, d_idx, d_val):
+        check(_ffi.lib().pvs_pq_scan_topk_dev(self.handle, ptr(d_lut), nq, m, ksub, ptr(d_codes), N, ptr(d_invq), ptr(d_invdb), k,
+                                              col_offset, int(merge), ptr(d_idx), ptr(d_val)))
+
+    def rescore_rows_dev(self, d_q, nq, d_x, N, d, d_invq, d_invdb, d_cand, R, d_val):
+        check(_ffi.lib().pvs_rescore_rows_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, d, ptr(d_invq), ptr(d_invdb), ptr(d_cand), R,
+                                              ptr(d_val)))
 
     def f32_to_f16_dev(self, d_src, n, d_dst):
         check(_ffi.lib().pvs_f32_to_f16_dev(self.handle, ptr(d_src), n, ptr(d_dst)))

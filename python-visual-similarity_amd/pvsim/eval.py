@@ -34,14 +34,30 @@ def _first_rows(encoder, queries) -> np.ndarray:
 def _vectors_and_paths(encoding_map):
     """-> ((N, L) matrix, paths, resident index or None).  A pvsim.index.DeviceIndex already holds the matrix (and a normalised
     copy on the GPU); a plain dict is stacked the way the reference does it (eval.py:28)."""
+    from .compact import CompactIndex
     from .index import DeviceIndex
     if isinstance(encoding_map, DeviceIndex):
         return encoding_map.matrix, list(encoding_map.keys()), encoding_map
+    if isinstance(encoding_map, CompactIndex):             # codes only: there is no host matrix, N comes from len()
+        return None, encoding_map.paths, encoding_map
     return np.array(list(encoding_map.values())), list(encoding_map.keys()), None
+
+
+def _rank_compact(query_vecs: np.ndarray, index, k: int | None, rerank: int = 0):
+    """_rank against a pvsim.compact.CompactIndex (ADC ranking, optionally re-ranked exactly on the ADC top-`rerank`)."""
+    if k is None:
+        raise ValueError("a CompactIndex ranks a finite list: pass k (k=None asks for the complete ranking, which needs the "
+                         "full-precision rows -- use a dict or a DeviceIndex for that)")
+    kk = max(0, min(int(k), len(index)))
+    if query_vecs.shape[0] == 0 or kk == 0:
+        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float32)
+    return index.rank(query_vecs, kk, rerank=rerank)             # rerank < k raises there, as it does for a direct call
 
 
 def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None, resident=None):
     """-> (indices (nq, k') int64, scores (nq, k')) with k' = min(k, N) (k=None: all N)."""
+    if all_vectors is None:                                     # a CompactIndex: no host matrix
+        return _rank_compact(query_vecs, resident, k)
     n = all_vectors.shape[0]
     kk = n if k is None else max(0, min(int(k), n))
     if query_vecs.shape[0] == 0 or kk == 0:
@@ -60,13 +76,19 @@ def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=No
 
 
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
-                           k: int = 5) -> list[tuple[str, float]]:
-    """[(image_path, similarity)] of the k most similar database entries, best first."""
+                           k: int = 5, rerank: int = 0) -> list[tuple[str, float]]:
+    """[(image_path, similarity)] of the k most similar database entries, best first.  `rerank=R` (CompactIndex only): the
+    ADC top-R re-ranked by the exact cosine of the kept projected rows."""
     all_vectors, all_paths, resident = _vectors_and_paths(dataset)
     query_vector = encoder.encode(uploaded_image)
     if query_vector.ndim == 1:
         query_vector = query_vector.reshape(1, -1)
-    idx, val = _rank(query_vector[:1], all_vectors, k, getattr(encoder, "context", None), resident)
+    if all_vectors is None:                                     # a CompactIndex: the only index that can re-rank
+        idx, val = _rank_compact(query_vector[:1], resident, k, rerank)
+    else:
+        if rerank:
+            raise ValueError("rerank= applies to a CompactIndex only")
+        idx, val = _rank(query_vector[:1], all_vectors, k, getattr(encoder, "context", None), resident)
     return [(all_paths[i], s) for i, s in zip(idx[0], val[0])]
 
 

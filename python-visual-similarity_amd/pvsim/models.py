@@ -39,8 +39,14 @@ class PCAModel:
 
 def save_model(path: str, model) -> None:
     """Persist a fitted clustering / PCA model (scikit-learn object or one of the classes above) as a plain
-    .npz of arrays -- the engine's replacement for the reference's joblib pickles (nothing executable)."""
-    if hasattr(model, "cluster_centers_"):
+    .npz of arrays -- the engine's replacement for the reference's joblib pickles (nothing executable).  Kind "pq": the
+    codebooks of a pvsim.compact.ProductQuantizer, plus its `.projection` (d, L) when it carries one."""
+    if hasattr(model, "codebooks") and hasattr(model, "ksub"):           # pvsim.compact.ProductQuantizer (+ optional projection)
+        if model.codebooks is None:
+            raise ValueError("cannot serialise a product quantiser that has not been fitted")
+        extra = {} if getattr(model, "projection", None) is None else {"projection": np.asarray(model.projection, np.float32)}
+        np.savez(path, kind="pq", codebooks=np.asarray(model.codebooks, np.float32), **extra)
+    elif hasattr(model, "cluster_centers_"):
         np.savez(path, kind="kmeans", cluster_centers=np.asarray(model.cluster_centers_, np.float32))
     elif hasattr(model, "means_"):
         np.savez(path, kind="gmm", weights=model.weights_, means=model.means_, covariances=model.covariances_)
@@ -63,4 +69,9 @@ def load_model(path: str):
             return GMMModel(z["weights"], z["means"], z["covariances"])
         if kind == "pca":
             return PCAModel(z["components"], z["mean"])
+        if kind == "pq":
+            from .compact import ProductQuantizer
+            pq = ProductQuantizer.from_codebooks(z["codebooks"])
+            pq.projection = z["projection"] if "projection" in z.files else None
+            return pq
     raise ValueError(f"{path}: unknown model kind {kind!r}")
