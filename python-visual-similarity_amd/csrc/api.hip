@@ -18,7 +18,9 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-int ws_reserve(pvs_ctx* ctx, int which, size_t bytes, void** out) {
+static_assert(WS_VERIFY_SMALL + 1 == pvs_ctx::NWS, "one block per WsSlot");
+
+int ws_reserve(pvs_ctx* ctx, WsSlot which, size_t bytes, void** out) {
   if (bytes == 0) bytes = 16;
   if (ctx->ws_bytes[which] < bytes) {
     if (ctx->ws[which]) {
@@ -53,7 +55,7 @@ static int drain_timers(pvs_ctx* ctx) {
 
 // ---- device blocks of table objects: recycled through the context (see pvs_ctx::block_cache)
 static int table_alloc(pvs_ctx* ctx, void** dptr, size_t bytes) {
-  const size_t want = (std::max<size_t>(bytes, 16) + 255) / 256 * 256;
+  const size_t want = ws_round(std::max<size_t>(bytes, 16));
   auto it = ctx->block_cache.lower_bound(want);
   if (it != ctx->block_cache.end() && it->first <= 2 * want + 4096) {
     *dptr = it->second;
@@ -542,8 +544,7 @@ static int project_if_needed(pvs_ctx* ctx, const pvs_pca* pca, int model_dim, co
   if (pca->C != model_dim)
     PVS_FAIL(PVS_ERR_DIM, "PCA outputs %d components but the clustering model expects %d", pca->C, model_dim);
   float* proj = nullptr;
-  PVS_TRY(ws_reserve(ctx, 3, (size_t)std::max<int64_t>(total, 1) * pca->C * sizeof(float),
-                     reinterpret_cast<void**>(&proj)));
+  PVS_TRY(ws_reserve(ctx, WS_PROJECTED, (size_t)std::max<int64_t>(total, 1) * pca->C * sizeof(float), &proj));
   PVS_TRY(launch_pca(ctx, pca, d_desc, kind, total, proj));
   d_desc = proj;
   kind = PVS_DESC_F32;
@@ -590,8 +591,7 @@ PVS_EXPORT int pvs_vlad_encode_dev(pvs_ctx* ctx, const pvs_codebook* cb, const p
   }
   int32_t* labels = d_labels;
   if (!labels)
-    PVS_TRY(ws_reserve(ctx, 1, (size_t)std::max<int64_t>(total_desc, 1) * sizeof(int32_t),
-                       reinterpret_cast<void**>(&labels)));
+    PVS_TRY(ws_reserve(ctx, WS_SCRATCH, (size_t)std::max<int64_t>(total_desc, 1) * sizeof(int32_t), &labels));
   const float2* rowstat = nullptr;   // uint8 rows: per-row (sum + 1e-7, reciprocal) left by the prefilter for the aggregate pass
   PVS_TRY(launch_assign(ctx, cb, x, kind, total_desc, ld, labels, &rowstat));
   return launch_vlad_aggregate(ctx, cb, x, kind, ld, d_offsets, n_images, labels, *prm, d_out, d_inv_norm, false, rowstat, total_desc);
@@ -624,18 +624,17 @@ PVS_EXPORT int pvs_vlad_encode(pvs_ctx* ctx, const pvs_codebook* cb, const pvs_p
   const size_t out_elems = (size_t)n_images * cb->K * cb->D;
   char* d_x = nullptr;
   char* d_small = nullptr;
-  float* d_out = nullptr;
-  PVS_TRY(ws_reserve(ctx, 0, desc_bytes, reinterpret_cast<void**>(&d_x)));
-  const size_t off_bytes = (size_t)(n_images + 1) * sizeof(int64_t);
-  const size_t lab_off = (off_bytes + 255) / 256 * 256;
-  PVS_TRY(ws_reserve(ctx, 2, lab_off + (size_t)std::max<int64_t>(total, 1) * sizeof(int32_t) + out_elems * 4 + 256,
-                     reinterpret_cast<void**>(&d_small)));
-  int64_t* d_off = reinterpret_cast<int64_t*>(d_small);
-  int32_t* d_lab = reinterpret_cast<int32_t*>(d_small + lab_off);
-  const size_t out_off = (lab_off + (size_t)std::max<int64_t>(total, 1) * 4 + 255) / 256 * 256;
-  d_out = reinterpret_cast<float*>(d_small + out_off);
+  PVS_TRY(ws_reserve(ctx, WS_STAGE_IN, desc_bytes, &d_x));
+  WsLayout<> lay;
+  const auto off_p = lay.add<int64_t>((size_t)n_images + 1);
+  const auto lab_p = lay.add<int32_t>((size_t)std::max<int64_t>(total, 1));
+  const auto out_p = lay.add<float>(out_elems);
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, lay.bytes(), &d_small));
+  int64_t* d_off = off_p(d_small);
+  int32_t* d_lab = lab_p(d_small);
+  float* d_out = out_p(d_small);
   if (desc_bytes) PVS_HIP(hipMemcpyAsync(d_x, desc, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
-  PVS_HIP(hipMemcpyAsync(d_off, offsets, off_bytes, hipMemcpyHostToDevice, ctx->stream));
+  PVS_HIP(hipMemcpyAsync(d_off, offsets, (size_t)(n_images + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   PVS_TRY(pvs_vlad_encode_dev(ctx, cb, pca, d_x, desc_kind, d_off, n_images, total, prm, d_out, d_lab, nullptr));
   PVS_HIP(hipMemcpyAsync(out, d_out, out_elems * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (out_labels && total > 0)
@@ -706,11 +705,13 @@ PVS_EXPORT int pvs_fisher_encode(pvs_ctx* ctx, const pvs_gmm* g, const pvs_pca* 
   const size_t out_elems = (size_t)n_images * ((size_t)g->K + 2 * (size_t)g->K * g->D);
   char* d_x = nullptr;
   char* d_small = nullptr;
-  PVS_TRY(ws_reserve(ctx, 0, desc_bytes, reinterpret_cast<void**>(&d_x)));
-  const size_t off_bytes = ((size_t)(n_images + 1) * sizeof(int64_t) + 255) / 256 * 256;
-  PVS_TRY(ws_reserve(ctx, 2, off_bytes + out_elems * 8, reinterpret_cast<void**>(&d_small)));
-  int64_t* d_off = reinterpret_cast<int64_t*>(d_small);
-  double* d_out = reinterpret_cast<double*>(d_small + off_bytes);
+  PVS_TRY(ws_reserve(ctx, WS_STAGE_IN, desc_bytes, &d_x));
+  WsLayout<> lay;
+  const auto off_p = lay.add<int64_t>((size_t)n_images + 1);
+  const auto out_p = lay.add<double>(out_elems);
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, lay.bytes(), &d_small));
+  int64_t* d_off = off_p(d_small);
+  double* d_out = out_p(d_small);
   if (desc_bytes) PVS_HIP(hipMemcpyAsync(d_x, desc, desc_bytes, hipMemcpyHostToDevice, ctx->stream));
   PVS_HIP(hipMemcpyAsync(d_off, offsets, (size_t)(n_images + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   PVS_TRY(pvs_fisher_encode_dev(ctx, g, pca, d_x, desc_kind, d_off, n_images, total, prm, d_out, 1));
@@ -766,25 +767,25 @@ PVS_EXPORT int pvs_cosine(pvs_ctx* ctx, const void* A, int64_t M, const void* B,
   PVS_NEED(out, "out");
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t es = is_f64 ? 8 : 4;
-  const size_t a_bytes = ((size_t)M * L * es + 255) / 256 * 256, b_bytes = ((size_t)N * L * es + 255) / 256 * 256;
-  char* d_in = nullptr;
+  char* d_stage = nullptr;
   char* d_o = nullptr;
   const bool same = (A == B && M == N);
-  PVS_TRY(ws_reserve(ctx, 0, a_bytes + (same ? 0 : b_bytes), reinterpret_cast<void**>(&d_in)));
-  const size_t nrm_bytes = ((size_t)(M + N) * 4 + 255) / 256 * 256;
-  PVS_TRY(ws_reserve(ctx, 2, nrm_bytes + (size_t)M * N * es, reinterpret_cast<void**>(&d_o)));
+  WsLayout<> in, res;
+  const auto a_p = in.add<char>((size_t)M * L * es), b_p = in.add<char>(same ? 0 : (size_t)N * L * es);
+  PVS_TRY(ws_reserve(ctx, WS_STAGE_IN, in.bytes(), &d_stage));
+  char* d_in = a_p(d_stage);
+  char* d_b = same ? d_in : b_p(d_stage);
+  const auto nrm_p = res.add<float>((size_t)(M + N));
+  const auto out_p = res.add<char>((size_t)M * N * es);
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, res.bytes(), &d_o));
   PVS_HIP(hipMemcpyAsync(d_in, A, (size_t)M * L * es, hipMemcpyHostToDevice, ctx->stream));
-  char* d_b = d_in;
-  if (!same) {
-    d_b = d_in + a_bytes;
-    PVS_HIP(hipMemcpyAsync(d_b, B, (size_t)N * L * es, hipMemcpyHostToDevice, ctx->stream));
-  }
-  void* d_out = d_o + nrm_bytes;
+  if (!same) PVS_HIP(hipMemcpyAsync(d_b, B, (size_t)N * L * es, hipMemcpyHostToDevice, ctx->stream));
+  void* d_out = out_p(d_o);
   if (is_f64) {
     PVS_TRY(launch_cosine_f64(ctx, reinterpret_cast<double*>(d_in), M, reinterpret_cast<double*>(d_b), N, L,
                               reinterpret_cast<double*>(d_out)));
   } else {
-    float* inva = reinterpret_cast<float*>(d_o);
+    float* inva = nrm_p(d_o);
     float* invb = inva + M;
     PVS_TRY(launch_row_inv_norms(ctx, reinterpret_cast<float*>(d_in), M, L, inva));
     PVS_TRY(launch_row_inv_norms(ctx, reinterpret_cast<float*>(d_b), N, L, invb));
@@ -841,7 +842,7 @@ static int cosine_topk_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const voi
   // HBM speed instead of 128-row MFMA tiles with 127 idle rows; the same scores bit for bit (filter.hip)
   if (!f16 && N <= ((int64_t)1 << 28) && cosine_dense_rows_eligible(static_cast<const float*>(d_Q), static_cast<const float*>(d_DB), nq, L)) {
     float* row = nullptr;
-    PVS_TRY(ws_reserve(ctx, 2, (size_t)nq * N * sizeof(float), reinterpret_cast<void**>(&row)));
+    PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)nq * N * sizeof(float), &row));
     PVS_TRY(launch_cosine_dense_rows(ctx, static_cast<const float*>(d_Q), nq, static_cast<const float*>(d_DB), N, L, d_inv_q, d_inv_db, row, N));
     return launch_topk(ctx, row, nq, N, N, k, col_offset, merge, d_idx, d_val);
   }
@@ -852,7 +853,7 @@ static int cosine_topk_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const voi
   const char* q = static_cast<const char*>(d_Q);
   const char* db = static_cast<const char*>(d_DB);
   float* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * NC * sizeof(float), reinterpret_cast<void**>(&panel)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
   for (int64_t q0 = 0; q0 < nq; q0 += QT) {
     const int64_t qn = std::min(QT, nq - q0);
     for (int64_t c0 = 0; c0 < N; c0 += NC) {
@@ -942,20 +943,23 @@ PVS_EXPORT int pvs_cosine_topk(pvs_ctx* ctx, const float* Q, int64_t nq, const f
   if (N <= 0) PVS_FAIL(PVS_ERR_INVALID, "empty database");
   PVS_HIP(hipSetDevice(ctx->device));
   const bool same = (Q == DB && nq == N);
-  const size_t q_bytes = ((size_t)nq * L * 4 + 255) / 256 * 256, db_bytes = ((size_t)N * L * 4 + 255) / 256 * 256;
   char* d_in = nullptr;
   char* d_s = nullptr;
-  PVS_TRY(ws_reserve(ctx, 0, q_bytes + (same ? 0 : db_bytes), reinterpret_cast<void**>(&d_in)));
-  const size_t nrm = ((size_t)(nq + N) * 4 + 255) / 256 * 256, idxb = ((size_t)nq * k * 8 + 255) / 256 * 256;
-  PVS_TRY(ws_reserve(ctx, 1, nrm + idxb + (size_t)nq * k * 4, reinterpret_cast<void**>(&d_s)));
-  float* dq = reinterpret_cast<float*>(d_in);
-  float* ddb = same ? dq : reinterpret_cast<float*>(d_in + q_bytes);
+  WsLayout<> in, res;
+  const auto q_p = in.add<float>((size_t)nq * L), db_p = in.add<float>(same ? 0 : (size_t)N * L);
+  PVS_TRY(ws_reserve(ctx, WS_STAGE_IN, in.bytes(), &d_in));
+  const auto nrm_p = res.add<float>((size_t)(nq + N));
+  const auto idx_p = res.add<int64_t>((size_t)nq * k);
+  const auto val_p = res.add<float>((size_t)nq * k);
+  PVS_TRY(ws_reserve(ctx, WS_SCRATCH, res.bytes(), &d_s));
+  float* dq = q_p(d_in);
+  float* ddb = same ? dq : db_p(d_in);
   PVS_HIP(hipMemcpyAsync(dq, Q, (size_t)nq * L * 4, hipMemcpyHostToDevice, ctx->stream));
   if (!same) PVS_HIP(hipMemcpyAsync(ddb, DB, (size_t)N * L * 4, hipMemcpyHostToDevice, ctx->stream));
-  float* invq = reinterpret_cast<float*>(d_s);
+  float* invq = nrm_p(d_s);
   float* invd = invq + nq;
-  int64_t* d_idx = reinterpret_cast<int64_t*>(d_s + nrm);
-  float* d_val = reinterpret_cast<float*>(d_s + nrm + idxb);
+  int64_t* d_idx = idx_p(d_s);
+  float* d_val = val_p(d_s);
   PVS_TRY(launch_row_inv_norms(ctx, dq, nq, L, invq));
   PVS_TRY(launch_row_inv_norms(ctx, ddb, N, L, invd));
   // many queries: the filtered path returns the same lists (bit-identical) faster; it declines what does not qualify
@@ -1005,7 +1009,7 @@ PVS_EXPORT int pvs_cosine_topk_f64_dev(pvs_ctx* ctx, const double* d_Q, int64_t 
   PVS_HIP(hipSetDevice(ctx->device));
   const int64_t QT = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / N));
   double* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * N * sizeof(double), reinterpret_cast<void**>(&panel)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * N * sizeof(double), &panel));
   for (int64_t q0 = 0; q0 < nq; q0 += QT) {
     const int64_t qn = std::min(QT, nq - q0);
     // the whole problem in one panel and Q == DB: the symmetric kernel (launch_cosine_f64_dev detects it)
@@ -1032,18 +1036,21 @@ PVS_EXPORT int pvs_cosine_topk_f64(pvs_ctx* ctx, const double* Q, int64_t nq, co
   // query block: as many rows as one score panel of pvs_cosine_topk_f64_dev holds, at most 2 GiB of rows
   const int64_t QB = same ? nq : std::max<int64_t>(1, std::min<int64_t>(nq, std::min<int64_t>(((int64_t)128 << 20) / N,
                                                                                              ((int64_t)256 << 20) / L)));
-  const size_t db_bytes = ((size_t)N * L * 8 + 255) / 256 * 256, q_bytes = same ? 0 : ((size_t)QB * L * 8 + 255) / 256 * 256;
   char* d_in = nullptr;
   char* d_s = nullptr;
-  PVS_TRY(ws_reserve(ctx, 0, db_bytes + q_bytes, reinterpret_cast<void**>(&d_in)));
-  const size_t nrm_b = ((size_t)(N + QB) * 8 + 255) / 256 * 256, idx_b = ((size_t)QB * k * 8 + 255) / 256 * 256;
-  PVS_TRY(ws_reserve(ctx, 6, nrm_b + 2 * idx_b, reinterpret_cast<void**>(&d_s)));
-  double* d_db = reinterpret_cast<double*>(d_in);
-  double* d_q = same ? d_db : reinterpret_cast<double*>(d_in + db_bytes);
-  double* inv_db = reinterpret_cast<double*>(d_s);
+  WsLayout<> in, res;
+  const auto db_p = in.add<double>((size_t)N * L), q_p = in.add<double>(same ? 0 : (size_t)QB * L);
+  PVS_TRY(ws_reserve(ctx, WS_STAGE_IN, in.bytes(), &d_in));
+  const auto nrm_p = res.add<double>((size_t)(N + QB));
+  const auto idx_p = res.add<int64_t>((size_t)QB * k);
+  const auto val_p = res.add<double>((size_t)QB * k);
+  PVS_TRY(ws_reserve(ctx, WS_LISTS, res.bytes(), &d_s));
+  double* d_db = db_p(d_in);
+  double* d_q = same ? d_db : q_p(d_in);
+  double* inv_db = nrm_p(d_s);
   double* inv_q = same ? inv_db : inv_db + N;
-  int64_t* d_idx = reinterpret_cast<int64_t*>(d_s + nrm_b);
-  double* d_val = reinterpret_cast<double*>(d_s + nrm_b + idx_b);
+  int64_t* d_idx = idx_p(d_s);
+  double* d_val = val_p(d_s);
   PVS_HIP(hipMemcpyAsync(d_db, DB, (size_t)N * L * 8, hipMemcpyHostToDevice, ctx->stream));
   PVS_TRY(launch_row_inv_norms_f64(ctx, d_db, N, L, inv_db));
   for (int64_t q0 = 0; q0 < nq; q0 += QB) {
@@ -1108,7 +1115,7 @@ PVS_EXPORT int pvs_kmeans_step_dev(pvs_ctx* ctx, const pvs_codebook* cb, const f
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t n = (size_t)cb->K * cb->D + cb->K + 2;
   double* d_stats = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, n * sizeof(double), reinterpret_cast<void**>(&d_stats)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, n * sizeof(double), &d_stats));
   PVS_TRY(launch_kmeans_step(ctx, cb, d_x, total_desc, d_labels, d_prev_labels, d_stats, d_sqdist));
   return stats_to_host(ctx, d_stats, n, h_stats);
 }
@@ -1122,7 +1129,7 @@ PVS_EXPORT int pvs_gmm_em_step_dev(pvs_ctx* ctx, const pvs_gmm* gmm, const float
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t n = (size_t)gmm->K + (size_t)2 * gmm->K * gmm->D + 1;
   double* d_stats = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, n * sizeof(double), reinterpret_cast<void**>(&d_stats)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, n * sizeof(double), &d_stats));
   PVS_TRY(launch_gmm_em_step(ctx, gmm, d_x, gmm->D, total_desc, d_stats));
   return stats_to_host(ctx, d_stats, n, h_stats);
 }
@@ -1137,7 +1144,7 @@ PVS_EXPORT int pvs_label_sums_dev(pvs_ctx* ctx, const float* d_x, int D, int64_t
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t n = (size_t)K * D;
   double* d_out = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, n * sizeof(double), reinterpret_cast<void**>(&d_out)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, n * sizeof(double), &d_out));
   PVS_TRY(launch_label_sums(ctx, d_x, total_desc, D, d_labels, K, square, d_out));
   return stats_to_host(ctx, d_out, n, h_out);
 }
@@ -1150,7 +1157,7 @@ PVS_EXPORT int pvs_gram_dev(pvs_ctx* ctx, const float* d_x, int D, int64_t total
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t n = (size_t)D + (size_t)D * D;
   double* d_out = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, n * sizeof(double), reinterpret_cast<void**>(&d_out)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, n * sizeof(double), &d_out));
   PVS_TRY(launch_gram(ctx, d_x, total_desc, D, d_out));
   return stats_to_host(ctx, d_out, n, h_out);
 }
@@ -1166,10 +1173,12 @@ PVS_EXPORT int pvs_seed_distances_dev(pvs_ctx* ctx, const float* d_x, int D, int
   if (n_cand < 1 || n_cand > 8 || D <= 0) PVS_FAIL(PVS_ERR_INVALID, "1..8 candidates of positive dimension");
   PVS_HIP(hipSetDevice(ctx->device));
   char* ws = nullptr;
-  const size_t cand_b = ((size_t)n_cand * D * 4 + 255) / 256 * 256;
-  PVS_TRY(ws_reserve(ctx, 2, cand_b + 8 * sizeof(double), reinterpret_cast<void**>(&ws)));
-  float* d_cand = reinterpret_cast<float*>(ws);
-  double* d_pot = reinterpret_cast<double*>(ws + cand_b);
+  WsLayout<> lay;
+  const auto cand_p = lay.add<float>((size_t)n_cand * D);
+  const auto pot_p = lay.add<double>(8);
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, lay.bytes(), &ws));
+  float* d_cand = cand_p(ws);
+  double* d_pot = pot_p(ws);
   if (!cand_on_device) PVS_HIP(hipMemcpyAsync(d_cand, h_cand, (size_t)n_cand * D * 4, hipMemcpyHostToDevice, ctx->stream));
   PVS_TRY(launch_seed_distances(ctx, d_x, total_desc, D, cand_on_device ? cand : d_cand, n_cand, d_mind, d_dist, d_pot));
   double pot8[8];
@@ -1194,16 +1203,16 @@ PVS_EXPORT int pvs_seed_pick_dev(pvs_ctx* ctx, const float* d_x, int D, int64_t 
     if (h_blocks[c] < 0 || h_blocks[c] >= nblk) PVS_FAIL(PVS_ERR_INVALID, "candidate block out of range");
   PVS_HIP(hipSetDevice(ctx->device));
   char* ws = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)n_cand * 32, reinterpret_cast<void**>(&ws)));
-  int64_t* d_blk = reinterpret_cast<int64_t*>(ws);
-  double* d_base = reinterpret_cast<double*>(ws + (size_t)n_cand * 8);
-  double* d_tgt = reinterpret_cast<double*>(ws + (size_t)n_cand * 16);
-  int64_t* d_idx = reinterpret_cast<int64_t*>(ws + (size_t)n_cand * 24);
-  PVS_HIP(hipMemcpyAsync(d_blk, h_blocks, (size_t)n_cand * 8, hipMemcpyHostToDevice, ctx->stream));
-  PVS_HIP(hipMemcpyAsync(d_base, h_base, (size_t)n_cand * 8, hipMemcpyHostToDevice, ctx->stream));
-  PVS_HIP(hipMemcpyAsync(d_tgt, h_target, (size_t)n_cand * 8, hipMemcpyHostToDevice, ctx->stream));
-  PVS_TRY(launch_seed_pick(ctx, d_x, total_desc, D, d_mind, d_blk, d_base, d_tgt, n_cand, d_idx, d_cand));
-  PVS_HIP(hipMemcpyAsync(h_idx, d_idx, (size_t)n_cand * 8, hipMemcpyDeviceToHost, ctx->stream));
+  WsLayout<8> lay;   // four packed tables of n_cand
+  const auto blk_p = lay.add<int64_t>((size_t)n_cand);
+  const auto base_p = lay.add<double>((size_t)n_cand), tgt_p = lay.add<double>((size_t)n_cand);
+  const auto idx_p = lay.add<int64_t>((size_t)n_cand);
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, lay.bytes(), &ws));
+  PVS_HIP(hipMemcpyAsync(blk_p(ws), h_blocks, (size_t)n_cand * 8, hipMemcpyHostToDevice, ctx->stream));
+  PVS_HIP(hipMemcpyAsync(base_p(ws), h_base, (size_t)n_cand * 8, hipMemcpyHostToDevice, ctx->stream));
+  PVS_HIP(hipMemcpyAsync(tgt_p(ws), h_target, (size_t)n_cand * 8, hipMemcpyHostToDevice, ctx->stream));
+  PVS_TRY(launch_seed_pick(ctx, d_x, total_desc, D, d_mind, blk_p(ws), base_p(ws), tgt_p(ws), n_cand, idx_p(ws), d_cand));
+  PVS_HIP(hipMemcpyAsync(h_idx, idx_p(ws), (size_t)n_cand * 8, hipMemcpyDeviceToHost, ctx->stream));
   PVS_HIP(hipStreamSynchronize(ctx->stream));
   return PVS_OK;
 }
@@ -1216,7 +1225,7 @@ PVS_EXPORT int pvs_min_update_dev(pvs_ctx* ctx, float* d_mind, const float* d_di
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t nblk = (size_t)((total_desc + 4095) / 4096);
   double* d_bs = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, nblk * sizeof(double), reinterpret_cast<void**>(&d_bs)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, nblk * sizeof(double), &d_bs));
   PVS_TRY(launch_min_update(ctx, d_mind, d_dist, total_desc, d_bs));
   return stats_to_host(ctx, d_bs, nblk, h_block_sums);
 }
@@ -1232,23 +1241,18 @@ PVS_EXPORT int pvs_kmeanspp_run_dev(pvs_ctx* ctx, const float* d_x, int D, int64
   if (h_indices[0] < 0 || h_indices[0] >= total_desc) PVS_FAIL(PVS_ERR_INVALID, "first centre out of range");
   PVS_HIP(hipSetDevice(ctx->device));
   const size_t nblk = (size_t)((total_desc + 4095) / 4096);
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t mind_b = al((size_t)total_desc * 4), dist_b = al((size_t)trials * total_desc * 4), cand_b = al((size_t)trials * D * 4),
-               bs_b = al(nblk * 8), uni_b = al((size_t)std::max(n_clusters - 1, 1) * trials * 8), idx_b = al((size_t)n_clusters * 8), small_b = 512;
+  const KmeansppLayout lay = kmeanspp_layout(total_desc, nblk, D, n_clusters, trials);
   char* ws = nullptr;
-  PVS_TRY(ws_reserve(ctx, 3, mind_b + dist_b + cand_b + bs_b + uni_b + idx_b + small_b, reinterpret_cast<void**>(&ws)));
-  float* d_mind = reinterpret_cast<float*>(ws);
-  float* d_dist = reinterpret_cast<float*>(ws + mind_b);
-  float* d_cand = reinterpret_cast<float*>(ws + mind_b + dist_b);
-  double* d_bs = reinterpret_cast<double*>(ws + mind_b + dist_b + cand_b);
-  double* d_uni = reinterpret_cast<double*>(ws + mind_b + dist_b + cand_b + bs_b);
-  int64_t* d_indices = reinterpret_cast<int64_t*>(ws + mind_b + dist_b + cand_b + bs_b + uni_b);
-  char* d_small = ws + mind_b + dist_b + cand_b + bs_b + uni_b + idx_b;
+  PVS_TRY(ws_reserve(ctx, WS_PROJECTED, lay.bytes, &ws));
+  float* d_mind = lay.mind(ws);
+  double* d_uni = lay.uniform(ws);
+  int64_t* d_indices = lay.indices(ws);
   PVS_HIP(hipMemsetAsync(d_mind, 0x7f, (size_t)total_desc * 4, ctx->stream));     // 3.39e38: "no centre yet"
   if (n_clusters > 1)
     PVS_HIP(hipMemcpyAsync(d_uni, h_uniform, (size_t)(n_clusters - 1) * trials * 8, hipMemcpyHostToDevice, ctx->stream));
   PVS_HIP(hipMemcpyAsync(d_indices, h_indices, 8, hipMemcpyHostToDevice, ctx->stream));
-  PVS_TRY(launch_kmeanspp_run(ctx, d_x, total_desc, D, n_clusters, trials, d_uni, d_mind, d_dist, d_cand, d_bs, d_small, d_indices));
+  PVS_TRY(launch_kmeanspp_run(ctx, d_x, total_desc, D, n_clusters, trials, d_uni, d_mind, lay.dist(ws), lay.cand(ws), lay.block_sums(ws), lay.small(ws),
+                              d_indices));
   PVS_HIP(hipMemcpyAsync(h_indices, d_indices, (size_t)n_clusters * 8, hipMemcpyDeviceToHost, ctx->stream));
   PVS_HIP(hipStreamSynchronize(ctx->stream));
   return PVS_OK;

@@ -12,6 +12,7 @@
 
 #include "../../include/pvsim.h"
 #include "../../include/pvsim_diag.h"
+#include "workspace.hpp"
 
 #define PVS_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -57,14 +58,7 @@ struct pvs_ctx {
   hipStream_t stream = nullptr;
   bool owns_stream = false;
   int num_cu = 256;
-  // grow-only scratch areas (device)
-  // 0 host-API input staging, 1 scratch (labels, tables, responsibilities), 2 host-API outputs / score panel,
-  // 3 PCA projections, 4 materialised RootSIFT rows
-  // 5 fp16 row copies (filtered top-k), 6 filtered top-k lists / candidates
-  // 7 row norms of the neighbour search, 8 float64 row copies of the neighbour search (neighbors.hip)
-  // 9 per-image table of the dense SIFT extractor (dsift.hip)
-  // 10 Gaussian pyramids of one chunk, 11 image table / block counts, 12 candidates and keypoints of the keypoint SIFT extractor (sift.hip)
-  // 13 tile / pair table, 14 float64 match points, 15 hypothesis counts and the trial mask of the spatial verification (match.hip)
+  // grow-only scratch areas (device), one per pvs::WsSlot: who reserves which, and when a pointer into one dies, is the table in workspace.hpp
   static constexpr int NWS = 16;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
@@ -141,8 +135,6 @@ struct pvs_pca {
 };
 
 namespace pvs {
-
-int ws_reserve(pvs_ctx* ctx, int which, size_t bytes, void** out);
 
 // raise a kernel's dynamic-LDS limit once per context (and again when a launch needs more)
 inline int ensure_lds(pvs_ctx* ctx, const void* fn, size_t bytes) {

@@ -170,7 +170,7 @@ static int launch_gemm_mfma(pvs_ctx* ctx, GemmArgs g, const GemmPlan& plan) {
       hipLaunchKernelGGL(kfull, dim3((unsigned)plan.n_tail), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
     } else {
       float* part = nullptr;
-      PVS_TRY(ws_reserve(ctx, 4, bytes, reinterpret_cast<void**>(&part)));
+      PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, bytes, &part));
       g.tile_base = plan.n_main;
       g.splitk = std::min(plan.splitk, nparts);
       g.nparts = nparts;
@@ -401,7 +401,7 @@ static int launch_gemm_f64(pvs_ctx* ctx, GemmArgsF64 g, const GemmPlan& plan) {
       hipLaunchKernelGGL(kfull, dim3((unsigned)plan.n_tail), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
     } else {
       double* part = nullptr;
-      PVS_TRY(ws_reserve(ctx, 4, bytes, reinterpret_cast<void**>(&part)));
+      PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, bytes, &part));
       g.splitk = sk;
       g.nparts = sk;
       g.partial = part;
@@ -441,12 +441,12 @@ int launch_cosine_f64_dev(pvs_ctx* ctx, const double* A, int64_t M, const double
   return symm ? launch_gemm_f64<true>(ctx, g, *plan) : launch_gemm_f64<false>(ctx, g, *plan);
 }
 
-// host-API form: norms of both operands (workspace slot 1), then the GEMM; out is M x N, ld = N
+// host-API form: norms of both operands (WS_SCRATCH), then the GEMM; out is M x N, ld = N
 int launch_cosine_f64(pvs_ctx* ctx, const double* A, int64_t M, const double* B, int64_t N, int64_t L, double* out) {
   if (M <= 0 || N <= 0) return PVS_OK;
   double* inv = nullptr;
   const bool same = (A == B && M == N);
-  PVS_TRY(ws_reserve(ctx, 1, (size_t)(M + N) * sizeof(double), reinterpret_cast<void**>(&inv)));
+  PVS_TRY(ws_reserve(ctx, WS_SCRATCH, (size_t)(M + N) * sizeof(double), &inv));
   PVS_TRY(launch_row_inv_norms_f64(ctx, A, M, L, inv));
   if (!same) PVS_TRY(launch_row_inv_norms_f64(ctx, B, N, L, inv + M));
   return launch_cosine_f64_dev(ctx, A, M, B, N, L, inv, same ? inv : inv + M, out, N);

@@ -321,7 +321,7 @@ PVS_EXPORT int pvs_dsift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind,
   if (rows > out_rows) PVS_FAIL(PVS_ERR_INVALID, "dense SIFT: %lld rows do not fit the output of %lld rows", (long long)rows, (long long)out_rows);
   if (rows > 0 && (!d_pixels || !d_out)) PVS_FAIL(PVS_ERR_INVALID, "pvs_dsift_dev: null pixels or output");
   DsiftImage* d_meta = nullptr;
-  PVS_TRY(ws_reserve(ctx, 9, meta_bytes, reinterpret_cast<void**>(&d_meta)));
+  PVS_TRY(ws_reserve(ctx, WS_DSIFT_TABLE, meta_bytes, &d_meta));
   PVS_HIP(hipMemcpyAsync(d_meta, h_meta, meta_bytes, hipMemcpyHostToDevice, ctx->stream));
   PVS_HIP(hipMemcpyAsync(d_row_offsets, h_off, off_bytes, hipMemcpyHostToDevice, ctx->stream));
   PVS_HIP(hipEventRecord(ctx->dsift_ev[slot], ctx->stream));

@@ -282,30 +282,28 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
   const float margin = (float)(2.0 * eps);
 
   // ---- workspace
-  const size_t q16_b = ((size_t)nq * L * 2 + 255) / 256 * 256, db16_b = same ? 0 : ((size_t)N * L * 2 + 255) / 256 * 256;
+  WsLayout<> l16;
+  const auto q16_p = l16.add<_Float16>((size_t)nq * L), db16_p = l16.add<_Float16>(same ? 0 : (size_t)N * L);
   char* w5 = nullptr;
-  if (ws_reserve(ctx, 5, q16_b + db16_b, reinterpret_cast<void**>(&w5)) != PVS_OK) {
+  if (ws_reserve(ctx, WS_FP16_ROWS, l16.bytes(), &w5) != PVS_OK) {
     (void)hipGetLastError();   // no room for the fp16 copies: the plain exact path needs none
-    PVS_FAIL(PVS_ERR_UNSUPPORTED, "filtered top-k: no device memory for the fp16 copies (%zu bytes)", q16_b + db16_b);
+    PVS_FAIL(PVS_ERR_UNSUPPORTED, "filtered top-k: no device memory for the fp16 copies (%zu bytes)", l16.bytes());
   }
-  _Float16* q16 = reinterpret_cast<_Float16*>(w5);
-  _Float16* db16 = same ? q16 : reinterpret_cast<_Float16*>(w5 + q16_b);
-  auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-  const size_t o_invq = 0, o_invd = o_invq + al((size_t)nq * 4), o_stats = o_invd + al((size_t)N * 4),
-               o_aidx = o_stats + 256, o_aval = o_aidx + al((size_t)QT * k * 8), o_cidx = o_aval + al((size_t)QT * k * 4),
-               o_cval = o_cidx + al((size_t)QT * cap * 8), o_cnt = o_cval + al((size_t)QT * cap * 4), o_end = o_cnt + al((size_t)QT * 4);
+  _Float16* q16 = q16_p(w5);
+  _Float16* db16 = same ? q16 : db16_p(w5);
+  const FilterListsLayout lay = filter_lists_layout(nq, N, QT, k, cap);
   char* w6 = nullptr;
-  PVS_TRY(ws_reserve(ctx, 6, o_end, reinterpret_cast<void**>(&w6)));
-  float* invq16 = reinterpret_cast<float*>(w6 + o_invq);
-  float* invd16 = same ? invq16 : reinterpret_cast<float*>(w6 + o_invd);
-  unsigned long long* stats = reinterpret_cast<unsigned long long*>(w6 + o_stats);
-  int64_t* aidx = reinterpret_cast<int64_t*>(w6 + o_aidx);
-  float* aval = reinterpret_cast<float*>(w6 + o_aval);
-  int64_t* cidx = reinterpret_cast<int64_t*>(w6 + o_cidx);
-  float* cval = reinterpret_cast<float*>(w6 + o_cval);
-  int* cnt = reinterpret_cast<int*>(w6 + o_cnt);
+  PVS_TRY(ws_reserve(ctx, WS_LISTS, lay.bytes, &w6));
+  float* invq16 = lay.invq(w6);
+  float* invd16 = same ? invq16 : lay.invdb(w6);
+  unsigned long long* stats = lay.stats(w6);
+  int64_t* aidx = lay.aidx(w6);
+  float* aval = lay.aval(w6);
+  int64_t* cidx = lay.cidx(w6);
+  float* cval = lay.cval(w6);
+  int* cnt = lay.cnt(w6);
   float* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * NC * sizeof(float), reinterpret_cast<void**>(&panel)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
   PVS_HIP(hipMemsetAsync(stats, 0, 32, ctx->stream));
 
   // ---- 1. scaled fp16 rows
@@ -324,7 +322,8 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
   std::vector<int> h_cnt;
   for (int64_t q0 = 0; q0 < nq; q0 += QT) {
     const int64_t qn = std::min(QT, nq - q0);
-    PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * NC * sizeof(float), reinterpret_cast<void**>(&panel)));   // (the exact fallback shares the slot)
+    // step 7 of the previous block may have called cosine_topk_exact, which reserves WS_PANEL_OUT for a panel of its own size
+    PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
     PVS_HIP(hipMemsetAsync(cidx, 0xff, (size_t)qn * cap * 8, ctx->stream));
     for (int64_t c0 = 0; c0 < N; c0 += NC) {
       const int64_t cn = std::min(NC, N - c0);
@@ -361,14 +360,18 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
         if (h_cnt[(size_t)i] > cap) rows.push_back(i);
       const int64_t nr = (int64_t)rows.size();
       const int64_t rb = std::max<int64_t>(1, std::min<int64_t>(nr, ((int64_t)1 << 28) / N));   // rows per exact batch (score rows <= 1 GiB)
-      char* w4 = nullptr;
-      const size_t rows_b = al((size_t)nr * 8), g_b = al((size_t)rb * L * 4), gi_b = al((size_t)rb * 4), li_b = al((size_t)rb * k * 8);
-      PVS_TRY(ws_reserve(ctx, 3, rows_b + g_b + gi_b + li_b + al((size_t)rb * k * 4), reinterpret_cast<void**>(&w4)));
-      int64_t* d_rows = reinterpret_cast<int64_t*>(w4);
-      float* gq = reinterpret_cast<float*>(w4 + rows_b);
-      float* gi = reinterpret_cast<float*>(w4 + rows_b + g_b);
-      int64_t* li = reinterpret_cast<int64_t*>(w4 + rows_b + g_b + gi_b);
-      float* lv = reinterpret_cast<float*>(w4 + rows_b + g_b + gi_b + li_b);
+      char* w3 = nullptr;
+      WsLayout<> ovf;
+      const auto rows_p = ovf.add<int64_t>((size_t)nr);
+      const auto gq_p = ovf.add<float>((size_t)rb * L), gi_p = ovf.add<float>((size_t)rb);
+      const auto li_p = ovf.add<int64_t>((size_t)rb * k);
+      const auto lv_p = ovf.add<float>((size_t)rb * k);
+      PVS_TRY(ws_reserve(ctx, WS_PROJECTED, ovf.bytes(), &w3));
+      int64_t* d_rows = rows_p(w3);
+      float* gq = gq_p(w3);
+      float* gi = gi_p(w3);
+      int64_t* li = li_p(w3);
+      float* lv = lv_p(w3);
       PVS_HIP(hipMemcpyAsync(d_rows, rows.data(), (size_t)nr * 8, hipMemcpyHostToDevice, ctx->stream));
       for (int64_t r0 = 0; r0 < nr; r0 += rb) {
         const int64_t rn = std::min(rb, nr - r0);

@@ -40,10 +40,9 @@ __global__ __launch_bounds__(256) void materialise_kernel(const void* __restrict
 }
 
 static int materialise_f32(pvs_ctx* ctx, const void*& d_desc, int& kind, int64_t total, int D) {
-  constexpr int ws_slot = 4;  // never aliases the host-API staging slot 0
   if (kind == PVS_DESC_F32 || total <= 0) return PVS_OK;
   float* buf = nullptr;
-  PVS_TRY(ws_reserve(ctx, ws_slot, (size_t)total * D * sizeof(float), reinterpret_cast<void**>(&buf)));
+  PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, (size_t)total * D * sizeof(float), &buf));   // never the host entry points' WS_STAGE_IN
   const dim3 grid((unsigned)((total + 3) / 4));
   if (kind == PVS_DESC_U8_ROOTSIFT)
     hipLaunchKernelGGL(materialise_kernel<PVS_DESC_U8_ROOTSIFT>, grid, dim3(256), 0, ctx->stream, d_desc, total, D, buf);
@@ -920,7 +919,7 @@ int launch_gmm_posterior(pvs_ctx* ctx, const pvs_gmm* g, const void* d_desc, int
   int k = kind;
   PVS_TRY(materialise_f32(ctx, x, k, total, g->D));
   double* tab = nullptr;
-  PVS_TRY(ws_reserve(ctx, 1, (size_t)2 * g->K * g->D * sizeof(double), reinterpret_cast<void**>(&tab)));
+  PVS_TRY(ws_reserve(ctx, WS_SCRATCH, (size_t)2 * g->K * g->D * sizeof(double), &tab));
   if (g->K <= PM_COLS) return posterior_mfma_on(ctx, g, static_cast<const float*>(x), ld, total, d_resp, tab);
   return posterior_on(ctx, g, static_cast<const float*>(x), ld, total, d_resp, tab);
 }
@@ -928,16 +927,13 @@ int launch_gmm_posterior(pvs_ctx* ctx, const pvs_gmm* g, const void* d_desc, int
 // one batch of images (offsets are absolute descriptor rows; the batch's descriptors are rows [t0, t0 + tn))
 static int fisher_batch(pvs_ctx* ctx, const pvs_gmm* g, const float* x, int ld, const int64_t* d_offsets, int64_t img0,
                         int64_t n_img, int64_t t0, int64_t tn, const pvs_norm_params& prm, void* d_out, int out_f64,
-                        char* ws, size_t tab_b, size_t resp_b) {
+                        double* tab, double* resp, double* partial) {
   const int K = g->K, D = g->D;
   const bool mfma = K <= PM_COLS;
   const int bt = D <= 128 ? 128 : 256;
   const int dblocks = mfma ? (D + MM_DIMS - 1) / MM_DIMS : (D + bt - 1) / bt;
   const int kblocks = mfma ? 1 : (K + MOM_KB - 1) / MOM_KB;
   const int bpi = dblocks * kblocks;
-  double* tab = reinterpret_cast<double*>(ws);
-  double* resp = reinterpret_cast<double*>(ws + tab_b);
-  double* partial = reinterpret_cast<double*>(ws + tab_b + resp_b);
   const int64_t L = (int64_t)K + 2 * (int64_t)K * D;
   double* resp_abs = resp - t0 * K;  // kernels index responsibilities by ABSOLUTE descriptor row
   if (tn > 0) {
@@ -1008,27 +1004,26 @@ int launch_gmm_em_step(pvs_ctx* ctx, const pvs_gmm* g, const float* x, int ld, i
   constexpr int CHUNK = 2048;
   const int nslab = (K + PM_COLS - 1) / PM_COLS;   // the moments kernel takes 256 components at a time
   const int64_t len = (int64_t)K * 2 * D;
-  const size_t tab_b = ((size_t)2 * K * D * 8 + 255) / 256 * 256;
   const int64_t rows_per_batch = std::max<int64_t>(CHUNK, (((int64_t)2 << 30) / ((int64_t)K * 8)) / CHUNK * CHUNK);
   const int dblocks = (D + MM_DIMS - 1) / MM_DIMS;
   int first = 1;
   for (int64_t t0 = 0; t0 < total; t0 += rows_per_batch) {
     const int64_t tn = std::min(rows_per_batch, total - t0);
     const int64_t nch = (tn + CHUNK - 1) / CHUNK;
-    const size_t resp_b = ((size_t)tn * K * 8 + 255) / 256 * 256;
-    const size_t lse_b = ((size_t)tn * 8 + 255) / 256 * 256;
-    const size_t off_b = ((size_t)(nch + 1) * 8 + 255) / 256 * 256;
     const int64_t slab_len = (int64_t)PM_COLS * 2 * D;
-    const size_t raw_b = ((size_t)nch * slab_len * 8 + 255) / 256 * 256;
-    const size_t s0_b = ((size_t)nch * PM_COLS * 8 + 255) / 256 * 256;
+    WsLayout<> lay;
+    const auto tab_p = lay.add<double>((size_t)2 * K * D);
+    const auto resp_p = lay.add<double>((size_t)tn * K), lse_p = lay.add<double>((size_t)tn);
+    const auto off_p = lay.add<int64_t>((size_t)nch + 1);
+    const auto raw_p = lay.add<double>((size_t)nch * slab_len), raw0_p = lay.add<double>((size_t)nch * PM_COLS);
     char* ws = nullptr;
-    PVS_TRY(ws_reserve(ctx, 1, tab_b + resp_b + lse_b + off_b + raw_b + s0_b, reinterpret_cast<void**>(&ws)));
-    double* tab = reinterpret_cast<double*>(ws);
-    double* resp = reinterpret_cast<double*>(ws + tab_b);
-    double* lse = reinterpret_cast<double*>(ws + tab_b + resp_b);
-    int64_t* off = reinterpret_cast<int64_t*>(ws + tab_b + resp_b + lse_b);
-    double* raw = reinterpret_cast<double*>(ws + tab_b + resp_b + lse_b + off_b);
-    double* raw0 = reinterpret_cast<double*>(ws + tab_b + resp_b + lse_b + off_b + raw_b);
+    PVS_TRY(ws_reserve(ctx, WS_SCRATCH, lay.bytes(), &ws));
+    double* tab = tab_p(ws);
+    double* resp = resp_p(ws);
+    double* lse = lse_p(ws);
+    int64_t* off = off_p(ws);
+    double* raw = raw_p(ws);
+    double* raw0 = raw0_p(ws);
     if (K <= PM_COLS) PVS_TRY(posterior_mfma_on(ctx, g, x + t0 * ld, ld, tn, resp, tab, lse));
     else PVS_TRY(posterior_on(ctx, g, x + t0 * ld, ld, tn, resp, tab, lse));
     hipLaunchKernelGGL(chunk_offsets_kernel, dim3((unsigned)((nch + 256) / 256)), dim3(256), 0, ctx->stream, off, t0, tn, CHUNK, nch);
@@ -1087,13 +1082,14 @@ int launch_fisher(pvs_ctx* ctx, const pvs_gmm* g, const void* d_desc, int kind, 
       ++i1;
     }
     const int64_t n_img = i1 - i0, t0 = off[i0], tn = off[i1] - off[i0];
-    const size_t tab_b = ((size_t)2 * K * D * 8 + 255) / 256 * 256;
-    const size_t resp_b = ((size_t)std::max<int64_t>(tn, 1) * K * 8 + 255) / 256 * 256;
     const int dbl = K <= PM_COLS ? (D + MM_DIMS - 1) / MM_DIMS : bpi;
-    const size_t part_b = (size_t)n_img * std::max(dbl, bpi) * 8;
+    WsLayout<> lay;
+    const auto tab_p = lay.add<double>((size_t)2 * K * D);
+    const auto resp_p = lay.add<double>((size_t)std::max<int64_t>(tn, 1) * K);
+    const auto part_p = lay.add<double>((size_t)n_img * std::max(dbl, bpi));
     char* ws = nullptr;
-    PVS_TRY(ws_reserve(ctx, 1, tab_b + resp_b + part_b, reinterpret_cast<void**>(&ws)));
-    PVS_TRY(fisher_batch(ctx, g, x, ld, d_offsets, i0, n_img, t0, tn, prm, d_out, out_f64, ws, tab_b, resp_b));
+    PVS_TRY(ws_reserve(ctx, WS_SCRATCH, lay.bytes(), &ws));
+    PVS_TRY(fisher_batch(ctx, g, x, ld, d_offsets, i0, n_img, t0, tn, prm, d_out, out_f64, tab_p(ws), resp_p(ws), part_p(ws)));
     i0 = i1;
   }
   return PVS_OK;

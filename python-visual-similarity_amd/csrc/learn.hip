@@ -135,11 +135,13 @@ int launch_kmeans_step(pvs_ctx* ctx, const pvs_codebook* cb, const float* x, int
   for (int64_t t0 = 0; D <= AGG_D_MAX && t0 < total; t0 += rows_per_batch) {
     const int64_t tn = std::min(rows_per_batch, total - t0);
     const int64_t nch = (tn + LEARN_CHUNK - 1) / LEARN_CHUNK;
-    const size_t off_b = ((size_t)(nch + 1) * 8 + 255) / 256 * 256;
+    WsLayout<> lay;
+    const auto off_p = lay.add<int64_t>((size_t)nch + 1);
+    const auto part_p = lay.add<float>((size_t)nch * len);
     char* ws = nullptr;
-    PVS_TRY(ws_reserve(ctx, 1, off_b + (size_t)nch * len * 4, reinterpret_cast<void**>(&ws)));
-    int64_t* off = reinterpret_cast<int64_t*>(ws);
-    float* part = reinterpret_cast<float*>(ws + off_b);
+    PVS_TRY(ws_reserve(ctx, WS_SCRATCH, lay.bytes(), &ws));
+    int64_t* off = off_p(ws);
+    float* part = part_p(ws);
     PVS_TRY(launch_assign(ctx, cb, x + t0 * D, PVS_DESC_F32, tn, D, d_labels + t0));
     hipLaunchKernelGGL(chunk_offsets_kernel, dim3((unsigned)((nch + 256) / 256)), dim3(256), 0, ctx->stream, off, t0, tn,
                        LEARN_CHUNK, nch);
@@ -151,11 +153,13 @@ int launch_kmeans_step(pvs_ctx* ctx, const pvs_codebook* cb, const float* x, int
   }
   // counts, changed labels, inertia
   const int64_t nblk = (total + 63) / 64;
-  const size_t cnt_b = ((size_t)(K + 1) * 8 + 255) / 256 * 256;
+  WsLayout<> lay;
+  const auto cnt_p = lay.add<unsigned long long>((size_t)K + 1);
+  const auto bs_p = lay.add<double>((size_t)nblk);
   char* ws = nullptr;
-  PVS_TRY(ws_reserve(ctx, 1, cnt_b + (size_t)nblk * 8, reinterpret_cast<void**>(&ws)));
-  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(ws);
-  double* bs = reinterpret_cast<double*>(ws + cnt_b);
+  PVS_TRY(ws_reserve(ctx, WS_SCRATCH, lay.bytes(), &ws));
+  unsigned long long* cnt = cnt_p(ws);
+  double* bs = bs_p(ws);
   PVS_HIP(hipMemsetAsync(cnt, 0, (size_t)(K + 1) * 8, ctx->stream));
   const unsigned hb = (unsigned)std::min<int64_t>((total + 255) / 256, 2048);
   hipLaunchKernelGGL(learn_label_stats_kernel, dim3(hb), dim3(256), (size_t)K * 4, ctx->stream, d_labels, d_prev_labels, total, K,
@@ -184,7 +188,7 @@ int launch_label_sums(pvs_ctx* ctx, const float* x, int64_t total, int D, const 
   const int64_t len = (int64_t)K * D;
   const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4));
   float* zero = nullptr;
-  PVS_TRY(ws_reserve(ctx, 3, (size_t)len * 4, reinterpret_cast<void**>(&zero)));
+  PVS_TRY(ws_reserve(ctx, WS_PROJECTED, (size_t)len * 4, &zero));
   PVS_HIP(hipMemsetAsync(zero, 0, (size_t)len * 4, ctx->stream));
   pvs_codebook cb;
   cb.K = K; cb.D = D; cb.d_cent = zero;
@@ -193,15 +197,17 @@ int launch_label_sums(pvs_ctx* ctx, const float* x, int64_t total, int D, const 
   for (int64_t t0 = 0; t0 < total; t0 += rows_per_batch) {
     const int64_t tn = std::min(rows_per_batch, total - t0);
     const int64_t nch = (tn + LEARN_CHUNK - 1) / LEARN_CHUNK;
-    const size_t off_b = ((size_t)(nch + 1) * 8 + 255) / 256 * 256;
+    WsLayout<> lay;
+    const auto off_p = lay.add<int64_t>((size_t)nch + 1);
+    const auto part_p = lay.add<float>((size_t)nch * len);
     char* ws = nullptr;
-    PVS_TRY(ws_reserve(ctx, 1, off_b + (size_t)nch * len * 4, reinterpret_cast<void**>(&ws)));
-    int64_t* off = reinterpret_cast<int64_t*>(ws);
-    float* part = reinterpret_cast<float*>(ws + off_b);
+    PVS_TRY(ws_reserve(ctx, WS_SCRATCH, lay.bytes(), &ws));
+    int64_t* off = off_p(ws);
+    float* part = part_p(ws);
     const float* xb = x + t0 * D;   // the batch's rows; offsets and labels below are relative to it
     if (square) {
       float* sq = nullptr;
-      PVS_TRY(ws_reserve(ctx, 4, (size_t)tn * D * 4, reinterpret_cast<void**>(&sq)));
+      PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, (size_t)tn * D * 4, &sq));
       hipLaunchKernelGGL(learn_square_kernel, dim3(4096), dim3(256), 0, ctx->stream, xb, tn * D, sq);
       xb = sq;
     }
@@ -281,14 +287,16 @@ int launch_gram(pvs_ctx* ctx, const float* x, int64_t total, int D, double* d_ou
   const int64_t nchunk_all = (total + GRAM_ROWS - 1) / GRAM_ROWS;
   const int64_t per_batch = std::max<int64_t>(1, ((int64_t)1 << 30) / (tl * 8));
   double* acc = nullptr;
-  PVS_TRY(ws_reserve(ctx, 4, (size_t)tl * 8, reinterpret_cast<void**>(&acc)));
+  PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, (size_t)tl * 8, &acc));
   int first = 1;
   for (int64_t c0 = 0; c0 < nchunk_all; c0 += per_batch) {
     const int64_t nc = std::min(per_batch, nchunk_all - c0);
+    WsLayout<8> lay;   // tile partials and column sums, packed
+    const auto part_p = lay.add<double>((size_t)nc * tl), cs_p = lay.add<double>((size_t)nc * D);
     char* ws = nullptr;
-    PVS_TRY(ws_reserve(ctx, 1, (size_t)nc * (tl + D) * 8, reinterpret_cast<void**>(&ws)));
-    double* part = reinterpret_cast<double*>(ws);
-    double* cs = part + nc * tl;
+    PVS_TRY(ws_reserve(ctx, WS_SCRATCH, lay.bytes(), &ws));
+    double* part = part_p(ws);
+    double* cs = cs_p(ws);
     const int64_t r0 = c0 * GRAM_ROWS;
     const int64_t rows = std::min<int64_t>(total - r0, nc * GRAM_ROWS);
     hipLaunchKernelGGL(learn_gram_kernel, dim3((unsigned)(ntile * ntile), (unsigned)nc), dim3(256), 0, ctx->stream, x + r0 * D, rows, D,
@@ -428,7 +436,7 @@ int launch_seed_distances(pvs_ctx* ctx, const float* x, int64_t total, int D, co
   const size_t lds = seed_lds_bytes(n_cand, D);
   const int64_t nblk = (total + SEED_ROWS - 1) / SEED_ROWS;
   double* bp = nullptr;
-  PVS_TRY(ws_reserve(ctx, 1, (size_t)nblk * SEED_MAX * 8, reinterpret_cast<void**>(&bp)));
+  PVS_TRY(ws_reserve(ctx, WS_SCRATCH, (size_t)nblk * SEED_MAX * 8, &bp));
   if (gc)
     hipLaunchKernelGGL(learn_seed_kernel<true>, dim3((unsigned)nblk), dim3(256), lds, ctx->stream, x, total, D, d_cand, n_cand, d_mind, d_dist, bp);
   else
@@ -591,7 +599,7 @@ int launch_kmeanspp_run(pvs_ctx* ctx, const float* x, int64_t total, int D, int 
   const bool gc = seed_global_cand(trials, D);
   const size_t lds = seed_lds_bytes(trials, D);
   double* bp = nullptr;
-  PVS_TRY(ws_reserve(ctx, 1, (size_t)nblk_seed * SEED_MAX * 8, reinterpret_cast<void**>(&bp)));
+  PVS_TRY(ws_reserve(ctx, WS_SCRATCH, (size_t)nblk_seed * SEED_MAX * 8, &bp));
   // first centre: its distances are the running minima
   hipLaunchKernelGGL(learn_copy_row_kernel, dim3(1), dim3(64), 0, ctx->stream, x, D, d_indices, 0, d_cand);
   PVS_TRY(launch_seed_distances(ctx, x, total, D, d_cand, 1, nullptr, d_dist, d_pots));

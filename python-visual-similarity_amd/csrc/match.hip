@@ -366,8 +366,6 @@ __global__ __launch_bounds__(256) void verify_refine_kernel(const PairRec* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host side
-constexpr int WS_MATCH_TABLE = 13, WS_VERIFY_POINTS = 14, WS_VERIFY_SMALL = 15;
-
 int check_csr(const char* who, const int64_t* off, int64_t n_images, const char* name) {
   if (n_images < 0) PVS_FAIL(PVS_ERR_INVALID, "%s: negative image count (%s)", who, name);
   if (!off) PVS_FAIL(PVS_ERR_INVALID, "%s: null offsets (%s)", who, name);
@@ -410,7 +408,7 @@ int upload_pairs(pvs_ctx* ctx, const int64_t* h_off_a, const int64_t* h_off_b, c
     ob += r.n_b;
     mx = std::max(mx, (int)r.n_a);
   }
-  PVS_TRY(ws_reserve(ctx, WS_MATCH_TABLE, recs.size() * sizeof(PairRec), reinterpret_cast<void**>(d_pairs)));
+  PVS_TRY(ws_reserve(ctx, WS_MATCH_TABLE, recs.size() * sizeof(PairRec), d_pairs));
   PVS_HIP(hipMemcpyAsync(*d_pairs, recs.data(), recs.size() * sizeof(PairRec), hipMemcpyHostToDevice, ctx->stream));
   *total_a = oa;
   *max_a = mx;
@@ -450,7 +448,7 @@ PVS_EXPORT int pvs_match_u8_dev(pvs_ctx* ctx, const void* d_rows_a, const int64_
   if (any_b && !d_rows_b) PVS_FAIL(PVS_ERR_INVALID, "%s: null B rows", who);
   PVS_HIP(hipSetDevice(ctx->device));
   MatchTile* d_tiles = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_MATCH_TABLE, tiles.size() * sizeof(MatchTile), reinterpret_cast<void**>(&d_tiles)));
+  PVS_TRY(ws_reserve(ctx, WS_MATCH_TABLE, tiles.size() * sizeof(MatchTile), &d_tiles));
   // pageable source: the runtime has copied it out of `tiles` when the call returns
   PVS_HIP(hipMemcpyAsync(d_tiles, tiles.data(), tiles.size() * sizeof(MatchTile), hipMemcpyHostToDevice, ctx->stream));
   ScopedTimer tm(ctx, T_MISC);
@@ -508,10 +506,12 @@ PVS_EXPORT int pvs_verify_dev(pvs_ctx* ctx, const float* d_frames_a, const int64
   if (total_a > 0 && (!d_frames_a || !d_frames_b || !d_matches || !d_mask)) PVS_FAIL(PVS_ERR_INVALID, "%s: null frames, matches or mask", who);
   VPoint* d_pts = nullptr;
   char* d_small = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_VERIFY_POINTS, (size_t)total_a * sizeof(VPoint), reinterpret_cast<void**>(&d_pts)));
-  PVS_TRY(ws_reserve(ctx, WS_VERIFY_SMALL, (size_t)total_a * 5, reinterpret_cast<void**>(&d_small)));
-  int32_t* d_hyp = reinterpret_cast<int32_t*>(d_small);
-  uint8_t* d_tmp = reinterpret_cast<uint8_t*>(d_small) + (size_t)total_a * 4;
+  PVS_TRY(ws_reserve(ctx, WS_VERIFY_POINTS, (size_t)total_a * sizeof(VPoint), &d_pts));
+  WsLayout<4> lay;
+  const auto hyp_p = lay.add<int32_t>((size_t)total_a);
+  const auto tmp_p = lay.add<uint8_t>((size_t)total_a);
+  PVS_TRY(ws_reserve(ctx, WS_VERIFY_SMALL, lay.bytes(), &d_small));
+  int32_t* d_hyp = hyp_p(d_small);
   const double tol_sq = tol * tol;
   if ((max_a + 255) / 256 > 65535) PVS_FAIL(PVS_ERR_UNSUPPORTED, "%s: an image with %d rows is beyond the exhaustive search", who, max_a);
   const unsigned chunks = (unsigned)((max_a + 255) / 256);
@@ -526,7 +526,7 @@ PVS_EXPORT int pvs_verify_dev(pvs_ctx* ctx, const float* d_frames_a, const int64
       PVS_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(verify_refine_kernel, dim3(np), dim3(256), 0, ctx->stream, d_pairs + p0, d_match_counts + p0, d_pts, d_hyp, tol_sq,
-                       refine_rounds, d_tmp, d_inliers + p0, d_models + 6 * p0, d_best + p0, d_mask);
+                       refine_rounds, tmp_p(d_small), d_inliers + p0, d_models + 6 * p0, d_best + p0, d_mask);
     PVS_HIP(hipGetLastError());
   }
   return PVS_OK;

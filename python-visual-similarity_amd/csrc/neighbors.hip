@@ -284,8 +284,6 @@ static int nb_sqnorms(pvs_ctx* ctx, const T* x, int64_t rows, int64_t L, double*
   return PVS_OK;
 }
 
-static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
-
 // float64 kNN over complete rows: f64 GEMM panel -> -d -> rank (approximate k-th) -> candidates within the margin -> re-score in
 // the fixed order of nb_rescore_kernel -> rank.  The GEMM's split-K tail sums some tiles in another order, so its values alone
 // could order two identical rows by rounding; the re-score makes the value a function of the two rows.
@@ -295,17 +293,22 @@ static int knn_f64_rows(pvs_ctx* ctx, const double* Q, int64_t nq, const double*
   const int cap = std::min(NB_CAP_MAX, std::max(256, 8 * k));
   const bool filt = k <= NB_K_MAX;
   double* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * N * sizeof(double), reinterpret_cast<void**>(&panel)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * N * sizeof(double), &panel));
   char* w6 = nullptr;
-  const size_t ai_b = al256((size_t)QT * k * 8), av_b = al256((size_t)QT * k * 8), c_b = al256((size_t)QT * cap * 8),
-               n_b = al256((size_t)QT * 4), k_b = al256((size_t)QT * cap * 8);
-  PVS_TRY(ws_reserve(ctx, 6, ai_b + av_b + c_b + n_b + k_b + 256, reinterpret_cast<void**>(&w6)));
-  int64_t* aidx = reinterpret_cast<int64_t*>(w6);
-  double* aval = reinterpret_cast<double*>(w6 + ai_b);
-  int64_t* cand = reinterpret_cast<int64_t*>(w6 + ai_b + av_b);
-  int* count = reinterpret_cast<int*>(w6 + ai_b + av_b + c_b);
-  double* key = reinterpret_cast<double*>(w6 + ai_b + av_b + c_b + n_b);
-  unsigned long long* ovf = reinterpret_cast<unsigned long long*>(w6 + ai_b + av_b + c_b + n_b + k_b);
+  WsLayout<> lay;
+  const auto aidx_p = lay.add<int64_t>((size_t)QT * k);
+  const auto aval_p = lay.add<double>((size_t)QT * k);
+  const auto cand_p = lay.add<int64_t>((size_t)QT * cap);
+  const auto count_p = lay.add<int>((size_t)QT);
+  const auto key_p = lay.add<double>((size_t)QT * cap);
+  const auto ovf_p = lay.add<unsigned long long>(32);
+  PVS_TRY(ws_reserve(ctx, WS_LISTS, lay.bytes(), &w6));
+  int64_t* aidx = aidx_p(w6);
+  double* aval = aval_p(w6);
+  int64_t* cand = cand_p(w6);
+  int* count = count_p(w6);
+  double* key = key_p(w6);
+  unsigned long long* ovf = ovf_p(w6);
   PVS_HIP(hipMemsetAsync(ovf, 0, 8, ctx->stream));
   for (int64_t q0 = 0; q0 < nq; q0 += QT) {
     const int64_t qn = std::min(QT, nq - q0);
@@ -336,14 +339,15 @@ static int knn_f64_rows(pvs_ctx* ctx, const double* Q, int64_t nq, const double*
   return PVS_OK;
 }
 
-// float32 rows -> float64 copies in workspace slot 8 (the full f64 pass); Q == X shares one copy
+// float32 rows -> float64 copies in WS_NB_F64_ROWS (the full f64 pass); Q == X shares one copy
 static int to_f64_copies(pvs_ctx* ctx, const float* Q, int64_t nq, const float* X, int64_t N, int64_t L, double** q64, double** x64) {
   const bool same = (Q == X && nq == N);
-  const size_t xb = al256((size_t)N * L * 8), qb = same ? 0 : al256((size_t)nq * L * 8);
+  WsLayout<> lay;
+  const auto x_p = lay.add<double>((size_t)N * L), q_p = lay.add<double>(same ? 0 : (size_t)nq * L);
   char* w = nullptr;
-  PVS_TRY(ws_reserve(ctx, 8, xb + qb, reinterpret_cast<void**>(&w)));
-  *x64 = reinterpret_cast<double*>(w);
-  *q64 = same ? *x64 : reinterpret_cast<double*>(w + xb);
+  PVS_TRY(ws_reserve(ctx, WS_NB_F64_ROWS, lay.bytes(), &w));
+  *x64 = x_p(w);
+  *q64 = same ? *x64 : q_p(w);
   ScopedTimer tm(ctx, T_MISC);
   hipLaunchKernelGGL(nb_f32_to_f64_kernel, dim3(nb_grid(N * L)), dim3(256), 0, ctx->stream, X, N * L, *x64);
   if (!same) hipLaunchKernelGGL(nb_f32_to_f64_kernel, dim3(nb_grid(nq * L)), dim3(256), 0, ctx->stream, Q, nq * L, *q64);
@@ -371,13 +375,14 @@ PVS_EXPORT int pvs_l2_knn_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const v
   if (nq == 0) return PVS_OK;
   if (!d_idx || !d_sqdist) PVS_FAIL(PVS_ERR_INVALID, "pvs_l2_knn_dev: null output");
   const bool same = (d_Q == d_X && nq == N);
-  // norms |x|^2 (queries) and |y|^2 (rows), f64, + the largest of both: workspace slot 7
-  const size_t nrm_b = al256((size_t)(N + (same ? 0 : nq)) * 8) + 256;
+  // norms |x|^2 (queries) and |y|^2 (rows), f64, + the largest of both
+  WsLayout<> nrm;
+  const auto nrm_p = nrm.add<double>((size_t)(N + (same ? 0 : nq))), max_p = nrm.add<double>(32);
   char* w7 = nullptr;
-  PVS_TRY(ws_reserve(ctx, 7, nrm_b, reinterpret_cast<void**>(&w7)));
-  double* yn = reinterpret_cast<double*>(w7);
+  PVS_TRY(ws_reserve(ctx, WS_NB_NORMS, nrm.bytes(), &w7));
+  double* yn = nrm_p(w7);
   double* xn = same ? yn : yn + N;
-  double* d_max = reinterpret_cast<double*>(w7 + nrm_b - 256);
+  double* d_max = max_p(w7);
   if (is_f64) {
     const double* Q = static_cast<const double*>(d_Q);
     const double* X = static_cast<const double*>(d_X);
@@ -405,20 +410,18 @@ PVS_EXPORT int pvs_l2_knn_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const v
     const bool mfma = L % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0 &&
                       L <= (int64_t)8 * 1024 * 1024;
     const double chain = mfma ? 1025.0 + (double)L / 1024.0 : (double)L + 1.0;
-    // slot 6: |y|^2 / 2 in f32, approximate lists, candidates, counts, keys, overflow counter
-    const size_t hy_b = al256((size_t)N * 4), ai_b = al256((size_t)QT * k * 8), av_b = al256((size_t)QT * k * 4),
-                 c_b = al256((size_t)QT * cap * 8), n_b = al256((size_t)QT * 4), k_b = al256((size_t)QT * cap * 8);
+    const KnnF32Layout lay = knn_f32_layout(N, QT, k, cap);
     char* w6 = nullptr;
-    PVS_TRY(ws_reserve(ctx, 6, hy_b + ai_b + av_b + c_b + n_b + k_b + 256, reinterpret_cast<void**>(&w6)));
-    float* hy = reinterpret_cast<float*>(w6);
-    int64_t* aidx = reinterpret_cast<int64_t*>(w6 + hy_b);
-    float* aval = reinterpret_cast<float*>(w6 + hy_b + ai_b);
-    int64_t* cand = reinterpret_cast<int64_t*>(w6 + hy_b + ai_b + av_b);
-    int* count = reinterpret_cast<int*>(w6 + hy_b + ai_b + av_b + c_b);
-    double* key = reinterpret_cast<double*>(w6 + hy_b + ai_b + av_b + c_b + n_b);
-    unsigned long long* ovf = reinterpret_cast<unsigned long long*>(w6 + hy_b + ai_b + av_b + c_b + n_b + k_b);
+    PVS_TRY(ws_reserve(ctx, WS_LISTS, lay.bytes, &w6));
+    float* hy = lay.hy(w6);
+    int64_t* aidx = lay.aidx(w6);
+    float* aval = lay.aval(w6);
+    int64_t* cand = lay.cand(w6);
+    int* count = lay.count(w6);
+    double* key = lay.key(w6);
+    unsigned long long* ovf = lay.ovf(w6);
     float* panel = nullptr;
-    PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * NC * sizeof(float), reinterpret_cast<void**>(&panel)));
+    PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
     PVS_HIP(hipMemsetAsync(ovf, 0, 8, ctx->stream));
     hipLaunchKernelGGL(nb_half_f32_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, yn, N, hy);
     PVS_HIP(hipGetLastError());
@@ -492,12 +495,14 @@ static int radius_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_
     Q = q64;
     X = x64;
   }
-  const size_t nrm_b = al256((size_t)(N + (same ? 0 : nq)) * 8), cur_b = al256((size_t)nq * 8);
+  WsLayout<> nrm;
+  const auto nrm_p = nrm.add<double>((size_t)(N + (same ? 0 : nq)));
+  const auto cur_p = nrm.add<int64_t>((size_t)nq);
   char* w7 = nullptr;
-  PVS_TRY(ws_reserve(ctx, 7, nrm_b + cur_b, reinterpret_cast<void**>(&w7)));
-  double* yn = reinterpret_cast<double*>(w7);
+  PVS_TRY(ws_reserve(ctx, WS_NB_NORMS, nrm.bytes(), &w7));
+  double* yn = nrm_p(w7);
   double* xn = same ? yn : yn + N;
-  int64_t* cursor = reinterpret_cast<int64_t*>(w7 + nrm_b);
+  int64_t* cursor = cur_p(w7);
   PVS_TRY(nb_sqnorms(ctx, X, N, L, yn));
   if (!same) PVS_TRY(nb_sqnorms(ctx, Q, nq, L, xn));
   if (fill) {
@@ -508,7 +513,7 @@ static int radius_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_
   }
   const int64_t QT = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / N));
   double* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * N * sizeof(double), reinterpret_cast<void**>(&panel)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * N * sizeof(double), &panel));
   for (int64_t q0 = 0; q0 < nq; q0 += QT) {
     const int64_t qn = std::min(QT, nq - q0);
     PVS_TRY(launch_cosine_f64_dev(ctx, Q + q0 * L, qn, X, N, L, nullptr, nullptr, panel, N));

@@ -350,7 +350,7 @@ PVS_EXPORT int pvs_pq_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t nq
   const int64_t QT = deep ? std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 28) / N)) : std::min<int64_t>(nq, PQ_PANEL_QUERIES);
   const int64_t NC = deep ? N : std::min<int64_t>(N, std::max<int64_t>(PQ_PANEL_MIN_COLS, PQ_PANEL_ELEMS / QT));
   float* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, 2, (size_t)QT * NC * sizeof(float), reinterpret_cast<void**>(&panel)));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
   const int64_t tsize = (int64_t)m * ksub;
   for (int64_t q0 = 0; q0 < nq; q0 += QT) {
     const int64_t qn = std::min(QT, nq - q0);

@@ -613,16 +613,17 @@ PVS_EXPORT int pvs_sift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, 
 
     float* d_pyr = nullptr;
     char* d_meta = nullptr;
-    PVS_TRY(ws_reserve(ctx, 10, (size_t)floats * sizeof(float), reinterpret_cast<void**>(&d_pyr)));
-    const size_t table_bytes = ((size_t)n_img * sizeof(SiftImage) + 15) & ~(size_t)15;
-    const size_t blk_bytes = (((size_t)n_blocks + 1) * sizeof(int) + 15) & ~(size_t)15;
-    const size_t img_bytes = (((size_t)n_img + 1) * sizeof(int) + 15) & ~(size_t)15;
-    PVS_TRY(ws_reserve(ctx, 11, table_bytes + 2 * blk_bytes + 2 * img_bytes, reinterpret_cast<void**>(&d_meta)));
-    SiftImage* d_table = reinterpret_cast<SiftImage*>(d_meta);
-    int* d_cnt = reinterpret_cast<int*>(d_meta + table_bytes);
-    int* d_off = reinterpret_cast<int*>(d_meta + table_bytes + blk_bytes);
-    int* d_cand_start = reinterpret_cast<int*>(d_meta + table_bytes + 2 * blk_bytes);
-    int* d_img_rows = reinterpret_cast<int*>(d_meta + table_bytes + 2 * blk_bytes + img_bytes);
+    PVS_TRY(ws_reserve(ctx, WS_SIFT_PYRAMID, (size_t)floats * sizeof(float), &d_pyr));
+    WsLayout<16> meta;
+    const auto table_p = meta.add<SiftImage>((size_t)n_img);
+    const auto cnt_p = meta.add<int>((size_t)n_blocks + 1), off_p = meta.add<int>((size_t)n_blocks + 1);
+    const auto cand_start_p = meta.add<int>((size_t)n_img + 1), img_rows_p = meta.add<int>((size_t)n_img + 1);
+    PVS_TRY(ws_reserve(ctx, WS_SIFT_TABLES, meta.bytes(), &d_meta));
+    SiftImage* d_table = table_p(d_meta);
+    int* d_cnt = cnt_p(d_meta);
+    int* d_off = off_p(d_meta);
+    int* d_cand_start = cand_start_p(d_meta);
+    int* d_img_rows = img_rows_p(d_meta);
     PVS_HIP(hipMemcpyAsync(d_table, table.data() + first, (size_t)n_img * sizeof(SiftImage), hipMemcpyHostToDevice, ctx->stream));
     a.img = d_table;
     a.pyr = d_pyr;
@@ -676,16 +677,14 @@ PVS_EXPORT int pvs_sift_dev(pvs_ctx* ctx, const void* d_pixels, int pixel_kind, 
     if (n_cand == 0) continue;
 
     char* d_kp_block = nullptr;
-    const size_t nc = (size_t)n_cand;
-    const size_t cand_b = nc * sizeof(int4), kp_b = nc * sizeof(SiftKp), int_b = ((nc + 1) * sizeof(int) + 15) & ~(size_t)15;
-    const size_t bins_b = nc * SF_MAX_PEAKS * sizeof(float);
-    PVS_TRY(ws_reserve(ctx, 12, cand_b + kp_b + 3 * int_b + bins_b, reinterpret_cast<void**>(&d_kp_block)));
-    int4* d_cand = reinterpret_cast<int4*>(d_kp_block);
-    SiftKp* d_kp = reinterpret_cast<SiftKp*>(d_kp_block + cand_b);
-    int* d_npeaks = reinterpret_cast<int*>(d_kp_block + cand_b + kp_b);
-    int* d_nkeep = reinterpret_cast<int*>(d_kp_block + cand_b + kp_b + int_b);
-    int* d_row_off = reinterpret_cast<int*>(d_kp_block + cand_b + kp_b + 2 * int_b);
-    float* d_bins = reinterpret_cast<float*>(d_kp_block + cand_b + kp_b + 3 * int_b);
+    const auto kl = sift_cand_layout<int4, SiftKp>((size_t)n_cand, SF_MAX_PEAKS);
+    PVS_TRY(ws_reserve(ctx, WS_SIFT_KEYPOINTS, kl.bytes, &d_kp_block));
+    int4* d_cand = kl.cand(d_kp_block);
+    SiftKp* d_kp = kl.kp(d_kp_block);
+    int* d_npeaks = kl.npeaks(d_kp_block);
+    int* d_nkeep = kl.nkeep(d_kp_block);
+    int* d_row_off = kl.row_off(d_kp_block);
+    float* d_bins = kl.bins(d_kp_block);
     d.counts = d_off;
     d.cand = d_cand;
     for (int o = 0; o < max_oct; ++o) {

@@ -1056,15 +1056,17 @@ int launch_assign(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, int 
   if (pre) {
     const int64_t cap = (nblocks + grid - 1) / grid * ASSIGN_ROWS;   // a workgroup can list at most what it processes
     char* ws = nullptr;
-    const size_t cnt_b = ((size_t)grid * 8 + 255) / 256 * 256;
     // uint8 rows: the prefilter forms every row's sum anyway and leaves (sum + 1e-7, 1 / that) for the aggregate pass,
     // which then converts elements without a reduction and a division per member row
     const bool stat = rowstat_out != nullptr && kind == PVS_DESC_U8_ROOTSIFT;
-    const size_t list_b = ((size_t)grid * cap * 8 + 255) / 256 * 256;
-    PVS_TRY(ws_reserve(ctx, 6, cnt_b + list_b + (stat ? (size_t)total * sizeof(float2) : 0), reinterpret_cast<void**>(&ws)));
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(ws);
-    int64_t* rows = reinterpret_cast<int64_t*>(ws + cnt_b);
-    float2* rowstat = stat ? reinterpret_cast<float2*>(ws + cnt_b + list_b) : nullptr;
+    WsLayout<> lay;
+    const auto cnt_p = lay.add<unsigned long long>((size_t)grid);
+    const auto rows_p = lay.add<int64_t>((size_t)grid * cap);
+    const auto stat_p = lay.add<float2>(stat ? (size_t)total : 0);
+    PVS_TRY(ws_reserve(ctx, WS_LISTS, lay.bytes(), &ws));
+    unsigned long long* cnt = cnt_p(ws);
+    int64_t* rows = rows_p(ws);
+    float2* rowstat = stat ? stat_p(ws) : nullptr;
     if (stat) *rowstat_out = rowstat;
     Assign16Args p{d_desc, total, cb->D, ld, static_cast<const _Float16*>(cb->d_c16), cb->d_cnorm, cb->K_pad, cb->D_pad16,
                    cb->c16_shift, cb->cmax, static_cast<const _Float16*>(cb->d_cnk), cb->cn_e1, cb->K, d_labels, rows, cnt, cap, rowstat,

@@ -1,0 +1,144 @@
+// Device scratch memory of a context: the slot names, the typed reserve, and the layout of a block that holds several buffers.
+// Nothing here needs a HIP header, so a host-only program can include this file alone (bench/ws_layout_check.cpp does).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+struct pvs_ctx;
+
+namespace pvs {
+
+// A context keeps 16 grow-only blocks of device memory (pvs_ctx::ws).  ws_reserve(ctx, slot, bytes, &p) hands out the slot's block,
+// and when the block is too small it waits for the stream, FREES the block and allocates a larger one.  Hence the rule:
+//
+//   A pointer into a slot is dead once anything that may reserve the same slot has been called; re-reserve after such a call.
+//
+// Every function that reserves a slot is listed here; keep the table in step with `grep ws_reserve`.
+//
+//   WS_STAGE_IN       api.hip: pvs_vlad_encode, pvs_fisher_encode, pvs_cosine, pvs_cosine_topk, pvs_cosine_topk_f64 (host rows uploaded)
+//   WS_SCRATCH        api.hip: pvs_vlad_encode_dev (labels), pvs_cosine_topk (norms | lists); cosine.hip: launch_cosine_f64 (norms);
+//                     fisher.hip: launch_gmm_posterior, launch_gmm_em_step, launch_fisher (table | responsibilities | partials);
+//                     learn.hip: launch_kmeans_step (twice), launch_label_sums, launch_gram, launch_seed_distances, launch_kmeanspp_run
+//   WS_PANEL_OUT      api.hip: pvs_vlad_encode, pvs_fisher_encode, pvs_cosine (offsets | outputs of the host entry points),
+//                     cosine_topk_impl, pvs_cosine_topk_f64_dev (score panels), pvs_kmeans_step_dev, pvs_gmm_em_step_dev, pvs_label_sums_dev,
+//                     pvs_gram_dev, pvs_seed_distances_dev, pvs_seed_pick_dev, pvs_min_update_dev (statistics); filter.hip:
+//                     launch_cosine_topk_filtered; neighbors.hip: knn_f64_rows, pvs_l2_knn_dev, radius_impl; pq.hip: pvs_pq_scan_topk_dev
+//   WS_PROJECTED      api.hip: project_if_needed (PCA rows), pvs_kmeanspp_run_dev; learn.hip: launch_label_sums (zero centres);
+//                     filter.hip: launch_cosine_topk_filtered (rows and lists of the overflowing queries)
+//   WS_AUX_ROWS       fisher.hip: materialise_f32 (RootSIFT rows); cosine.hip: launch_gemm_mfma, launch_gemm_f64 (split-K partials);
+//                     learn.hip: launch_label_sums (squared rows), launch_gram (tile accumulator)
+//   WS_FP16_ROWS      filter.hip: launch_cosine_topk_filtered
+//   WS_LISTS          filter.hip: launch_cosine_topk_filtered; api.hip: pvs_cosine_topk_f64; vlad.hip: launch_assign;
+//                     neighbors.hip: knn_f64_rows, pvs_l2_knn_dev
+//   WS_NB_NORMS       neighbors.hip: pvs_l2_knn_dev, radius_impl
+//   WS_NB_F64_ROWS    neighbors.hip: to_f64_copies
+//   WS_DSIFT_TABLE    dsift.hip: pvs_dsift_dev
+//   WS_SIFT_PYRAMID, WS_SIFT_TABLES, WS_SIFT_KEYPOINTS    sift.hip: pvs_sift_dev
+//   WS_MATCH_TABLE    match.hip: upload_pairs, pvs_match_u8_dev
+//   WS_VERIFY_POINTS, WS_VERIFY_SMALL    match.hip: pvs_verify_dev
+enum WsSlot : int {
+  WS_STAGE_IN = 0, WS_SCRATCH = 1, WS_PANEL_OUT = 2, WS_PROJECTED = 3, WS_AUX_ROWS = 4, WS_FP16_ROWS = 5, WS_LISTS = 6, WS_NB_NORMS = 7,
+  WS_NB_F64_ROWS = 8, WS_DSIFT_TABLE = 9, WS_SIFT_PYRAMID = 10, WS_SIFT_TABLES = 11, WS_SIFT_KEYPOINTS = 12, WS_MATCH_TABLE = 13,
+  WS_VERIFY_POINTS = 14, WS_VERIFY_SMALL = 15
+};
+
+int ws_reserve(pvs_ctx* ctx, WsSlot which, size_t bytes, void** out);   // api.hip
+template <class T>
+inline int ws_reserve(pvs_ctx* ctx, WsSlot which, size_t bytes, T** out) {
+  void* p = nullptr;
+  const int rc = ws_reserve(ctx, which, bytes, &p);
+  *out = static_cast<T*>(p);
+  return rc;
+}
+
+constexpr size_t ws_round(size_t bytes, size_t align = 256) { return (bytes + align - 1) / align * align; }
+
+// One buffer of a block: where it starts, and the typed pointer once the block's base is known.
+template <class T>
+struct WsPiece {
+  size_t off = 0;
+  T* operator()(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+};
+
+// Buffers of one block, in the order of the add() calls; each takes its bytes rounded up to ALIGN, so each starts on a multiple of it.
+template <size_t ALIGN = 256>
+class WsLayout {
+  size_t end_ = 0;
+
+ public:
+  template <class T>
+  WsPiece<T> add(size_t count) {
+    const WsPiece<T> p{end_};
+    end_ += ws_round(count * sizeof(T), ALIGN);
+    return p;
+  }
+  size_t bytes() const { return end_; }
+};
+
+// ---- layouts that bench/ws_layout_check.cpp holds against their closed forms; the call sites build theirs through these functions.
+// A braced list is evaluated left to right, so the pieces lie in the order of the struct's members.
+// launch_cosine_topk_filtered, WS_LISTS: norms of the fp16 rows, counters, approximate lists, candidate lists, candidate counts
+struct FilterListsLayout {
+  WsPiece<float> invq, invdb;
+  WsPiece<unsigned long long> stats;
+  WsPiece<int64_t> aidx;
+  WsPiece<float> aval;
+  WsPiece<int64_t> cidx;
+  WsPiece<float> cval;
+  WsPiece<int> cnt;
+  size_t bytes;
+};
+inline FilterListsLayout filter_lists_layout(size_t nq, size_t N, size_t QT, size_t k, size_t cap) {
+  WsLayout<> l;
+  return {l.add<float>(nq),       l.add<float>(N),          l.add<unsigned long long>(32), l.add<int64_t>(QT * k), l.add<float>(QT * k),
+          l.add<int64_t>(QT * cap), l.add<float>(QT * cap), l.add<int>(QT),                l.bytes()};
+}
+
+// pvs_l2_knn_dev (float32), WS_LISTS: |y|^2 / 2 in f32, approximate lists, candidates, counts, keys, overflow counter
+struct KnnF32Layout {
+  WsPiece<float> hy;
+  WsPiece<int64_t> aidx;
+  WsPiece<float> aval;
+  WsPiece<int64_t> cand;
+  WsPiece<int> count;
+  WsPiece<double> key;
+  WsPiece<unsigned long long> ovf;
+  size_t bytes;
+};
+inline KnnF32Layout knn_f32_layout(size_t N, size_t QT, size_t k, size_t cap) {
+  WsLayout<> l;
+  return {l.add<float>(N), l.add<int64_t>(QT * k), l.add<float>(QT * k), l.add<int64_t>(QT * cap), l.add<int>(QT), l.add<double>(QT * cap),
+          l.add<unsigned long long>(32), l.bytes()};
+}
+
+// pvs_kmeanspp_run_dev, WS_PROJECTED: nblk = blocks of 4096 rows; `small` is the kernel's own 512 bytes of counters
+struct KmeansppLayout {
+  WsPiece<float> mind, dist, cand;
+  WsPiece<double> block_sums, uniform;
+  WsPiece<int64_t> indices;
+  WsPiece<char> small;
+  size_t bytes;
+};
+inline KmeansppLayout kmeanspp_layout(size_t total, size_t nblk, size_t D, size_t n_clusters, size_t trials) {
+  WsLayout<> l;
+  return {l.add<float>(total), l.add<float>(trials * total), l.add<float>(trials * D), l.add<double>(nblk),
+          l.add<double>((n_clusters > 1 ? n_clusters - 1 : 1) * trials), l.add<int64_t>(n_clusters), l.add<char>(512), l.bytes()};
+}
+
+// pvs_sift_dev, WS_SIFT_KEYPOINTS (16-byte pieces): candidates, refined keypoints, three int tables of n_cand + 1, orientation bins
+template <class Cand, class Kp>
+struct SiftCandLayout {
+  WsPiece<Cand> cand;
+  WsPiece<Kp> kp;
+  WsPiece<int> npeaks, nkeep, row_off;
+  WsPiece<float> bins;
+  size_t bytes;
+};
+template <class Cand, class Kp>
+inline SiftCandLayout<Cand, Kp> sift_cand_layout(size_t n_cand, size_t max_peaks) {
+  WsLayout<16> l;
+  return {l.add<Cand>(n_cand), l.add<Kp>(n_cand), l.add<int>(n_cand + 1), l.add<int>(n_cand + 1), l.add<int>(n_cand + 1),
+          l.add<float>(n_cand * max_peaks), l.bytes()};
+}
+
+}  // namespace pvs
