@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/pvsim.h"
@@ -144,6 +145,26 @@ inline int ensure_lds(pvs_ctx* ctx, const void* fn, size_t bytes) {
     ctx->lds_attr[fn] = (int)bytes;
   }
   return PVS_OK;
+}
+
+// a launch with dynamic LDS on the context's stream: limit raised (once), launched, launch error checked
+template <class Kernel, class... Args>
+inline int launch_lds(pvs_ctx* ctx, Kernel kernel, dim3 grid, dim3 block, size_t lds_bytes, const Args&... args) {
+  PVS_TRY(ensure_lds(ctx, reinterpret_cast<const void*>(kernel), lds_bytes));
+  hipLaunchKernelGGL(kernel, grid, block, lds_bytes, ctx->stream, args...);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+// f(std::integral_constant<int, KIND>{}) for the descriptor kind given at run time (a pvs_desc_kind)
+template <class F>
+inline int dispatch_desc_kind(int kind, F&& f) {
+  switch (kind) {
+    case PVS_DESC_F32: return f(std::integral_constant<int, PVS_DESC_F32>{});
+    case PVS_DESC_F32_ROOTSIFT: return f(std::integral_constant<int, PVS_DESC_F32_ROOTSIFT>{});
+    case PVS_DESC_U8_ROOTSIFT: return f(std::integral_constant<int, PVS_DESC_U8_ROOTSIFT>{});
+    default: PVS_FAIL(PVS_ERR_INVALID, "unknown descriptor kind %d", kind);
+  }
 }
 
 struct ScopedTimer {

@@ -58,14 +58,11 @@ static int materialise_f32(pvs_ctx* ctx, const void*& d_desc, int& kind, int64_t
 int launch_materialise(pvs_ctx* ctx, const void* d_desc, int kind, int64_t total, int D, float* d_out) {
   if (total <= 0) return PVS_OK;
   const dim3 grid((unsigned)((total + 3) / 4));
-  switch (kind) {
-    case PVS_DESC_F32: hipLaunchKernelGGL(materialise_kernel<PVS_DESC_F32>, grid, dim3(256), 0, ctx->stream, d_desc, total, D, d_out); break;
-    case PVS_DESC_F32_ROOTSIFT: hipLaunchKernelGGL(materialise_kernel<PVS_DESC_F32_ROOTSIFT>, grid, dim3(256), 0, ctx->stream, d_desc, total, D, d_out); break;
-    case PVS_DESC_U8_ROOTSIFT: hipLaunchKernelGGL(materialise_kernel<PVS_DESC_U8_ROOTSIFT>, grid, dim3(256), 0, ctx->stream, d_desc, total, D, d_out); break;
-    default: PVS_FAIL(PVS_ERR_INVALID, "unknown descriptor kind %d", kind);
-  }
-  PVS_HIP(hipGetLastError());
-  return PVS_OK;
+  return dispatch_desc_kind(kind, [&](auto k) -> int {
+    hipLaunchKernelGGL(materialise_kernel<decltype(k)::value>, grid, dim3(256), 0, ctx->stream, d_desc, total, D, d_out);
+    PVS_HIP(hipGetLastError());
+    return PVS_OK;
+  });
 }
 
 // ------------------------------------------------------------------------------------ PCA.transform

@@ -551,10 +551,7 @@ static int launch_fused_kind(pvs_ctx* ctx, const FusedArgs& a, int grid) {
   auto kp = vlad_fused_kernel<KIND, false>;
   auto kd = vlad_fused_kernel<KIND, true>;
   auto k = a.stamps != nullptr ? kd : kp;
-  PVS_TRY(ensure_lds(ctx, reinterpret_cast<const void*>(k), FU_LDS));
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(FU_THREADS), FU_LDS, ctx->stream, a);
-  PVS_HIP(hipGetLastError());
-  return PVS_OK;
+  return launch_lds(ctx, k, dim3((unsigned)grid), dim3(FU_THREADS), FU_LDS, a);
 }
 
 bool vlad_fused_eligible(const pvs_codebook* cb, const void* d_desc, int kind, int ld, const float* d_out) {
@@ -587,12 +584,7 @@ int launch_vlad_fused(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, 
   a.stamps = ctx->d_fused_stamps;
   ScopedTimer tm(ctx, T_ASSIGN);
   hipLaunchKernelGGL(fused_queue_init_kernel, dim3(1), dim3(1), 0, ctx->stream, ctx->d_queue, (unsigned int)grid);
-  switch (kind) {
-    case PVS_DESC_F32: return launch_fused_kind<PVS_DESC_F32>(ctx, a, grid);
-    case PVS_DESC_F32_ROOTSIFT: return launch_fused_kind<PVS_DESC_F32_ROOTSIFT>(ctx, a, grid);
-    case PVS_DESC_U8_ROOTSIFT: return launch_fused_kind<PVS_DESC_U8_ROOTSIFT>(ctx, a, grid);
-    default: PVS_FAIL(PVS_ERR_INVALID, "unknown descriptor kind %d", kind);
-  }
+  return dispatch_desc_kind(kind, [&](auto k) { return launch_fused_kind<decltype(k)::value>(ctx, a, grid); });
 }
 
 }  // namespace pvs

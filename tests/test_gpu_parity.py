@@ -857,6 +857,39 @@ def test_prefiltered_assignment_odd_shapes(gpu_ctx, K, D, monkeypatch):
     assert np.array_equal(pre, orc.kmeans_predict(x, C)) or np.mean(pre != orc.kmeans_predict(x, C)) < 1e-3
 
 
+@pytest.mark.parametrize("kind", [DESC_U8_ROOTSIFT, DESC_F32])
+@pytest.mark.parametrize("total", [4096, 4097, 4351])
+def test_prefilter_lists_at_the_smallest_sizes(gpu_ctx, tables, kind, total):
+    """The prefilter's lists where the last block is short: 4096 rows is the smallest input the prefilter runs on, 4097 and 4351 leave
+    the last block of 256 with 1 and 255 rows.  Rows past the end are prefetched as copies of the last row and must stay out of the
+    ballot, next to rows that must be listed: an exact tie (a duplicated centre) and an all-zero row among the last 32.  Labels and
+    encodings of the 32x32x16 (1) and the 16x16x32 (4) prefilter equal those of the exact kernel alone (0), bit for bit."""
+    rng = np.random.default_rng(23)
+    raw = synth.sift_like(total, rng)
+    C = tables["centroids"].copy()
+    assert C.shape == (256, 128)
+    a = int(np.bincount(orc.kmeans_predict(synth.rootsift(raw), C)[:-32], minlength=256)[:255].argmax())
+    C[255] = C[a]                                    # the most used centre twice: every row nearest to it ties exactly
+    raw[total - 3] = raw[np.flatnonzero(orc.kmeans_predict(synth.rootsift(raw), C)[:-32] == a)[0]]
+    raw[total - 7] = 0.0
+    # NumPy oracle: at least one row whose two nearest centres tie exactly, so the list path is certainly taken
+    xr = synth.rootsift(raw)
+    pd = np.einsum("ij,ij->i", C, C)[None, :] + np.float32(-2.0) * np.einsum("id,kd->ik", xr, C)
+    two = np.partition(pd, 1, axis=1)[:, :2]
+    assert np.any(two[-32:, 0] == two[-32:, 1])
+    x = raw.astype(np.uint8) if kind == DESC_U8_ROOTSIFT else xr
+    cb = gpu_ctx.codebook(C)
+    off = np.array([0, 1000, total], np.int64)
+    with gpu_ctx.option(_ffi.OPT_ASSIGN_PREFILTER, 0):
+        v_exact, exact = gpu_ctx.vlad_encode(cb, x, off, kind, return_labels=True)
+    assert not np.any(exact == 255)                  # the first of the two equal centres wins
+    for variant in (1, 4):
+        with gpu_ctx.option(_ffi.OPT_ASSIGN_PREFILTER, variant):
+            v, lab = gpu_ctx.vlad_encode(cb, x, off, kind, return_labels=True)
+        assert np.array_equal(exact, lab), (variant, np.argwhere(exact != lab)[:10])
+        assert v_exact.tobytes() == v.tobytes(), variant
+
+
 @pytest.mark.parametrize("M,N,L", [(300, 300, 32768), (130, 257, 4096), (129, 700, 2600), (64, 64, 40)])
 def test_cosine_scores_are_the_defined_fp32_recurrence(gpu_ctx, M, N, L):
     """Beyond the 2e-6 tolerance against the reference's BLAS result: the exact GEMM's score is a defined recurrence
