@@ -446,6 +446,30 @@ int pvs_pq_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t nq, int m, in
 int pvs_rescore_rows_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_X, int64_t N, int64_t d, const float* d_inv_q,
                          const float* d_inv_db, const int64_t* d_cand /*[nq][R]*/, int64_t R, float* d_val /*[nq][R]*/);
 
+/* ---------------------------------------------------------------- query expansion, database-side augmentation
+ * Chum et al. (ICCV 2007), Arandjelovic & Zisserman (CVPR 2012), Radenovic et al. (PAMI 2018): the query, or every database row, is
+ * replaced by a weighted sum of itself and the rows its first ranking found.  The device's part is that sum over whole rows, gathered
+ * by index.  T is float32 (is_f64 == 0) or float64; ALL arithmetic is in T with separate roundings -- a multiply, then an add, never
+ * an fma -- in the stated order, so that a restatement with element operations in T gives the same bits.
+ *   X       T [N][L], the rows to gather from.
+ *   self    T [n][L] or NULL; w_self T [n], NULL = 1 (read only together with self).
+ *   idx     int64 [n][r]; w T [n][r].
+ *   out     T [n][L].  For each row i and column t: acc = +0; with self, acc = acc + w_self[i] * self[i][t]; then for j = 0 .. r-1
+ *           ascending, with c = idx[i][j]: if 0 <= c < N, acc = acc + w[i][j] * X[c][t], otherwise the slot is skipped (unfilled list
+ *           slots may be passed as -1); out[i][t] = acc.
+ * n == 0 is a no-op; r == 0 gives the self term alone (+0 without one).  d_out may be d_self itself (each element is read and then
+ * written by the same lane); any other overlap of the two, and any overlap of [d_out, d_out + n L) with [d_X, d_X + N L), is
+ * PVS_ERR_INVALID, found on the host before anything is launched, as are L < 1, N < 0, n < 0, r < 0 and a missing pointer that is
+ * needed (d_out; d_idx and d_w when r > 0; d_X when r > 0 and N > 0).  Matrices need the alignment of their elements only; rows whose
+ * byte length is a multiple of 16 in 16-byte aligned matrices move as 16-byte loads.  Needs no workspace; enqueues on the context's
+ * stream and does not wait for it; timed on slot 6. */
+#define PVS_COMBINE_CHUNK_BYTES 8192   /* bytes of an output row that one workgroup owns (2048 float32 / 1024 float64 columns) */
+#define PVS_COMBINE_BATCH 8            /* list slots whose row loads are in flight together */
+int pvs_combine_rows_dev(pvs_ctx* ctx, const void* d_X, int64_t N, int64_t L, int is_f64,
+                         const void* d_self /*[n][L] or NULL*/, const void* d_w_self /*[n], NULL = 1*/,
+                         const int64_t* d_idx /*[n][r]*/, const void* d_w /*[n][r]*/, int64_t n, int r,
+                         void* d_out /*[n][L]*/);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

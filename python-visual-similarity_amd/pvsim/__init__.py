@@ -2,9 +2,10 @@
 
     from pvsim.encoders import VLADEncoder, FisherVectorEncoder, Pipeline, KMeansWeights, GMMWeights
     from pvsim.features import RootSIFT, SIFT, Lambda, DeepConvFeature
-    from pvsim import eval                     # retrieve_top_k_similar, top_k_map, top_k_accuracy, rerank_spatial
+    from pvsim import eval                     # retrieve_top_k_similar, top_k_map, top_k_accuracy, rerank_spatial, expand_verified
     from pvsim import verify                   # LocalFeatureIndex, SpatialVerifier, match (spatial re-ranking)
     from pvsim import CompactIndex, ProductQuantizer   # product-quantised index, ADC search (m + 4 bytes per image)
+    from pvsim import QueryExpansion                   # query expansion / database-side augmentation on a DeviceIndex
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -14,7 +15,8 @@ from .engine import Context, default_context, pack_descriptors
 from . import models
 from ._errors import CapacityError
 from .compact import CompactIndex, ProductQuantizer
+from .expand import QueryExpansion
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "ProductQuantizer"]
+           "CompactIndex", "ProductQuantizer", "QueryExpansion"]

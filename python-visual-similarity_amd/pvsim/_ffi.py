@@ -25,6 +25,7 @@ DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT = 0, 1, 2
 OPT_ASSIGN_PREFILTER, OPT_VLAD_PATH, OPT_TOPK_SELECT_ONLY, OPT_AGG_VARIANT, OPT_FISHER_SCALE = 0, 1, 2, 3, 4      # pvs_option
 PIX_U8_RGB, PIX_U8_GRAY, PIX_F32_RGB, PIX_F32_GRAY = 0, 1, 2, 3          # pvs_pixel_kind
 DSIFT_U8, DSIFT_F32, DSIFT_F32_RAW, DSIFT_F32_QUANT = 0, 1, 2, 3                         # pvs_dsift_out
+COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
 VLAD_PATH_AUTO, VLAD_PATH_GATHER, VLAD_PATH_STREAM, VLAD_PATH_FUSED = 0, 1, 2, 3
 TIMER_NAMES = ("assign", "aggregate", "cosine_gemm", "topk", "fisher_posterior", "fisher_moments", "misc", "rescore")
 
@@ -123,6 +124,7 @@ SIGNATURES = {
     "pvs_pq_lut_dev": [_vp, _vp, _vp, _i64, _vp],
     "pvs_pq_scan_topk_dev": [_vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _vp, _int, _i64, _int, _vp, _vp],
     "pvs_rescore_rows_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp],
+    "pvs_combine_rows_dev": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _int, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

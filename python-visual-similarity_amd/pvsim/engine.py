@@ -440,6 +440,14 @@ class Context:
         check(_ffi.lib().pvs_rescore_rows_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, d, ptr(d_invq), ptr(d_invdb), ptr(d_cand), R,
                                               ptr(d_val)))
 
+    # query expansion / database-side augmentation
+    COMBINE_CHUNK_BYTES, COMBINE_BATCH = _ffi.COMBINE_CHUNK_BYTES, _ffi.COMBINE_BATCH
+
+    def combine_rows_dev(self, d_x, N, L, is_f64, d_self, d_w_self, d_idx, d_w, n, r, d_out):
+        """pvs_combine_rows_dev: out[i] = w_self[i] self[i] + sum_j w[i][j] X[idx[i][j]] in list order, slots outside [0, N) skipped"""
+        check(_ffi.lib().pvs_combine_rows_dev(self.handle, ptr(d_x), N, L, int(bool(is_f64)), ptr(d_self), ptr(d_w_self), ptr(d_idx),
+                                              ptr(d_w), n, r, ptr(d_out)))
+
     def f32_to_f16_dev(self, d_src, n, d_dst):
         check(_ffi.lib().pvs_f32_to_f16_dev(self.handle, ptr(d_src), n, ptr(d_dst)))
 

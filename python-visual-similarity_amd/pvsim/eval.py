@@ -14,7 +14,7 @@ import numpy as np
 from ._utils import cosine_similarity  # re-exported like the reference's `from ._utils import *`
 from .engine import default_context
 
-__all__ = ["retrieve_top_k_similar", "top_k_map", "top_k_accuracy", "rerank_spatial"]
+__all__ = ["retrieve_top_k_similar", "top_k_map", "top_k_accuracy", "rerank_spatial", "expand_verified"]
 
 
 
@@ -54,6 +54,23 @@ def _rank_compact(query_vecs: np.ndarray, index, k: int | None, rerank: int = 0)
     return index.rank(query_vecs, kk, rerank=rerank)             # rerank < k raises there, as it does for a direct call
 
 
+def _rank_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths, k: int, ctx, resident, expand, members=None):
+    """_rank with query expansion (pvsim.expand): on the resident index, or on a DeviceIndex that holds the dict for this call."""
+    from .index import DeviceIndex
+    if resident is not None:
+        return resident.rank_expanded(query_vecs, k, expand, members=members)
+    temp = DeviceIndex(dict(zip(paths, all_vectors)), ctx or default_context())
+    try:
+        return temp.rank_expanded(query_vecs, k, expand, members=members)
+    finally:
+        temp.close()
+
+
+def _no_compact_expansion(all_vectors, expand):
+    if expand is not None and all_vectors is None:
+        raise ValueError("query expansion needs the full-precision rows: use a dict or a DeviceIndex, not a CompactIndex")
+
+
 def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None, resident=None):
     """-> (indices (nq, k') int64, scores (nq, k')) with k' = min(k, N) (k=None: all N)."""
     if all_vectors is None:                                     # a CompactIndex: no host matrix
@@ -75,11 +92,25 @@ def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=No
     return ctx.cosine_topk_f64(query_vecs, all_vectors, kk)
 
 
+def _rank_maybe_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths, k: int | None, ctx, resident, expand):
+    """_rank, or with `expand` (a pvsim.expand.QueryExpansion) the ranking of the expanded queries: same k' and same empty results"""
+    if expand is None:
+        return _rank(query_vecs, all_vectors, k, ctx, resident)
+    _no_compact_expansion(all_vectors, expand)
+    n = all_vectors.shape[0]
+    kk = n if k is None else max(0, min(int(k), n))
+    if query_vecs.shape[0] == 0 or kk == 0:
+        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float32)
+    return _rank_expanded(query_vecs, all_vectors, paths, kk, ctx, resident, expand)
+
+
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
-                           k: int = 5, rerank: int = 0) -> list[tuple[str, float]]:
+                           k: int = 5, rerank: int = 0, expand=None) -> list[tuple[str, float]]:
     """[(image_path, similarity)] of the k most similar database entries, best first.  `rerank=R` (CompactIndex only): the
-    ADC top-R re-ranked by the exact cosine of the kept projected rows."""
+    ADC top-R re-ranked by the exact cosine of the kept projected rows.  `expand`: a pvsim.expand.QueryExpansion; the list is
+    then the ranking of the expanded query (dict or DeviceIndex; a dict is uploaded for the call)."""
     all_vectors, all_paths, resident = _vectors_and_paths(dataset)
+    _no_compact_expansion(all_vectors, expand)
     query_vector = encoder.encode(uploaded_image)
     if query_vector.ndim == 1:
         query_vector = query_vector.reshape(1, -1)
@@ -88,7 +119,39 @@ def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.nda
     else:
         if rerank:
             raise ValueError("rerank= applies to a CompactIndex only")
-        idx, val = _rank(query_vector[:1], all_vectors, k, getattr(encoder, "context", None), resident)
+        idx, val = _rank_maybe_expanded(query_vector[:1], all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
+    return [(all_paths[i], s) for i, s in zip(idx[0], val[0])]
+
+
+def expand_verified(uploaded_image: np.ndarray, ranked, index, encoder, k: int = 5, qe=None,
+                    min_inliers: int = 4) -> list[tuple[str, float]]:
+    """Query expansion over spatially verified results (Chum et al., ICCV 2007): `ranked` is what `rerank_spatial` returned,
+    [(image_path, similarity, inliers)]; its first `qe.n` entries with at least `min_inliers` inliers are folded into the query
+    (pvsim.expand.QueryExpansion; the default is average expansion over 10), and the k best entries of `index` (a dict or a
+    DeviceIndex) for the expanded query come back as [(image_path, similarity)].  With no verified entry there is nothing to
+    expand with: the first k of `ranked`, without the inlier counts."""
+    from .expand import QueryExpansion
+    qe = QueryExpansion() if qe is None else qe
+    if not isinstance(qe, QueryExpansion):
+        raise TypeError("qe must be a pvsim.expand.QueryExpansion")
+    if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or min_inliers < 0:
+        raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers!r}")
+    if isinstance(k, bool) or int(k) != k or k < 0:
+        raise ValueError(f"k must be a non-negative integer, got {k!r}")
+    all_vectors, all_paths, resident = _vectors_and_paths(index)
+    _no_compact_expansion(all_vectors, qe)
+    ranked = list(ranked)
+    verified = [path for path, _, inliers in ranked if inliers >= min_inliers][:qe.n]
+    kk = min(int(k), len(all_paths))
+    if not verified or kk == 0:
+        return [(path, sim) for path, sim, _ in ranked[:k]]
+    pos = resident._pos if resident is not None else {p: i for i, p in enumerate(all_paths)}
+    members = np.full((1, min(qe.n, len(all_paths))), -1, np.int64)
+    members[0, :len(verified)] = [pos[p] for p in verified]
+    query_vector = encoder.encode(uploaded_image)
+    if query_vector.ndim == 1:
+        query_vector = query_vector.reshape(1, -1)
+    idx, val = _rank_expanded(query_vector[:1], all_vectors, all_paths, kk, getattr(encoder, "context", None), resident, qe, members)
     return [(all_paths[i], s) for i, s in zip(idx[0], val[0])]
 
 
@@ -114,12 +177,14 @@ def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: i
 
 
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-              path_labels_dict: dict[str, int], encoder, k: int = None) -> float:
-    """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95)."""
+              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None) -> float:
+    """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95).  `expand`: rank the
+    expanded queries (pvsim.expand.QueryExpansion)."""
     all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
+    _no_compact_expansion(all_vectors, expand)
     labels = list(image_labels)
     q = _first_rows(encoder, images)
-    idx, _ = _rank(q, all_vectors, k, getattr(encoder, "context", None), resident)
+    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
     db_labels = [path_labels_dict[p] for p in all_paths]
     aps = []
     for row, true_label in zip(idx, labels):
@@ -133,13 +198,15 @@ def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encodin
 
 
 def top_k_accuracy(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-                   path_labels_dict: dict[str, int], encoder, k: int) -> float:
-    """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145)."""
+                   path_labels_dict: dict[str, int], encoder, k: int, expand=None) -> float:
+    """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145).  `expand`: rank the
+    expanded queries (pvsim.expand.QueryExpansion)."""
     all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
+    _no_compact_expansion(all_vectors, expand)
     images = list(images)
     labels = list(image_labels)
     q = _first_rows(encoder, images)
-    idx, _ = _rank(q, all_vectors, k, getattr(encoder, "context", None), resident)
+    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
     db_labels = [path_labels_dict[p] for p in all_paths]
     correct = sum(1 for row, true_label in zip(idx, labels) if any(db_labels[i] == true_label for i in row))
     return float(correct / len(images))

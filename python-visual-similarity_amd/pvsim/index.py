@@ -54,7 +54,9 @@ class DeviceIndex(Mapping):
     passed wherever `eval.retrieve_top_k_similar` / `top_k_map` / `top_k_accuracy` take `dataset` / `encoding_map`; they then
     rank against the resident copy (pvs_cosine_topk_dev / pvs_cosine_topk_filtered_dev / pvs_cosine_topk_f64_dev: the same lists
     and scores, bit for bit, as with the dict).  dtype rule of the reference (pyvisim/_utils.py:312-330): float32 scores iff the
-    database AND the queries are float32, float64 otherwise."""
+    database AND the queries are float32, float64 otherwise.
+    `rank_expanded` re-queries with the first results folded into the query, and `augmented` builds the index whose rows have their
+    neighbours folded in (pvsim/expand.py); both sum whole rows on the device."""
 
     def __init__(self, encoding_map, ctx=None):
         from .engine import default_context
@@ -64,12 +66,28 @@ class DeviceIndex(Mapping):
         if mat.ndim != 2:
             raise ValueError("DeviceIndex needs one vector of the same length per entry")
         self._host = np.ascontiguousarray(mat, dtype=np.float32 if mat.dtype == np.float32 else np.float64)
-        self._pos = {p: i for i, p in enumerate(self._paths)}
         n, L = self._host.shape
         self._db = self.ctx.buffer(max(self._host.nbytes, 16))
-        self._inv = self.ctx.buffer(max(n, 1) * self._host.itemsize)
         if n and L:
             self._db.upload(self._host)
+        self._finish()
+
+    @classmethod
+    def _from_device(cls, paths, d_rows, n, L, dtype, ctx) -> "DeviceIndex":
+        """An index over rows that are already on the device (`d_rows`, a DeviceBuffer the index takes over): downloads the host copy
+        the Mapping serves and computes the norms with the kernel every index uses."""
+        self = cls.__new__(cls)
+        self.ctx, self._paths, self._db = ctx, list(paths), d_rows
+        self._host = d_rows.download((n, L), dtype) if n and L else np.zeros((n, L), dtype)
+        self._finish()
+        return self
+
+    def _finish(self):
+        n, L = self._host.shape
+        self._pos = {p: i for i, p in enumerate(self._paths)}
+        self._inv = self.ctx.buffer(max(n, 1) * self._host.itemsize)
+        self._inv_host = None
+        if n and L:
             if self._host.dtype == np.float32:
                 self.ctx.row_inv_norms_dev(self._db.ptr, n, L, self._inv.ptr)
             else:
@@ -90,36 +108,165 @@ class DeviceIndex(Mapping):
         """(N, L) host copy in index order (= np.array(list(d.values())))."""
         return self._host
 
+    @property
+    def inv_norms(self) -> np.ndarray:
+        """(N,) host copy of the device's 1 / ||row||, in the index's dtype (downloaded once)."""
+        if self._inv_host is None:
+            n, L = self._host.shape
+            self._inv_host = self._inv.download((n,), self._host.dtype) if n and L else np.zeros(n, self._host.dtype)
+        return self._inv_host
+
+    def _rank_dev(self, d_q: int, nq: int, k: int, want_inv: bool = False):
+        """`rank` of nq rows of the index's dtype that are on the device (raw pointer) -> (idx, val[, 1 / ||q|| (nq,)])."""
+        n, L = self._host.shape
+        dt = self._host.dtype
+        isz = dt.itemsize
+        d_invq = self.ctx.buffer(max(nq, 1) * isz)
+        d_idx = self.ctx.buffer(nq * k * 8)
+        d_val = self.ctx.buffer(nq * k * isz)
+        try:
+            if dt == np.float32:
+                self.ctx.row_inv_norms_dev(d_q, nq, L, d_invq.ptr)
+                if nq >= 512:     # as the host entry point: the filtered retrieval gives the same lists faster, and declines what does not qualify
+                    self.ctx.cosine_topk_filtered_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
+                else:
+                    self.ctx.cosine_topk_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), 0, False, d_idx.ptr, d_val.ptr)
+            else:
+                self.ctx.row_inv_norms_f64_dev(d_q, nq, L, d_invq.ptr)
+                self.ctx.cosine_topk_f64_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
+            out = d_idx.download((nq, k), np.int64), d_val.download((nq, k), dt)
+            return out + (d_invq.download((nq,), dt),) if want_inv else out
+        finally:
+            for b in (d_invq, d_idx, d_val):
+                b.free()
+
+    def _inv_norms_dev(self, d_q: int, nq: int) -> np.ndarray:
+        """1 / ||row|| of nq device rows of the index's dtype, by the kernel the rankings use -> host (nq,)"""
+        dt = self._host.dtype
+        d_inv = self.ctx.buffer(max(nq, 1) * dt.itemsize)
+        try:
+            (self.ctx.row_inv_norms_dev if dt == np.float32 else self.ctx.row_inv_norms_f64_dev)(d_q, nq, self._host.shape[1], d_inv.ptr)
+            return d_inv.download((nq,), dt)
+        finally:
+            d_inv.free()
+
     def rank(self, query_vecs: np.ndarray, k: int):
         """-> (idx (nq, k) int64, val (nq, k)) of the queries against the resident database; 1 <= k <= N."""
         q = np.asarray(query_vecs)
         n, L = self._host.shape
         if q.ndim != 2 or q.shape[1] != L:
             raise ValueError("query and database dimensions differ")
-        nq = q.shape[0]
         f32 = self._host.dtype == np.float32 and q.dtype == np.float32
         if not f32 and self._host.dtype == np.float32:                   # mixed dtypes: float64 scores from the host copies
             return self.ctx.cosine_topk_f64(q, self._host, int(k))
         q = np.ascontiguousarray(q, dtype=self._host.dtype)
-        isz = q.itemsize
         d_q = self.ctx.buffer(max(q.nbytes, 16)).upload(q)
-        d_invq = self.ctx.buffer(max(nq, 1) * isz)
-        d_idx = self.ctx.buffer(nq * k * 8)
-        d_val = self.ctx.buffer(nq * k * isz)
         try:
-            if f32:
-                self.ctx.row_inv_norms_dev(d_q.ptr, nq, L, d_invq.ptr)
-                if nq >= 512:     # as the host entry point: the filtered retrieval gives the same lists faster, and declines what does not qualify
-                    self.ctx.cosine_topk_filtered_dev(d_q.ptr, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
-                else:
-                    self.ctx.cosine_topk_dev(d_q.ptr, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), 0, False, d_idx.ptr, d_val.ptr)
-            else:
-                self.ctx.row_inv_norms_f64_dev(d_q.ptr, nq, L, d_invq.ptr)
-                self.ctx.cosine_topk_f64_dev(d_q.ptr, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
-            return d_idx.download((nq, k), np.int64), d_val.download((nq, k), q.dtype)
+            return self._rank_dev(d_q.ptr, q.shape[0], int(k))
         finally:
-            for b in (d_q, d_invq, d_idx, d_val):
+            d_q.free()
+
+    # ---- query expansion and database-side augmentation (pvsim/expand.py, DESIGN.md section 13)
+    def _list_weights(self, idx, val, scheme, alpha):
+        """weights of list entries `idx` with similarities `val`: expansion_weights(...) * inv_norms[idx], 0 on the -1 slots"""
+        from .expand import expansion_weights
+        inv = self.inv_norms
+        filled = idx >= 0
+        w = expansion_weights(val, scheme, alpha) * inv[np.where(filled, idx, 0)] if inv.size else np.zeros_like(val)
+        return np.ascontiguousarray(np.where(filled, w, self._host.dtype.type(0)))
+
+    def _combine(self, d_self, w_self, idx, w, d_out):
+        """pvs_combine_rows_dev of the resident rows: lists and weights go up, the rows stay where they are"""
+        n, r = idx.shape
+        N, L = self._host.shape
+        bufs = [self.ctx.buffer(max(a.nbytes, 16)) for a in (w_self, idx, w)]
+        try:
+            for b, a in zip(bufs, (w_self, idx, w)):
+                if a.size:
+                    b.upload(a)
+            self.ctx.combine_rows_dev(self._db.ptr, N, L, self._host.dtype == np.float64, d_self, bufs[0].ptr,
+                                      bufs[1].ptr if r else None, bufs[2].ptr if r else None, n, r, d_out)
+        finally:
+            for b in bufs:
                 b.free()
+
+    def rank_expanded(self, query_vecs: np.ndarray, k: int, qe, members=None, return_queries: bool = False):
+        """`rank` after query expansion `qe` (pvsim.expand.QueryExpansion): the queries are ranked, each is replaced by
+        qe.query_weight * q / |q| + sum_j w_j x_j / |x_j| over the first min(qe.n, N) entries x_j of its list (w_j from
+        expansion_weights of the list's scores), and the new rows are ranked; with qe.passes > 1 this repeats from the lists of the
+        new rows, always adding to the original query.  The sums run on the device, against the resident rows.
+        `members`: (nq, m) int64 database indices, -1 for an empty slot, that replace the first list (verified results, say); their
+        scores (only the "alpha" scheme reads them) are looked up in the complete first ranking.
+        -> (idx (nq, k), val (nq, k)), and the expanded queries (nq, L) behind them with return_queries.
+        A float64 query against a float32 index raises TypeError: expansion works in the index's dtype."""
+        from .expand import QueryExpansion
+        if not isinstance(qe, QueryExpansion):
+            raise TypeError("qe must be a pvsim.expand.QueryExpansion")
+        q = np.asarray(query_vecs)
+        N, L = self._host.shape
+        dt = self._host.dtype
+        if q.ndim != 2 or q.shape[1] != L:
+            raise ValueError("query and database dimensions differ")
+        if dt == np.float32 and q.dtype != np.float32:
+            raise TypeError("query expansion works in the index's dtype: a float32 index needs float32 queries")
+        if not 1 <= int(k) <= N:
+            raise ValueError(f"need 1 <= k <= N (k = {k}, N = {N})")
+        q = np.ascontiguousarray(q, dtype=dt)
+        nq = q.shape[0]
+        if members is not None:
+            members = np.ascontiguousarray(members, dtype=np.int64)
+            if members.ndim != 2 or members.shape[0] != nq:
+                raise ValueError("members must be an (nq, m) array of database indices")
+            if members.size and (members.min() < -1 or members.max() >= N):
+                raise ValueError("members must be database indices in [0, N), or -1 for an empty slot")
+        if nq == 0:
+            out = (np.zeros((0, int(k)), np.int64), np.zeros((0, int(k)), dt))
+            return out + (q,) if return_queries else out
+        n1 = min(qe.n, N)
+        d_q = self.ctx.buffer(q.nbytes).upload(q)
+        d_e = self.ctx.buffer(q.nbytes)
+        try:
+            if members is None:
+                idx, val, inv_q = self._rank_dev(d_q.ptr, nq, n1, want_inv=True)
+            elif qe.scheme == "alpha":                                   # the members' scores: from the complete ranking
+                full_idx, full_val, inv_q = self._rank_dev(d_q.ptr, nq, N, want_inv=True)
+                score_of = np.empty((nq, N), dt)
+                np.put_along_axis(score_of, full_idx, full_val, axis=1)
+                idx, val = members, np.take_along_axis(score_of, np.where(members >= 0, members, 0), axis=1)
+            else:
+                inv_q = self._inv_norms_dev(d_q.ptr, nq)
+                idx, val = members, np.zeros(members.shape, dt)
+            w_self = dt.type(qe.query_weight) * inv_q
+            for p in range(qe.passes):
+                self._combine(d_q.ptr, w_self, idx, self._list_weights(idx, val, qe.scheme, qe.alpha), d_e.ptr)
+                if p + 1 < qe.passes:
+                    idx, val = self._rank_dev(d_e.ptr, nq, n1)
+            out = self._rank_dev(d_e.ptr, nq, int(k))
+            return out + (d_e.download((nq, L), dt),) if return_queries else out
+        finally:
+            d_q.free(), d_e.free()
+
+    def augmented(self, r: int = 10, scheme: str = "linear", alpha: int = 3, block: int = 4096) -> "DeviceIndex":
+        """Database-side augmentation: a new DeviceIndex with the same paths in the same order, whose row i is
+        x_i / |x_i| + sum_j w_j x_j / |x_j| over the min(r, N - 1) nearest other rows of this index (w_j from expansion_weights
+        of their similarities to row i; "linear" falls from 1 to 1 / r with the rank).  Rows are ranked `block` at a time against
+        the whole index; only the lists and weights cross to the host.  This index is left as it is."""
+        from .expand import _check_count, _check_scheme, drop_self
+        _check_count("r", r)
+        _check_count("block", block)
+        _check_scheme(scheme, alpha)
+        N, L = self._host.shape
+        dt = self._host.dtype
+        d_new = self.ctx.buffer(max(N * L * dt.itemsize, 16))
+        if N and L:
+            kk = min(int(r), N - 1) + 1
+            inv = self.inv_norms
+            for b0 in range(0, N, int(block)):
+                b1 = min(N, b0 + int(block))
+                d_rows = self._db.ptr + b0 * L * dt.itemsize
+                idx, val = drop_self(*self._rank_dev(d_rows, b1 - b0, kk), np.arange(b0, b1))
+                self._combine(d_rows, inv[b0:b1], idx, self._list_weights(idx, val, scheme, alpha), d_new.ptr + b0 * L * dt.itemsize)
+        return DeviceIndex._from_device(self._paths, d_new, N, L, dt, self.ctx)
 
     def close(self):
         for b in (self._db, self._inv):
