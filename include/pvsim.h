@@ -446,6 +446,41 @@ int pvs_pq_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t nq, int m, in
 int pvs_rescore_rows_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_X, int64_t N, int64_t d, const float* d_inv_q,
                          const float* d_inv_db, const int64_t* d_cand /*[nq][R]*/, int64_t R, float* d_val /*[nq][R]*/);
 
+/* ---------------------------------------------------------------- inverted lists for the compact index
+ * IVFADC (Jegou, Douze, Schmid, PAMI 2011) for an inner-product score: a coarse quantiser cuts the database into nlist inverted
+ * lists, a row is product-quantised as its residual to its list's centroid, and a query scans only its nprobe best lists.
+ * q . x ~ q . c_l + q . r: the table of a query is the one of section 12 against the residual codebooks and does not depend on
+ * the list; the list adds one scalar.  Arithmetic as above: float32, separate roundings, the stated order.
+ *   coarse quantiser  centroids C float32 [nlist][d], 1 <= nlist <= 65536.
+ *   assignment  the list of row x is the l that minimises acc_l; acc_l starts at +0 and, for t ascending,
+ *               acc_l = acc_l + (x[t] - C[l][t])^2.  Ties go to the lowest l (the encode rule with m = 1, without its ksub limit).
+ *   residual    r[t] = x[t] - C[l][t], one subtraction.  Codes are the section 12 codes of r.
+ *   storage     rows sorted by (list, original index): list_off int64 [nlist + 1], ids int32 [N] (N < 2^31), codes uint8 [N][m] and
+ *               inv_db float32 [N] in stored order (1/||x|| of the unquantised row).  Empty lists are legal.
+ *   coarse term coarse[q][l] starts at +0 and adds q[t] * C[l][t] for t ascending.
+ *   probes      the first nprobe entries of the ranking of coarse[q][.] by (value descending, l ascending): pvs_topk_dev on that
+ *               panel.  1 <= nprobe <= min(nlist, 1024).
+ *   score       of stored row i of probed list l: sum starts at coarse[q][l] and adds lut[q][s][code[i][s]] for s ascending;
+ *               score = (sum * inv_q[q]) * inv_db[i].  A NULL inv_* pointer means 1.
+ *   ranking     over the union of the probed lists, by (score descending, ORIGINAL index ascending), NaN last; when the probed
+ *               lists hold fewer than k rows the remaining slots are idx = -1, val = -inf.  1 <= k <= 1024.
+ * n == 0 and nq == 0 are no-ops.  The entry points enqueue on the context's stream and do not wait for it. */
+/* d_x float32 [n][d] -> d_list int32 [n] and, unless NULL, d_residual float32 [n][d] (may not overlap d_x).  d <= 16384. */
+int pvs_ivf_assign_dev(pvs_ctx* ctx, const float* d_x, int64_t n, int d, const float* d_centroids /*[nlist][d]*/, int nlist,
+                       int32_t* d_list, float* d_residual);
+/* d_q float32 [nq][d] -> d_coarse float32 [nq][nlist] */
+int pvs_ivf_coarse_dev(pvs_ctx* ctx, const float* d_q, int64_t nq, int d, const float* d_centroids /*[nlist][d]*/, int nlist,
+                       float* d_coarse);
+/* d_probe int64 [nq][nprobe] and d_probe_val float32 [nq][nprobe] are the lists pvs_topk_dev gave for the coarse panel (a probe
+ * outside [0, nlist) counts as an empty list).  h_list_off is a HOST copy of d_list_off: all sizing is done from it, so nothing
+ * inside the call waits for the device; the two must agree.  Scores pass through a bounded workspace of candidate rows into the
+ * top-k kernels.  d_idx int64 [nq][k], d_val float32 [nq][k].  Every code must be < ksub and the ids of the probed rows distinct
+ * (preconditions: not checked). */
+int pvs_ivf_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t nq, int m, int ksub, const int64_t* d_probe,
+                          const float* d_probe_val, int nprobe, const int64_t* d_list_off, const int64_t* h_list_off, int nlist,
+                          const uint8_t* d_codes, const int32_t* d_ids, const float* d_inv_q, const float* d_inv_db, int k,
+                          int64_t* d_idx, float* d_val);
+
 /* ---------------------------------------------------------------- query expansion, database-side augmentation
  * Chum et al. (ICCV 2007), Arandjelovic & Zisserman (CVPR 2012), Radenovic et al. (PAMI 2018): the query, or every database row, is
  * replaced by a weighted sum of itself and the rows its first ranking found.  The device's part is that sum over whole rows, gathered

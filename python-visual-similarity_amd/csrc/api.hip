@@ -18,7 +18,7 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-static_assert(WS_VERIFY_SMALL + 1 == pvs_ctx::NWS, "one block per WsSlot");
+static_assert(WS_IVF_CANDIDATES + 1 == pvs_ctx::NWS, "one block per WsSlot");
 
 int ws_reserve(pvs_ctx* ctx, WsSlot which, size_t bytes, void** out) {
   if (bytes == 0) bytes = 16;

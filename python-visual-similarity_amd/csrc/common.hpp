@@ -60,7 +60,7 @@ struct pvs_ctx {
   bool owns_stream = false;
   int num_cu = 256;
   // grow-only scratch areas (device), one per pvs::WsSlot: who reserves which, and when a pointer into one dies, is the table in workspace.hpp
-  static constexpr int NWS = 16;
+  static constexpr int NWS = 17;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
   // cached tile lists of the similarity GEMM, one per GEMM model (cosine.hip): a context is one device + one stream, so the
@@ -253,6 +253,8 @@ int launch_topk(pvs_ctx* ctx, const float* scores, int64_t nq, int64_t ncols, in
                 int64_t col_offset, int merge, int64_t* d_idx, float* d_val);
 int launch_topk_merge(pvs_ctx* ctx, const int64_t* idx_lists, const float* val_lists, int n_lists, int64_t nq,
                       int k, int64_t* d_idx, float* d_val);
+int launch_topk_candidates(pvs_ctx* ctx, const int32_t* ids, const float* vals, int64_t nq, int64_t len, int k, int64_t* d_idx,
+                           float* d_val);
 int launch_rank_f64(pvs_ctx* ctx, const double* scores, int64_t nq, int64_t ncols, int64_t ld, int k, int64_t* d_idx, double* d_val);
 int launch_pca(pvs_ctx* ctx, const pvs_pca* p, const void* d_desc, int kind, int64_t total, float* d_out);
 int launch_gmm_posterior(pvs_ctx* ctx, const pvs_gmm* g, const void* d_desc, int kind, int ld, int64_t total,

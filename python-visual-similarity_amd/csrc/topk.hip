@@ -36,13 +36,15 @@ __device__ __forceinline__ uint64_t make_key(float v, uint32_t idx) {
 }
 
 struct TopkArgs {
-  const float* scores;      // panel mode: [nq][ld];   list mode: val lists [n_lists][nq][k]
-  const int64_t* idx_lists; // list mode only: [n_lists][nq][k]
+  const float* scores;      // panel mode: [nq][ld];   list mode: val lists [n_lists][nq][list_len]
+  const int64_t* idx_lists; // list mode only: [n_lists][nq][list_len]
+  const int32_t* id32_lists; // list mode: the indices as int32 instead (idx_lists is then NULL)
   int64_t nq, ncols, ld;
   int k;
   int64_t col_offset;
   int merge;
-  int n_lists;              // > 0 selects list mode (ncols = n_lists * k)
+  int n_lists;              // > 0 selects list mode (ncols = n_lists * list_len)
+  int64_t list_len;         // list mode: entries per input list (k for merged top-k lists; candidate rows may be longer than k)
   int64_t* idx;             // [nq][out_ld]; this launch writes columns [out_off, out_off + k)
   float* val;
   int64_t out_ld;
@@ -110,9 +112,9 @@ __global__ __launch_bounds__(TK_THREADS) void topk_kernel(TopkArgs a) {
       key[it] = 0ull;
       if (c < a.ncols) {
         if (a.n_lists > 0) {
-          const int64_t l = c / k, r = c - l * k;
-          const int64_t off = (l * a.nq + q) * k + r;
-          const int64_t id = a.idx_lists[off];
+          const int64_t l = c / a.list_len, r = c - l * a.list_len;
+          const int64_t off = (l * a.nq + q) * a.list_len + r;
+          const int64_t id = a.idx_lists ? a.idx_lists[off] : (int64_t)a.id32_lists[off];
           if (id >= 0) { key[it] = make_key(a.scores[off], (uint32_t)id); ++nvalid; }
         } else {
           const uint64_t kk = make_key(a.scores[q * a.ld + c], (uint32_t)(a.col_offset + c));
@@ -476,14 +478,14 @@ static int launch_topk_impl(pvs_ctx* ctx, const TopkArgs& a) {
 int launch_topk(pvs_ctx* ctx, const float* scores, int64_t nq, int64_t ncols, int64_t ld, int k, int64_t col_offset,
                 int merge, int64_t* d_idx, float* d_val) {
   if (k <= TK_KMAX) {
-    TopkArgs a{scores, nullptr, nq, ncols, ld, k, col_offset, merge, 0, d_idx, d_val, k, 0};
+    TopkArgs a{scores, nullptr, nullptr, nq, ncols, ld, k, col_offset, merge, 0, 0, d_idx, d_val, k, 0};
     return launch_topk_impl(ctx, a);
   }
   // deep ranking (e.g. top_k_map(k=None) = full argsort): pages of TK_KMAX, each page selects the best keys that
   // are strictly worse than the previous page's last key.  Needs the whole score row in this panel.
   if (merge) PVS_FAIL(PVS_ERR_UNSUPPORTED, "top-k deeper than %d cannot merge across panels", TK_KMAX);
   for (int off = 0; off < k; off += TK_KMAX) {
-    TopkArgs a{scores, nullptr, nq, ncols, ld, std::min(TK_KMAX, k - off), col_offset, 0, 0, d_idx, d_val, k, off};
+    TopkArgs a{scores, nullptr, nullptr, nq, ncols, ld, std::min(TK_KMAX, k - off), col_offset, 0, 0, 0, d_idx, d_val, k, off};
     PVS_TRY(launch_topk_impl(ctx, a));
   }
   return PVS_OK;
@@ -493,7 +495,16 @@ int launch_topk_merge(pvs_ctx* ctx, const int64_t* idx_lists, const float* val_l
                       int64_t* d_idx, float* d_val) {
   if (n_lists < 1) PVS_FAIL(PVS_ERR_INVALID, "top-k merge: n_lists must be >= 1");
   if (k > TK_KMAX) PVS_FAIL(PVS_ERR_UNSUPPORTED, "top-k merge: k must be <= %d", TK_KMAX);
-  TopkArgs a{val_lists, idx_lists, nq, (int64_t)n_lists * k, 0, k, 0, 0, n_lists, d_idx, d_val, k, 0};
+  TopkArgs a{val_lists, idx_lists, nullptr, nq, (int64_t)n_lists * k, 0, k, 0, 0, n_lists, k, d_idx, d_val, k, 0};
+  return launch_topk_impl(ctx, a);
+}
+
+// One candidate row per query, longer than k: the best k of vals[nq][len] / ids[nq][len] under (value descending, id ascending),
+// entries with id < 0 skipped, unfilled output slots -1 / -inf.  Ids must be distinct within a row (ivf.hip: the probed scan).
+int launch_topk_candidates(pvs_ctx* ctx, const int32_t* ids, const float* vals, int64_t nq, int64_t len, int k, int64_t* d_idx,
+                           float* d_val) {
+  if (k > TK_KMAX) PVS_FAIL(PVS_ERR_UNSUPPORTED, "top-k of candidate rows: k must be <= %d", TK_KMAX);
+  TopkArgs a{vals, nullptr, ids, nq, len, 0, k, 0, 0, 1, len, d_idx, d_val, k, 0};
   return launch_topk_impl(ctx, a);
 }
 

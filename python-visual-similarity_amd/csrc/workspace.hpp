@@ -8,7 +8,7 @@ struct pvs_ctx;
 
 namespace pvs {
 
-// A context keeps 16 grow-only blocks of device memory (pvs_ctx::ws).  ws_reserve(ctx, slot, bytes, &p) hands out the slot's block,
+// A context keeps 17 grow-only blocks of device memory (pvs_ctx::ws).  ws_reserve(ctx, slot, bytes, &p) hands out the slot's block,
 // and when the block is too small it waits for the stream, FREES the block and allocates a larger one.  Hence the rule:
 //
 //   A pointer into a slot is dead once anything that may reserve the same slot has been called; re-reserve after such a call.
@@ -36,10 +36,11 @@ namespace pvs {
 //   WS_SIFT_PYRAMID, WS_SIFT_TABLES, WS_SIFT_KEYPOINTS    sift.hip: pvs_sift_dev
 //   WS_MATCH_TABLE    match.hip: upload_pairs, pvs_match_u8_dev
 //   WS_VERIFY_POINTS, WS_VERIFY_SMALL    match.hip: pvs_verify_dev
+//   WS_IVF_CANDIDATES ivf.hip: pvs_ivf_scan_topk_dev (candidate scores | candidate ids of one query block)
 enum WsSlot : int {
   WS_STAGE_IN = 0, WS_SCRATCH = 1, WS_PANEL_OUT = 2, WS_PROJECTED = 3, WS_AUX_ROWS = 4, WS_FP16_ROWS = 5, WS_LISTS = 6, WS_NB_NORMS = 7,
   WS_NB_F64_ROWS = 8, WS_DSIFT_TABLE = 9, WS_SIFT_PYRAMID = 10, WS_SIFT_TABLES = 11, WS_SIFT_KEYPOINTS = 12, WS_MATCH_TABLE = 13,
-  WS_VERIFY_POINTS = 14, WS_VERIFY_SMALL = 15
+  WS_VERIFY_POINTS = 14, WS_VERIFY_SMALL = 15, WS_IVF_CANDIDATES = 16
 };
 
 int ws_reserve(pvs_ctx* ctx, WsSlot which, size_t bytes, void** out);   // api.hip
@@ -139,6 +140,17 @@ inline SiftCandLayout<Cand, Kp> sift_cand_layout(size_t n_cand, size_t max_peaks
   WsLayout<16> l;
   return {l.add<Cand>(n_cand), l.add<Kp>(n_cand), l.add<int>(n_cand + 1), l.add<int>(n_cand + 1), l.add<int>(n_cand + 1),
           l.add<float>(n_cand * max_peaks), l.bytes()};
+}
+
+// pvs_ivf_scan_topk_dev, WS_IVF_CANDIDATES: one query block's candidate rows, QB queries x W slots each
+struct IvfCandLayout {
+  WsPiece<float> val;
+  WsPiece<int32_t> id;
+  size_t bytes;
+};
+inline IvfCandLayout ivf_cand_layout(size_t QB, size_t W) {
+  WsLayout<> l;
+  return {l.add<float>(QB * W), l.add<int32_t>(QB * W), l.bytes()};
 }
 
 }  // namespace pvs

@@ -5,6 +5,7 @@
     from pvsim import eval                     # retrieve_top_k_similar, top_k_map, top_k_accuracy, rerank_spatial, expand_verified
     from pvsim import verify                   # LocalFeatureIndex, SpatialVerifier, match (spatial re-ranking)
     from pvsim import CompactIndex, ProductQuantizer   # product-quantised index, ADC search (m + 4 bytes per image)
+    from pvsim import IVFCompactIndex                  # the same cut into inverted lists: a query scans nprobe of nlist lists
     from pvsim import QueryExpansion                   # query expansion / database-side augmentation on a DeviceIndex
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
@@ -14,9 +15,9 @@ fallback.  Importing the package does not touch the GPU; the first computation d
 from .engine import Context, default_context, pack_descriptors
 from . import models
 from ._errors import CapacityError
-from .compact import CompactIndex, ProductQuantizer
+from .compact import CompactIndex, IVFCompactIndex, ProductQuantizer
 from .expand import QueryExpansion
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "ProductQuantizer", "QueryExpansion"]
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion"]

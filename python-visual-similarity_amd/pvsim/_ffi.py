@@ -124,6 +124,9 @@ SIGNATURES = {
     "pvs_pq_lut_dev": [_vp, _vp, _vp, _i64, _vp],
     "pvs_pq_scan_topk_dev": [_vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _vp, _int, _i64, _int, _vp, _vp],
     "pvs_rescore_rows_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp],
+    "pvs_ivf_assign_dev": [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp],
+    "pvs_ivf_coarse_dev": [_vp, _vp, _i64, _int, _vp, _int, _vp],
+    "pvs_ivf_scan_topk_dev": [_vp, _vp, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "pvs_combine_rows_dev": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _int, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],

@@ -10,7 +10,7 @@ import numpy as np
 
 from .models import PCAModel
 
-__all__ = ["ProductQuantizer", "CompactIndex", "fit_projection", "save_arrays", "load_arrays"]
+__all__ = ["ProductQuantizer", "CompactIndex", "IVFCompactIndex", "fit_projection", "save_arrays", "load_arrays"]
 
 _MAX_PROJECTION_TRAIN = 4096
 _CHUNK_ROWS = 8192
@@ -227,24 +227,31 @@ class ProductQuantizer:
 
 
 # ------------------------------------------------------------------------------------------------ persistence (no device needed)
-def save_arrays(path: str, paths, codes, inv_norms, codebooks, projection=None, projected=None) -> None:
-    """One plain .npz of arrays (numpy.load(allow_pickle=False)), in the style of pvsim.index."""
-    arrays = dict(kind="compact_index", paths=np.array(list(paths), dtype=np.str_), codes=np.ascontiguousarray(codes, dtype=np.uint8),
+_KINDS = {"compact_index": "compact index", "ivf_compact_index": "IVF compact index"}
+
+
+def save_arrays(path: str, paths, codes, inv_norms, codebooks, projection=None, projected=None, kind: str = "compact_index",
+                **more) -> None:
+    """One plain .npz of arrays (numpy.load(allow_pickle=False)), in the style of pvsim.index.  `more`: further arrays of the kind
+    (an IVF index adds centroids, list_off and ids)."""
+    arrays = dict(kind=kind, paths=np.array(list(paths), dtype=np.str_), codes=np.ascontiguousarray(codes, dtype=np.uint8),
                   inv_norms=np.ascontiguousarray(inv_norms, dtype=np.float32), codebooks=np.ascontiguousarray(codebooks, dtype=np.float32))
     if projection is not None:
         arrays["projection"] = np.ascontiguousarray(projection, dtype=np.float32)
     if projected is not None:
         arrays["projected"] = np.ascontiguousarray(projected, dtype=np.float32)
+    arrays.update(more)
     np.savez(path, **arrays)
 
 
-def load_arrays(path: str) -> dict:
+def load_arrays(path: str, kind: str = "compact_index", more=()) -> dict:
     with np.load(path if path.endswith(".npz") else path + ".npz", allow_pickle=False) as z:
-        if "kind" not in z.files or str(z["kind"]) != "compact_index":
-            raise ValueError(f"{path}: not a compact index file")
+        if "kind" not in z.files or str(z["kind"]) != kind:
+            raise ValueError(f"{path}: not a{'n' if kind[0] in 'aeiou' else ''} {_KINDS[kind]} file")
         out = dict(paths=[str(p) for p in z["paths"]], codes=z["codes"], inv_norms=z["inv_norms"], codebooks=z["codebooks"],
                    projection=z["projection"] if "projection" in z.files else None,
                    projected=z["projected"] if "projected" in z.files else None)
+        out.update({name: z[name] for name in more})
     return out
 
 
@@ -292,6 +299,12 @@ class CompactIndex:
         """Train the projection and the quantiser on `train` (default: the database itself), project the database, record
         1/||projected row||, encode, and keep codes, norms and paths on the device.  `source` is an encoding map {path: vector}
         or a DeviceIndex (whose resident rows are read in place)."""
+        return cls._fit(source, m, n_components, projection, ksub, keep_projected, random_state, train, ctx, max_iter)
+
+    @classmethod
+    def _fit(cls, source, m, n_components, projection, ksub, keep_projected, random_state, train, ctx, max_iter, nlist=None):
+        """fit(); with `nlist` the rows are assigned to nlist coarse centroids (k-means on the projected training rows) and the
+        quantiser is trained on, and encodes, their residuals (IVFCompactIndex)."""
         from .engine import default_context
         from .index import DeviceIndex
         resident = source if isinstance(source, DeviceIndex) else None
@@ -315,6 +328,8 @@ class CompactIndex:
             raise ValueError(f"d={d} is not a multiple of m={pq.m} (d % m must be 0)")
         if tr.shape[0] < pq.ksub:
             raise ValueError(f"n={tr.shape[0]} training rows are fewer than ksub={pq.ksub} codewords (need n >= ksub)")
+        if nlist is not None:
+            nlist = _check_nlist(nlist, tr.shape[0], n)
         ctx = ctx or default_context()
         pq._ctx = ctx
         from .engine import DeviceBuffer
@@ -355,7 +370,24 @@ class CompactIndex:
             for r0, rn, buf in project_chunks(tr, db_ptr if train is None else None):
                 ytr[r0:r0 + rn] = buf.download((rn, d), np.float32)
                 give(buf)
-            pq.fit(ytr, random_state=random_state, max_iter=max_iter)
+            d_cent = d_lists = d_res = None
+            if nlist is None:
+                pq.fit(ytr, random_state=random_state, max_iter=max_iter)
+            else:                                    # coarse centroids, then the quantiser on the training rows' residuals
+                from .learn import _rng
+                rng = _rng(random_state)
+                cent = _fit_coarse(ctx, ytr, nlist, rng, max_iter)
+                d_cent = take(cent.nbytes).upload(cent)
+                res = np.empty_like(ytr)
+                for r0 in range(0, ytr.shape[0], _CHUNK_ROWS):
+                    rn = min(_CHUNK_ROWS, ytr.shape[0] - r0)
+                    d_y, d_l, d_r = take(rn * d * 4).upload(ytr[r0:r0 + rn]), take(rn * 4), take(rn * d * 4)
+                    ctx.ivf_assign_dev(d_y.ptr, rn, d, d_cent.ptr, nlist, d_l.ptr, d_r.ptr)
+                    res[r0:r0 + rn] = d_r.download((rn, d), np.float32)
+                    give(d_y), give(d_l), give(d_r)
+                pq.fit(res, random_state=rng, max_iter=max_iter)
+                del res
+                d_lists, d_res = take(n * 4), take(min(n, _CHUNK_ROWS) * d * 4)
             table = pq.table()
             d_codes, d_inv = take(n * pq.m), take(n * 4)
             d_proj = take(n * d * 4) if keep_projected else None
@@ -372,11 +404,24 @@ class CompactIndex:
                 chunks = project_chunks(mat, db_ptr, dest)
             for r0, rn, buf in chunks:
                 ctx.row_inv_norms_dev(buf.ptr, rn, d, d_inv.ptr + r0 * 4)
-                ctx.pq_encode_dev(table, buf.ptr, rn, d_codes.ptr + r0 * pq.m)
+                if nlist is None:
+                    ctx.pq_encode_dev(table, buf.ptr, rn, d_codes.ptr + r0 * pq.m)
+                else:
+                    ctx.ivf_assign_dev(buf.ptr, rn, d, d_cent.ptr, nlist, d_lists.ptr + r0 * 4, d_res.ptr)
+                    ctx.pq_encode_dev(table, d_res.ptr, rn, d_codes.ptr + r0 * pq.m)
                 ctx.sync()
                 give(buf)
             if d_w is not None:
                 give(d_w)
+            extra = {}
+            if nlist is not None:                    # sort into lists: by (list, original index), on the host
+                give(d_res)
+                lists = d_lists.download((n,), np.int32)
+                give(d_lists)
+                ids, list_off = _sort_into_lists(lists, nlist)
+                d_codes.upload(np.ascontiguousarray(d_codes.download((n, pq.m), np.uint8)[ids]))
+                d_inv.upload(np.ascontiguousarray(d_inv.download((n,), np.float32)[ids]))
+                extra = dict(cent=d_cent, ids=take(n * 4).upload(ids), list_off=take(list_off.nbytes).upload(list_off))
         except BaseException:
             for b in live:
                 b.free()
@@ -385,7 +430,9 @@ class CompactIndex:
         self = cls.__new__(cls)
         self.quantizer, self._paths, self._ctx = pq, [str(p) for p in paths], ctx
         self._L, self._w, self._keep, self._host = L, w, bool(keep_projected), None
-        self._dev = dict(codes=d_codes, inv=d_inv, projected=d_proj, w=None)
+        self._dev = dict(codes=d_codes, inv=d_inv, projected=d_proj, w=None, **extra)
+        if nlist is not None:
+            self._centroids, self._list_off, self._ids = cent, list_off, ids
         return self
 
     # ---- device residency
@@ -469,11 +516,27 @@ class CompactIndex:
     def rank(self, query_vecs, k: int, rerank: int = 0):
         """-> (idx (nq, k) int64, val (nq, k) float32): the ADC ranking (score descending, index ascending); with rerank=R >= k
         the ADC top-R re-scored exactly against the kept projected rows and ordered by (exact score descending, index ascending)."""
+        return self._rank(query_vecs, k, rerank)
+
+    def _scan(self, ctx, dev, buf, d_y, d_invq, d_lut, nq, kk, d_idx, d_val):
+        """the ADC lists of nq projected queries (rows d_y, tables d_lut) into d_idx / d_val (nq, kk); `buf` takes scratch buffers"""
+        n, pq = len(self), self.quantizer
+        ctx.pq_scan_topk_dev(d_lut.ptr, nq, pq.m, pq.ksub, dev["codes"].ptr, n, d_invq.ptr, dev["inv"].ptr, kk, 0, False,
+                             d_idx.ptr, d_val.ptr)
+
+    def _check_rank_args(self, k, rerank):
+        return _check_rank_args(k, rerank, len(self), self._keep)
+
+    def _rescore_norms(self, dev):
+        """1/||row|| indexed like the kept projected rows (by original index)"""
+        return dev["inv"]
+
+    def _rank(self, query_vecs, k, rerank, **scan_args):
         q = _f32_rows(query_vecs, "query")
         if q.shape[1] != self.input_dim:
             raise ValueError(f"query and database dimensions differ: {q.shape[1]} vs {self.input_dim}")
         n, pq = len(self), self.quantizer
-        k, rerank = _check_rank_args(k, rerank, n, self._keep)
+        k, rerank = self._check_rank_args(k, rerank, **scan_args)
         nq, d, kk = q.shape[0], pq.d, rerank or k
         if nq == 0:
             return np.zeros((0, k), np.int64), np.zeros((0, k), np.float32)
@@ -495,12 +558,12 @@ class CompactIndex:
             d_idx, d_val = buf(nq * kk * 8), buf(nq * kk * 4)
             ctx.row_inv_norms_dev(d_y.ptr, nq, d, d_invq.ptr)
             ctx.pq_lut_dev(pq.table(), d_y.ptr, nq, d_lut.ptr)
-            ctx.pq_scan_topk_dev(d_lut.ptr, nq, pq.m, pq.ksub, dev["codes"].ptr, n, d_invq.ptr, dev["inv"].ptr, kk, 0, False,
-                                 d_idx.ptr, d_val.ptr)
+            self._scan(ctx, dev, buf, d_y, d_invq, d_lut, nq, kk, d_idx, d_val, **scan_args)
             if not rerank:
                 return d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
             d_exact = buf(nq * kk * 4)
-            ctx.rescore_rows_dev(d_y.ptr, nq, dev["projected"].ptr, n, d, d_invq.ptr, dev["inv"].ptr, d_idx.ptr, kk, d_exact.ptr)
+            ctx.rescore_rows_dev(d_y.ptr, nq, dev["projected"].ptr, n, d, d_invq.ptr, self._rescore_norms(dev).ptr, d_idx.ptr, kk,
+                                 d_exact.ptr)
             idx, val = d_idx.download((nq, kk), np.int64), d_exact.download((nq, kk), np.float32)
         finally:
             for b in bufs:
@@ -537,3 +600,162 @@ def order_exact(idx: np.ndarray, val: np.ndarray, k: int):
         o = np.lexsort((idx[r], -key, nan))[:k]
         out_i[r], out_v[r] = idx[r][o], val[r][o]
     return out_i, out_v
+
+
+# ------------------------------------------------------------------------------------------------ inverted lists
+MAX_NPROBE = 1024
+MAX_IVF_K = 1024
+MAX_NLIST = 65536
+
+
+def _check_nlist(nlist, n_train: int, n: int) -> int:
+    if isinstance(nlist, bool) or int(nlist) != nlist or not 1 <= nlist <= MAX_NLIST:
+        raise ValueError(f"nlist must be an integer between 1 and {MAX_NLIST}, got {nlist!r}")
+    if n_train < nlist:
+        raise ValueError(f"n={n_train} training rows are fewer than nlist={nlist} coarse centroids (need n >= nlist)")
+    if n >= 2 ** 31:
+        raise ValueError(f"an IVF compact index holds fewer than 2^31 rows, got {n}")
+    return int(nlist)
+
+
+def _fit_coarse(ctx, rows: np.ndarray, nlist: int, rng, max_iter: int) -> np.ndarray:
+    """coarse centroids float32 (nlist, d): learn.fit_kmeans on the projected training rows"""
+    import warnings
+    from .learn import DeviceRows, fit_kmeans
+    dev = DeviceRows.from_host(ctx, rows)
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)             # duplicate rows: fewer distinct centroids, some lists stay empty
+            return np.ascontiguousarray(fit_kmeans(dev, nlist, random_state=rng, max_iter=max_iter).cluster_centers_, dtype=np.float32)
+    finally:
+        dev.free()
+
+
+def _sort_into_lists(lists: np.ndarray, nlist: int):
+    """list of every row -> (ids int32 (N,): the original index of each stored row, rows sorted by (list, original index);
+    list_off int64 (nlist + 1,))"""
+    lists = np.asarray(lists)
+    if lists.size and (int(lists.min()) < 0 or int(lists.max()) >= nlist):
+        raise ValueError(f"a list number lies outside [0, {nlist})")
+    ids = np.argsort(lists, kind="stable").astype(np.int32)
+    list_off = np.zeros(nlist + 1, np.int64)
+    np.cumsum(np.bincount(lists, minlength=nlist), out=list_off[1:])
+    return ids, list_off
+
+
+class IVFCompactIndex(CompactIndex):
+    """A CompactIndex cut into `nlist` inverted lists (IVFADC; Jegou, Douze, Schmid, PAMI 2011): coarse centroids (nlist, d), the rows
+    stored sorted by (list, original index) and product-quantised as residuals to their list's centroid.  `rank` scans the
+    `nprobe` lists whose centroids score best against the query: about nprobe / nlist of the rows.
+
+    `codes` and `inv_norms` are in STORED order, `ids` (N,) int32 names the original index of each stored row (the index into
+    `paths`, and into `projected`, which stays in original order), `list_off` (nlist + 1,) int64 bounds the lists."""
+
+    def __init__(self, paths, codes, inv_norms, quantizer, centroids, list_off, ids, projection=None, projected=None, ctx=None):
+        super().__init__(paths, codes, inv_norms, quantizer, projection, projected, ctx)
+        n = len(self._paths)
+        cent = np.asarray(centroids)
+        if cent.dtype == np.float64:
+            raise TypeError("centroids are float64: the compact index is a float32 structure, pass float32 centroids")
+        if cent.dtype != np.float32 or cent.ndim != 2 or cent.shape[1] != self.quantizer.d or not 1 <= cent.shape[0] <= MAX_NLIST:
+            raise ValueError(f"centroids must be float32 (nlist, {self.quantizer.d}) with 1 <= nlist <= {MAX_NLIST}, got {cent.dtype} "
+                             f"{cent.shape}")
+        off = np.asarray(list_off)
+        if off.dtype.kind not in "iu" or off.shape != (cent.shape[0] + 1,):
+            raise ValueError(f"list_off must be ({cent.shape[0] + 1},) integers, got {off.dtype} {off.shape}")
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        if off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+            raise ValueError(f"list_off must rise from 0 to {n} without decreasing")
+        ids = np.asarray(ids)
+        if ids.dtype.kind not in "iu" or ids.shape != (n,):
+            raise ValueError(f"ids must be ({n},) integers, got {ids.dtype} {ids.shape}")
+        if n >= 2 ** 31:
+            raise ValueError(f"an IVF compact index holds fewer than 2^31 rows, got {n}")
+        if n and not np.array_equal(np.sort(ids), np.arange(n)):
+            raise ValueError(f"ids must be a permutation of 0 .. {n - 1}")
+        self._centroids, self._list_off, self._ids = np.ascontiguousarray(cent), off, np.ascontiguousarray(ids, dtype=np.int32)
+
+    @classmethod
+    def fit(cls, source, nlist: int, m: int = 64, n_components=None, projection=None, ksub: int = 256, keep_projected: bool = False,
+            random_state=None, train=None, ctx=None, max_iter: int = 25) -> "IVFCompactIndex":
+        """CompactIndex.fit with a coarse quantiser: project, train `nlist` coarse centroids on the projected training rows
+        (learn.fit_kmeans), assign the rows, train the product quantiser on the training rows' residuals, encode the residuals,
+        sort the rows into their lists, and keep everything on the device."""
+        _check_nlist(nlist, nlist, 0)                # the type and range, before anything is computed
+        return cls._fit(source, m, n_components, projection, ksub, keep_projected, random_state, train, ctx, max_iter, nlist=nlist)
+
+    # ---- device residency
+    def _device(self) -> dict:
+        fresh = self._dev is None
+        dev = super()._device()
+        if fresh:
+            ctx = self.context
+            for name, a in (("cent", self._centroids), ("ids", self._ids), ("list_off", self._list_off)):
+                dev[name] = ctx.buffer(max(a.nbytes, 16)).upload(a)
+        return dev
+
+    @property
+    def nlist(self) -> int:
+        return self._centroids.shape[0]
+
+    @property
+    def centroids(self) -> np.ndarray:
+        return self._centroids
+
+    @property
+    def list_sizes(self) -> np.ndarray:
+        """rows per inverted list, int64 (nlist,)"""
+        return np.diff(self._list_off)
+
+    @property
+    def nbytes_breakdown(self) -> dict:
+        out = super().nbytes_breakdown
+        out.update(centroids=self._centroids.nbytes, ids=len(self) * 4, list_off=self._list_off.nbytes,
+                   inv_norms_original=len(self) * 4 if self._keep else 0)
+        return out
+
+    def _rescore_norms(self, dev):
+        """the stored norms are in list order, the kept rows in original order: exact re-scoring reads a copy of the norms in
+        original order (4 bytes per row, only beside kept rows; made on the first re-ranking)"""
+        if dev.get("inv_orig") is None:
+            stored = dev["inv"].download((len(self),), np.float32)
+            orig = np.empty_like(stored)
+            orig[self._ids] = stored
+            dev["inv_orig"] = self.context.buffer(max(orig.nbytes, 16)).upload(orig)
+        return dev["inv_orig"]
+
+    # ---- search
+    def rank(self, query_vecs, k: int, nprobe: int, rerank: int = 0):
+        """-> (idx (nq, k) int64, val (nq, k) float32): the ADC ranking over the `nprobe` best lists of each query, by (score
+        descending, original index ascending); slots the probed lists cannot fill are -1 / -inf.  rerank=R >= k re-scores the
+        ADC top-R exactly against the kept projected rows; unfilled slots stay last."""
+        return self._rank(query_vecs, k, rerank, nprobe=nprobe)
+
+    def _check_rank_args(self, k, rerank, nprobe):
+        if isinstance(nprobe, bool) or nprobe is None or int(nprobe) != nprobe or not 1 <= nprobe <= min(self.nlist, MAX_NPROBE):
+            raise ValueError(f"nprobe must be an integer with 1 <= nprobe <= {min(self.nlist, MAX_NPROBE)} (min(nlist, {MAX_NPROBE})), "
+                             f"got {nprobe!r}")
+        k, rerank = _check_rank_args(k, rerank, len(self), self._keep)
+        if max(k, rerank) > MAX_IVF_K:
+            raise ValueError(f"an IVFCompactIndex ranks at most {MAX_IVF_K} entries per query (k and rerank), got k={k}, rerank={rerank}")
+        return k, rerank
+
+    def _scan(self, ctx, dev, buf, d_y, d_invq, d_lut, nq, kk, d_idx, d_val, nprobe):
+        pq, nlist, nprobe = self.quantizer, self.nlist, int(nprobe)
+        d_coarse, d_pidx, d_pval = buf(nq * nlist * 4), buf(nq * nprobe * 8), buf(nq * nprobe * 4)
+        ctx.ivf_coarse_dev(d_y.ptr, nq, pq.d, dev["cent"].ptr, nlist, d_coarse.ptr)
+        ctx.topk_dev(d_coarse.ptr, nq, nlist, nlist, nprobe, 0, False, d_pidx.ptr, d_pval.ptr)
+        ctx.ivf_scan_topk_dev(d_lut.ptr, nq, pq.m, pq.ksub, d_pidx.ptr, d_pval.ptr, nprobe, dev["list_off"].ptr, self._list_off, nlist,
+                              dev["codes"].ptr, dev["ids"].ptr, d_invq.ptr, dev["inv"].ptr, kk, d_idx.ptr, d_val.ptr)
+
+    # ---- persistence
+    def save(self, path: str) -> None:
+        codes, inv, proj = self._download()
+        save_arrays(path, self._paths, codes, inv, self.quantizer.codebooks, self._w, proj, kind="ivf_compact_index",
+                    centroids=self._centroids, list_off=self._list_off, ids=self._ids)
+
+    @classmethod
+    def load(cls, path: str, ctx=None) -> "IVFCompactIndex":
+        a = load_arrays(path, kind="ivf_compact_index", more=("centroids", "list_off", "ids"))
+        return cls(a["paths"], a["codes"], a["inv_norms"], ProductQuantizer.from_codebooks(a["codebooks"], ctx), a["centroids"],
+                   a["list_off"], a["ids"], a["projection"], a["projected"], ctx)

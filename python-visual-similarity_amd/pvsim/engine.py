@@ -440,6 +440,23 @@ class Context:
         check(_ffi.lib().pvs_rescore_rows_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, d, ptr(d_invq), ptr(d_invdb), ptr(d_cand), R,
                                               ptr(d_val)))
 
+    # inverted lists of the compact index
+    def ivf_assign_dev(self, d_x, n, d, d_centroids, nlist, d_list, d_residual):
+        check(_ffi.lib().pvs_ivf_assign_dev(self.handle, ptr(d_x), n, d, ptr(d_centroids), nlist, ptr(d_list), ptr(d_residual)))
+
+    def ivf_coarse_dev(self, d_q, nq, d, d_centroids, nlist, d_coarse):
+        check(_ffi.lib().pvs_ivf_coarse_dev(self.handle, ptr(d_q), nq, d, ptr(d_centroids), nlist, ptr(d_coarse)))
+
+    def ivf_scan_topk_dev(self, d_lut, nq, m, ksub, d_probe, d_probe_val, nprobe, d_list_off, h_list_off, nlist, d_codes, d_ids,
+                          d_invq, d_invdb, k, d_idx, d_val):
+        """h_list_off: the host copy of the list offsets, a C-contiguous int64 array of nlist + 1 entries"""
+        h = np.ascontiguousarray(h_list_off, dtype=np.int64)
+        if h.shape != (nlist + 1,):
+            raise ValueError(f"h_list_off must have nlist + 1 = {nlist + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_ivf_scan_topk_dev(self.handle, ptr(d_lut), nq, m, ksub, ptr(d_probe), ptr(d_probe_val), nprobe,
+                                               ptr(d_list_off), ptr(h), nlist, ptr(d_codes), ptr(d_ids), ptr(d_invq), ptr(d_invdb), k,
+                                               ptr(d_idx), ptr(d_val)))
+
     # query expansion / database-side augmentation (DESIGN.md section 13)
     COMBINE_CHUNK_BYTES, COMBINE_BATCH = _ffi.COMBINE_CHUNK_BYTES, _ffi.COMBINE_BATCH
 

@@ -43,14 +43,28 @@ def _vectors_and_paths(encoding_map):
     return np.array(list(encoding_map.values())), list(encoding_map.keys()), None
 
 
-def _rank_compact(query_vecs: np.ndarray, index, k: int | None, rerank: int = 0):
-    """_rank against a pvsim.compact.CompactIndex (ADC ranking, optionally re-ranked exactly on the ADC top-`rerank`)."""
+def _check_nprobe(index, nprobe):
+    """nprobe= goes with an IVFCompactIndex, and only with one"""
+    from .compact import IVFCompactIndex
+    if isinstance(index, IVFCompactIndex):
+        if nprobe is None:
+            raise ValueError("an IVFCompactIndex scans the nprobe best lists of a query: pass nprobe=")
+    elif nprobe is not None:
+        raise ValueError("nprobe= applies to an IVFCompactIndex only")
+
+
+def _rank_compact(query_vecs: np.ndarray, index, k: int | None, rerank: int = 0, nprobe=None):
+    """_rank against a pvsim.compact.CompactIndex (ADC ranking, optionally re-ranked exactly on the ADC top-`rerank`); an
+    IVFCompactIndex takes `nprobe` as well, and its lists may end in unfilled slots (index -1)."""
+    _check_nprobe(index, nprobe)
     if k is None:
         raise ValueError("a CompactIndex ranks a finite list: pass k (k=None asks for the complete ranking, which needs the "
                          "full-precision rows -- use a dict or a DeviceIndex for that)")
     kk = max(0, min(int(k), len(index)))
     if query_vecs.shape[0] == 0 or kk == 0:
         return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float32)
+    if nprobe is not None:
+        return index.rank(query_vecs, kk, nprobe, rerank=rerank)
     return index.rank(query_vecs, kk, rerank=rerank)             # rerank < k raises there, as it does for a direct call
 
 
@@ -71,10 +85,13 @@ def _no_compact_expansion(all_vectors, expand):
         raise ValueError("query expansion needs the full-precision rows: use a dict or a DeviceIndex, not a CompactIndex")
 
 
-def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None, resident=None):
+def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None, resident=None, rerank: int = 0, nprobe=None):
     """-> (indices (nq, k') int64, scores (nq, k')) with k' = min(k, N) (k=None: all N)."""
     if all_vectors is None:                                     # a CompactIndex: no host matrix
-        return _rank_compact(query_vecs, resident, k)
+        return _rank_compact(query_vecs, resident, k, rerank, nprobe)
+    if rerank:
+        raise ValueError("rerank= applies to a CompactIndex only")
+    _check_nprobe(resident, nprobe)
     n = all_vectors.shape[0]
     kk = n if k is None else max(0, min(int(k), n))
     if query_vecs.shape[0] == 0 or kk == 0:
@@ -92,10 +109,16 @@ def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=No
     return ctx.cosine_topk_f64(query_vecs, all_vectors, kk)
 
 
-def _rank_maybe_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths, k: int | None, ctx, resident, expand):
+def _rank_maybe_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths, k: int | None, ctx, resident, expand, rerank: int = 0,
+                         nprobe=None):
     """_rank, or with `expand` (a pvsim.expand.QueryExpansion) the ranking of the expanded queries: same k' and same empty results"""
     if expand is None:
-        return _rank(query_vecs, all_vectors, k, ctx, resident)
+        if not rerank and nprobe is None:
+            return _rank(query_vecs, all_vectors, k, ctx, resident)
+        return _rank(query_vecs, all_vectors, k, ctx, resident, rerank, nprobe)
+    if rerank:
+        raise ValueError("rerank= applies to a CompactIndex only")
+    _check_nprobe(resident, nprobe)
     _no_compact_expansion(all_vectors, expand)
     n = all_vectors.shape[0]
     kk = n if k is None else max(0, min(int(k), n))
@@ -105,22 +128,24 @@ def _rank_maybe_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths,
 
 
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
-                           k: int = 5, rerank: int = 0, expand=None) -> list[tuple[str, float]]:
+                           k: int = 5, rerank: int = 0, expand=None, nprobe=None) -> list[tuple[str, float]]:
     """[(image_path, similarity)] of the k most similar database entries, best first.  `rerank=R` (CompactIndex only): the
     ADC top-R re-ranked by the exact cosine of the kept projected rows.  `expand`: a pvsim.expand.QueryExpansion; the list is
-    then the ranking of the expanded query (dict or DeviceIndex; a dict is uploaded for the call)."""
+    then the ranking of the expanded query (dict or DeviceIndex; a dict is uploaded for the call).  `nprobe` (IVFCompactIndex
+    only, and required there): the inverted lists scanned; the list is shorter than k when they hold fewer rows."""
     all_vectors, all_paths, resident = _vectors_and_paths(dataset)
     _no_compact_expansion(all_vectors, expand)
     query_vector = encoder.encode(uploaded_image)
     if query_vector.ndim == 1:
         query_vector = query_vector.reshape(1, -1)
     if all_vectors is None:                                     # a CompactIndex: the only index that can re-rank
-        idx, val = _rank_compact(query_vector[:1], resident, k, rerank)
+        idx, val = _rank_compact(query_vector[:1], resident, k, rerank, nprobe)
     else:
         if rerank:
             raise ValueError("rerank= applies to a CompactIndex only")
+        _check_nprobe(resident, nprobe)
         idx, val = _rank_maybe_expanded(query_vector[:1], all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
-    return [(all_paths[i], s) for i, s in zip(idx[0], val[0])]
+    return [(all_paths[i], s) for i, s in zip(idx[0], val[0]) if i >= 0]      # unfilled slots of an IVF list are dropped
 
 
 def expand_verified(uploaded_image: np.ndarray, ranked, index, encoder, k: int = 5, qe=None,
@@ -177,20 +202,21 @@ def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: i
 
 
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None) -> float:
+              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None) -> float:
     """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95).  `expand`: rank the
-    expanded queries (pvsim.expand.QueryExpansion)."""
+    expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
+    there) as in retrieve_top_k_similar."""
     all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
     _no_compact_expansion(all_vectors, expand)
     labels = list(image_labels)
     q = _first_rows(encoder, images)
-    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
+    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
     db_labels = [path_labels_dict[p] for p in all_paths]
     aps = []
     for row, true_label in zip(idx, labels):
         relevant_count, precision_sum = 0, 0.0
         for rank, i in enumerate(row, start=1):
-            if db_labels[i] == true_label:
+            if i >= 0 and db_labels[i] == true_label:                # i < 0: an unfilled slot at the end of an IVF list
                 relevant_count += 1
                 precision_sum += relevant_count / rank
         aps.append(precision_sum / relevant_count if relevant_count > 0 else 0.0)
@@ -198,15 +224,16 @@ def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encodin
 
 
 def top_k_accuracy(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-                   path_labels_dict: dict[str, int], encoder, k: int, expand=None) -> float:
+                   path_labels_dict: dict[str, int], encoder, k: int, expand=None, rerank: int = 0, nprobe=None) -> float:
     """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145).  `expand`: rank the
-    expanded queries (pvsim.expand.QueryExpansion)."""
+    expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
+    there) as in retrieve_top_k_similar."""
     all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
     _no_compact_expansion(all_vectors, expand)
     images = list(images)
     labels = list(image_labels)
     q = _first_rows(encoder, images)
-    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
+    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
     db_labels = [path_labels_dict[p] for p in all_paths]
-    correct = sum(1 for row, true_label in zip(idx, labels) if any(db_labels[i] == true_label for i in row))
+    correct = sum(1 for row, true_label in zip(idx, labels) if any(i >= 0 and db_labels[i] == true_label for i in row))
     return float(correct / len(images))

@@ -1,0 +1,396 @@
+"""GPU tests of the inverted lists of the compact index (csrc/ivf.hip, pvsim.IVFCompactIndex): every kernel against the NumPy twin
+(tests/ivf_numpy.py), bit for bit -- include/pvsim.h fixes each summation order, so there is no tolerance to argue about."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import ivf_numpy as iv
+import pq_numpy as tw
+
+pytestmark = pytest.mark.gpu
+
+ASSIGN_LDS_FLOATS = 16384      # centroid floats one LDS chunk of the assignment kernel holds
+
+
+def _up(ctx, a):
+    a = np.ascontiguousarray(a)
+    return ctx.buffer(max(a.nbytes, 16)).upload(a)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# ------------------------------------------------------------------------------------------------ assignment + residual
+@pytest.mark.parametrize("n,d,nlist", [(1, 2, 1), (65, 64, 7), (1000, 257, 300), (1000, 2, 7), (65, 257, 1), (1, 64, 300)])
+def test_assign_and_residual_match_twin(gpu_ctx, n, d, nlist):
+    """values spanning 2^-6 .. 2^6; centroid 1 is repeated as the last one (its list must stay empty: the lowest l keeps a tie),
+    a third of the rows sit exactly on centroids.  (1000, 257, 300) is 77100 centroid floats: five LDS chunks."""
+    rng = np.random.default_rng(1000 + n + d + nlist)
+    cent = (rng.standard_normal((nlist, d)) * np.exp2(rng.integers(-6, 7, (nlist, 1)))).astype(np.float32)
+    if nlist >= 3:
+        cent[nlist - 1] = cent[1]
+    x = (cent[rng.integers(0, nlist, n)] * (1 + 0.3 * rng.standard_normal((n, d)))).astype(np.float32)
+    x[::3] = cent[rng.integers(0, nlist, len(x[::3]))]
+    if nlist >= 3:
+        x[0] = cent[nlist - 1]
+    d_x, d_c, d_l, d_r = _up(gpu_ctx, x), _up(gpu_ctx, cent), gpu_ctx.buffer(n * 4), gpu_ctx.buffer(n * d * 4)
+    gpu_ctx.ivf_assign_dev(d_x.ptr, n, d, d_c.ptr, nlist, d_l.ptr, d_r.ptr)
+    lists, res = d_l.download((n,), np.int32), d_r.download((n, d), np.float32)
+    want_l, want_r = iv.assign(x, cent)
+    assert np.array_equal(lists, want_l) and np.array_equal(_bits(res), _bits(want_r))
+    if nlist >= 3:
+        assert lists[0] == 1 and not (lists == nlist - 1).any()
+    if (n, d, nlist) == (1000, 257, 300):
+        assert nlist * d > ASSIGN_LDS_FLOATS
+        gpu_ctx.ivf_assign_dev(d_x.ptr, n, d, d_c.ptr, nlist, d_l.ptr, None)          # labels alone
+        assert np.array_equal(d_l.download((n,), np.int32), want_l)
+    for b in (d_x, d_c, d_l, d_r):
+        b.free()
+
+
+# ------------------------------------------------------------------------------------------------ coarse terms, probes
+@pytest.mark.parametrize("nq,d,nlist", [(1, 2, 1), (5, 64, 7), (130, 257, 300)])
+def test_coarse_terms_and_probes_match_twin(gpu_ctx, nq, d, nlist):
+    rng = np.random.default_rng(1100 + nq)
+    cent = (rng.standard_normal((nlist, d)) * np.exp2(rng.integers(-6, 7, (nlist, 1)))).astype(np.float32)
+    if nlist >= 3:
+        cent[nlist - 1] = cent[1]                                  # equal coarse terms: the lower list comes first
+    q = rng.standard_normal((nq, d)).astype(np.float32)
+    d_q, d_c, d_o = _up(gpu_ctx, q), _up(gpu_ctx, cent), gpu_ctx.buffer(nq * nlist * 4)
+    gpu_ctx.ivf_coarse_dev(d_q.ptr, nq, d, d_c.ptr, nlist, d_o.ptr)
+    co = d_o.download((nq, nlist), np.float32)
+    want = iv.coarse(q, cent)
+    assert np.array_equal(_bits(co), _bits(want))
+    for nprobe in sorted({1, min(3, nlist), nlist}):
+        d_i, d_v = gpu_ctx.buffer(nq * nprobe * 8), gpu_ctx.buffer(nq * nprobe * 4)
+        gpu_ctx.topk_dev(d_o.ptr, nq, nlist, nlist, nprobe, 0, False, d_i.ptr, d_v.ptr)
+        pi, pv = iv.probes(want, nprobe)
+        assert np.array_equal(d_i.download((nq, nprobe), np.int64), pi)
+        assert np.array_equal(_bits(d_v.download((nq, nprobe), np.float32)), _bits(pv))
+        d_i.free(), d_v.free()
+    for b in (d_q, d_c, d_o):
+        b.free()
+
+
+# ------------------------------------------------------------------------------------------------ scan + ranking
+def _hand_lists(rng, N, nlist):
+    """list of every row: list 0 holds more than half the rows, the last list (and list 2, if there are five) stays empty"""
+    if nlist == 1:
+        return np.zeros(N, np.int64)
+    lists = rng.integers(0, nlist - 1, N)
+    if nlist >= 5:
+        lists[lists == 2] = 3
+    lists[rng.random(N) < 0.55] = 0
+    return lists
+
+
+def _search(ctx, table, co, nprobe, off, ids, codes, inv_q, inv_db, k):
+    """the probes by pvs_topk_dev, then pvs_ivf_scan_topk_dev -> (idx, val)"""
+    nq, m, ksub = table.shape
+    nlist = co.shape[1]
+    bufs = [_up(ctx, table), _up(ctx, co), ctx.buffer(nq * nprobe * 8), ctx.buffer(nq * nprobe * 4), _up(ctx, off), _up(ctx, codes),
+            _up(ctx, ids), ctx.buffer(nq * k * 8), ctx.buffer(nq * k * 4)]
+    d_t, d_co, d_pi, d_pv, d_off, d_codes, d_ids, d_idx, d_val = bufs
+    d_iq = _up(ctx, inv_q) if inv_q is not None else None
+    d_id = _up(ctx, inv_db) if inv_db is not None else None
+    ctx.topk_dev(d_co.ptr, nq, nlist, nlist, nprobe, 0, False, d_pi.ptr, d_pv.ptr)
+    ctx.ivf_scan_topk_dev(d_t.ptr, nq, m, ksub, d_pi.ptr, d_pv.ptr, nprobe, d_off.ptr, off, nlist, d_codes.ptr, d_ids.ptr,
+                          d_iq.ptr if d_iq else None, d_id.ptr if d_id else None, k, d_idx.ptr, d_val.ptr)
+    out = d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
+    for b in bufs + [d_iq, d_id]:
+        if b is not None:
+            b.free()
+    return out
+
+
+def _scan_case(seed, nq, m, ksub, N, nlist):
+    rng = np.random.default_rng(seed)
+    table = (rng.standard_normal((nq, m, ksub)) * np.exp2(rng.integers(-3, 4, (nq, m, 1)))).astype(np.float32)
+    co = rng.standard_normal((nq, nlist)).astype(np.float32)
+    ids, off = iv.sort_into_lists(_hand_lists(rng, N, nlist), nlist)
+    codes = rng.integers(0, ksub, (N, m)).astype(np.uint8)
+    inv_q = (0.5 + rng.random(nq)).astype(np.float32)
+    inv_db = (0.5 + rng.random(N)).astype(np.float32)
+    return table, co, off, ids, codes, inv_q, inv_db
+
+
+def _check(ctx, case, nprobe, k):
+    table, co, off, ids, codes, inv_q, inv_db = case
+    gi, gv = _search(ctx, table, co, nprobe, off, ids, codes, inv_q, inv_db, k)
+    wi, wv = iv.search(table, co, nprobe, off, ids, codes, inv_q, inv_db, k)
+    assert np.array_equal(gi, wi), (nprobe, k)
+    assert np.array_equal(_bits(gv), _bits(wv)), (nprobe, k)
+    return gi
+
+
+@pytest.mark.parametrize("N,nlist,m,ksub,nq", [(1, 1, 8, 16, 3), (65, 7, 6, 255, 5), (4099, 7, 16, 256, 4), (4099, 64, 7, 64, 9),
+                                               (65, 64, 32, 256, 2), (4099, 1, 64, 256, 2)])
+def test_scan_and_ranking_match_twin(gpu_ctx, N, nlist, m, ksub, nq):
+    """hand-set lists (one holds more than half the rows, at least one is empty when nlist > 1); m = 8 takes the dword path, 6 and 7
+    the byte path, 16 / 32 / 64 the 16-byte path; 4099 rows in one list cross a tile of the scan kernel"""
+    case = _scan_case(1200 + N + nlist, nq, m, ksub, N, nlist)
+    off = case[2]
+    if nlist > 1:
+        assert (np.diff(off) == 0).any() and np.diff(off).max() > N // 2
+    short = False
+    for nprobe in sorted({1, min(3, nlist), nlist}):
+        for k in (1, 10, 100):
+            gi = _check(gpu_ctx, case, nprobe, k)
+            short = short or bool((gi == -1).any())
+    assert short or N >= 4099                                      # k greater than the number of probed rows occurred
+
+
+def test_scan_queries_cross_the_query_block(gpu_ctx):
+    """the candidate workspace holds 64 MiB: with 16448 slots per query (8 bytes each) a block is 510 queries, 600 queries are two"""
+    N, nlist, m, ksub, nq = 16400, 2, 4, 16, 600
+    rng = np.random.default_rng(1300)
+    table = rng.standard_normal((nq, m, ksub)).astype(np.float32)
+    co = rng.standard_normal((nq, nlist)).astype(np.float32)
+    lists = np.zeros(N, np.int64)
+    lists[::41] = 1
+    ids, off = iv.sort_into_lists(lists, nlist)
+    width = -(-int(np.diff(off).sum()) // 64) * 64
+    assert (64 << 20) // (8 * width) < nq
+    codes = rng.integers(0, ksub, (N, m)).astype(np.uint8)
+    inv_db = (0.5 + rng.random(N)).astype(np.float32)
+    _check(gpu_ctx, (table, co, off, ids, codes, None, inv_db), 2, 10)
+
+
+def test_scan_above_the_lds_segment_limit(gpu_ctx):
+    """(m, ksub) = (161, 256): 41216 table entries, more than one LDS segment; the running sum lives across the segments"""
+    case = _scan_case(1400, 3, 161, 256, 2500, 7)
+    _check(gpu_ctx, case, 3, 10)
+    _check(gpu_ctx, case, 7, 100)
+
+
+def test_equal_scores_across_lists_rank_by_original_index(gpu_ctx):
+    """integer tables and coarse terms: all sums exact.  Every row of lists 0 and 1 scores the same, so the cut at k falls inside
+    a run of equal scores that spans two lists, and the order is by original index, not by stored position."""
+    rng = np.random.default_rng(1500)
+    N, nlist, m, ksub, nq = 300, 4, 4, 8, 3
+    table = rng.integers(-2, 3, (nq, m, ksub)).astype(np.float32)
+    table[0] = 1.0                                                 # query 0: the score is the coarse term + 4
+    co = rng.integers(-1, 2, (nq, nlist)).astype(np.float32)
+    co[0] = [3.0, 3.0, 5.0, -1.0]
+    lists = rng.integers(0, 2, N)                                  # lists 0 and 1 interleave in the original order
+    lists[:10] = [1, 0, 1, 1, 0, 1, 0, 0, 1, 0]
+    lists[20:24] = 2                                               # four better rows in list 2; list 3 is empty
+    ids, off = iv.sort_into_lists(lists, nlist)
+    codes = rng.integers(0, ksub, (N, m)).astype(np.uint8)
+    case = (table, co, off, ids, codes, None, None)
+    for nprobe, k in ((3, 10), (4, 100), (2, 5)):
+        gi = _check(gpu_ctx, case, nprobe, k)
+        if nprobe >= 3:
+            assert gi[0, :4].tolist() == [20, 21, 22, 23]
+            want = [i for i in range(N) if lists[i] < 2][:k - 4]
+            assert gi[0, 4:].tolist() == want and len({int(lists[i]) for i in want}) == 2
+
+
+def test_zero_centroid_one_list_equals_the_flat_scan(gpu_ctx):
+    """identity 1 on the device: nlist = 1, coarse term +0 -> the bits of pvs_pq_scan_topk_dev on the same codes"""
+    rng = np.random.default_rng(1600)
+    N, m, ksub, nq, d = 3000, 16, 256, 6, 32
+    table = rng.standard_normal((nq, m, ksub)).astype(np.float32)
+    codes = rng.integers(0, ksub, (N, m)).astype(np.uint8)
+    inv_q, inv_db = (0.5 + rng.random(nq)).astype(np.float32), (0.5 + rng.random(N)).astype(np.float32)
+    q = rng.standard_normal((nq, d)).astype(np.float32)
+    d_q, d_c, d_o = _up(gpu_ctx, q), _up(gpu_ctx, np.zeros((1, d), np.float32)), gpu_ctx.buffer(nq * 4)
+    gpu_ctx.ivf_coarse_dev(d_q.ptr, nq, d, d_c.ptr, 1, d_o.ptr)
+    co = d_o.download((nq, 1), np.float32)
+    assert not _bits(co).any()                                     # +0
+    off, ids = np.array([0, N], np.int64), np.arange(N, dtype=np.int32)
+    for k in (1, 10, 100):
+        gi, gv = _search(gpu_ctx, table, co, 1, off, ids, codes, inv_q, inv_db, k)
+        bufs = [_up(gpu_ctx, a) for a in (table, codes, inv_q, inv_db)] + [gpu_ctx.buffer(nq * k * 8), gpu_ctx.buffer(nq * k * 4)]
+        gpu_ctx.pq_scan_topk_dev(bufs[0].ptr, nq, m, ksub, bufs[1].ptr, N, bufs[2].ptr, bufs[3].ptr, k, 0, False, bufs[4].ptr, bufs[5].ptr)
+        fi, fv = bufs[4].download((nq, k), np.int64), bufs[5].download((nq, k), np.float32)
+        assert np.array_equal(gi, fi) and np.array_equal(_bits(gv), _bits(fv))
+        for b in bufs:
+            b.free()
+    for b in (d_q, d_c, d_o):
+        b.free()
+
+
+# ------------------------------------------------------------------------------------------------ through the class
+@pytest.fixture(scope="module")
+def corpus():
+    """400 VLAD-like rows of L = 256 (sparse blocks, signed, L2-normalised) and 10 queries near rows 0, 40, ..."""
+    rng = np.random.default_rng(1700)
+    basis = rng.standard_normal((16, 256)) * (rng.random((16, 256)) < 0.3)
+    x = rng.standard_normal((400, 16)) @ basis + 0.2 * rng.standard_normal((400, 256))
+    x = (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+    q = (x[::40] + 0.05 * rng.standard_normal((10, 256))).astype(np.float32)
+    return x, q
+
+
+FIT = dict(m=8, n_components=32, ksub=32, keep_projected=True, random_state=5, max_iter=10)
+
+
+@pytest.fixture(scope="module")
+def fitted(gpu_ctx, corpus):
+    from pvsim import IVFCompactIndex
+    x, q = corpus
+    db = {f"img/{i:04d}.jpg": x[i] for i in range(len(x))}
+    index = IVFCompactIndex.fit(db, 12, ctx=gpu_ctx, **FIT)
+    yield index, db
+    index.close()
+
+
+def _twin_of(index, x, q):
+    """the twin fed with the device's own projection, centroids and codebooks -> what rank must give"""
+    codes, inv_db, proj = index._download()
+    y = index.project(x)
+    assert np.array_equal(_bits(proj), _bits(y))                   # kept rows stay in original order
+    lists, res = iv.assign(y, index.centroids)
+    ids, off = iv.sort_into_lists(lists, index.nlist)
+    assert np.array_equal(ids, index._ids) and np.array_equal(off, index._list_off)
+    assert np.array_equal(index.list_sizes, np.bincount(lists, minlength=index.nlist))
+    cb = index.quantizer.codebooks
+    assert np.array_equal(codes, tw.encode(res, cb)[ids])
+    yq = index.project(q)
+    ctx = index.context
+    d_y, d_i = _up(ctx, yq), ctx.buffer(len(yq) * 4)
+    ctx.row_inv_norms_dev(d_y.ptr, len(yq), yq.shape[1], d_i.ptr)
+    inv_q = d_i.download((len(yq),), np.float32)
+    d_y.free(), d_i.free()
+    d_p, d_n = _up(ctx, y), ctx.buffer(len(y) * 4)
+    ctx.row_inv_norms_dev(d_p.ptr, len(y), y.shape[1], d_n.ptr)
+    inv_orig = d_n.download((len(y),), np.float32)
+    d_p.free(), d_n.free()
+    assert np.array_equal(_bits(inv_db), _bits(inv_orig[ids]))     # norms in stored order
+    return dict(table=tw.lut(yq, cb), co=iv.coarse(yq, index.centroids), off=off, ids=ids, codes=codes, inv_q=inv_q, inv_db=inv_db,
+                inv_orig=inv_orig, y=y, yq=yq)
+
+
+def test_fit_and_rank_equal_the_twin(fitted, corpus):
+    index, _ = fitted
+    x, q = corpus
+    t = _twin_of(index, x, q)
+    assert index.nlist == 12 and index.list_sizes.sum() == 400 and len(index) == 400
+    for nprobe in (1, 3, 12):
+        idx, val = index.rank(q, 10, nprobe)
+        wi, wv = iv.search(t["table"], t["co"], nprobe, t["off"], t["ids"], t["codes"], t["inv_q"], t["inv_db"], 10)
+        assert np.array_equal(idx, wi) and np.array_equal(_bits(val), _bits(wv))
+        ridx, rval = index.rank(q, 10, nprobe, rerank=50)
+        cand, _ = iv.search(t["table"], t["co"], nprobe, t["off"], t["ids"], t["codes"], t["inv_q"], t["inv_db"], 50)
+        wi, wv = tw.rerank(cand, tw.rescore(t["yq"], t["y"], cand, t["inv_q"], t["inv_orig"]), 10)
+        assert np.array_equal(ridx, wi) and np.array_equal(_bits(rval), _bits(wv))
+        filled = (cand >= 0).sum(1)
+        for r in range(len(q)):                                    # unfilled slots stay last
+            assert (ridx[r, :min(10, filled[r])] >= 0).all() and (ridx[r, filled[r]:] == -1).all()
+    ridx, _ = index.rank(q, 10, 12, rerank=50)
+    assert np.array_equal(ridx[:, 0], np.arange(0, 400, 40))       # every list probed + exact re-ranking: the source row comes first
+
+
+def test_save_load_eval_and_device_index_source(gpu_ctx, fitted, corpus, tmp_path):
+    from pvsim import IVFCompactIndex
+    from pvsim import eval as ev
+    from pvsim.index import DeviceIndex
+    index, db = fitted
+    x, q = corpus
+    fn = str(tmp_path / "ivf.npz")
+    index.save(fn)
+    back = IVFCompactIndex.load(fn, ctx=gpu_ctx)
+    assert back.paths == index.paths and back.nbytes == index.nbytes and np.array_equal(back.list_sizes, index.list_sizes)
+    dev = DeviceIndex(db, gpu_ctx)
+    other = IVFCompactIndex.fit(dev, 12, **FIT)
+    assert other.context is gpu_ctx and np.array_equal(other.centroids, index.centroids)
+    for got, want in zip(other._download(), index._download()):
+        assert np.array_equal(got.view(np.uint8), want.view(np.uint8))
+    for rr in (0, 30):
+        a = index.rank(q, 10, 3, rerank=rr)
+        for o in (back, other):
+            b = o.rank(q, 10, 3, rerank=rr)
+            assert np.array_equal(a[0], b[0]) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    back.close(), other.close(), dev.close()
+
+    class Identity:
+        def encode(self, v):
+            return v
+
+    idx, val = index.rank(q[:1], 5, 2)
+    hits = ev.retrieve_top_k_similar(q[0], index, Identity(), k=5, nprobe=2)
+    keep = idx[0] >= 0
+    assert [p for p, _ in hits] == [index.paths[i] for i in idx[0][keep]] and [s for _, s in hits] == val[0][keep].tolist()
+    ridx, _ = index.rank(q[:1], 5, 2, rerank=20)
+    hits = ev.retrieve_top_k_similar(q[0], index, Identity(), k=5, rerank=20, nprobe=2)
+    assert [p for p, _ in hits] == [index.paths[i] for i in ridx[0] if i >= 0]
+    labels = {p: i // 40 for i, p in enumerate(index.paths)}
+    assert ev.top_k_accuracy(list(q), list(range(10)), index, labels, Identity(), k=20, nprobe=12) > 0.9
+    assert 0.0 <= ev.top_k_map(list(q), list(range(10)), index, labels, Identity(), k=20, nprobe=1, rerank=20) <= 1.0
+    # one probed list holds fewer than k rows: the unfilled slots are dropped from the returned list
+    full, _ = index.rank(q[:1], 400, 1)
+    got = ev.retrieve_top_k_similar(q[0], index, Identity(), k=400, nprobe=1)
+    assert len(got) == int((full[0] >= 0).sum()) < 400
+
+
+def test_fit_frees_its_buffers_when_it_fails(gpu_ctx, fitted, monkeypatch):
+    from pvsim import IVFCompactIndex
+    _, db = fitted
+    taken = []
+    real = gpu_ctx.buffer
+
+    def counting(nbytes):
+        b = real(nbytes)
+        taken.append(b)
+        return b
+
+    monkeypatch.setattr(gpu_ctx, "buffer", counting)
+
+    def boom(*a, **k):
+        raise RuntimeError("encode failed")
+
+    monkeypatch.setattr(gpu_ctx, "pq_encode_dev", boom)
+    with pytest.raises(RuntimeError, match="encode failed"):
+        IVFCompactIndex.fit(db, 12, ctx=gpu_ctx, **FIT)
+    import gc
+    gc.collect()
+    assert taken and all(b.ptr == 0 for b in taken)                # every buffer the call took was given back
+
+
+# ------------------------------------------------------------------------------------------------ error paths
+def test_invalid_arguments_return_an_error_without_a_launch(gpu_ctx):
+    from pvsim import _ffi
+    lib, h = _ffi.lib(), gpu_ctx.handle
+    buf = gpu_ctx.buffer(1 << 16).fill_bytes(0)
+    p = buf.ptr
+    vp, null = C.c_void_p, C.c_void_p(None)
+    off = np.array([0, 20, 20, 50], np.int64)
+    buf.upload(off, offset=32768)
+
+    def scan(lut=p, nq=2, m=4, ksub=16, probe=p + 4096, pval=p + 8192, nprobe=2, d_off=p + 32768, h_off=off, nlist=3, codes=p + 12288,
+             ids=p + 16384, k=5, idx=p + 20480, val=p + 24576):
+        return lib.pvs_ivf_scan_topk_dev(h, vp(lut), nq, m, ksub, vp(probe), vp(pval), nprobe, vp(d_off),
+                                         _ffi.ptr(h_off) if h_off is not None else null, nlist, vp(codes), vp(ids), null, null, k, vp(idx),
+                                         vp(val))
+
+    assert scan() == _ffi.PVS_OK
+    bad_off = np.array([0, 30, 20, 50], np.int64)
+    huge = np.array([0, 1 << 31, 1 << 31, 1 << 31], np.int64)
+    for bad in (dict(m=0), dict(ksub=257), dict(ksub=0), dict(k=0), dict(k=1025), dict(nprobe=0), dict(nprobe=4), dict(nlist=0),
+                dict(nlist=65537), dict(idx=None), dict(val=None), dict(idx=p + 4), dict(val=p + 2), dict(lut=None), dict(codes=None),
+                dict(ids=None), dict(probe=None), dict(pval=None), dict(d_off=None), dict(h_off=None), dict(h_off=bad_off),
+                dict(h_off=huge), dict(nq=-1), dict(probe=p + 4100)):
+        assert scan(**bad) == _ffi.PVS_ERR_INVALID, bad
+        assert lib.pvs_last_error()
+    assert scan(nq=0, idx=None, val=None) == _ffi.PVS_OK               # nq == 0 is a no-op
+
+    def assign(x=p, n=5, d=4, cent=p + 4096, nlist=3, lst=p + 8192, res=p + 12288):
+        return lib.pvs_ivf_assign_dev(h, vp(x), n, d, vp(cent), nlist, vp(lst), vp(res))
+
+    assert assign() == _ffi.PVS_OK and assign(res=None) == _ffi.PVS_OK and assign(n=0, x=None) == _ffi.PVS_OK
+    for bad in (dict(d=0), dict(nlist=0), dict(nlist=65537), dict(n=-1), dict(n=1 << 31), dict(x=None), dict(cent=None), dict(lst=None),
+                dict(x=p + 2), dict(lst=p + 8194)):
+        assert assign(**bad) == _ffi.PVS_ERR_INVALID, bad
+    assert assign(d=16385) == _ffi.PVS_ERR_UNSUPPORTED
+
+    def coarse(q=p, nq=5, d=4, cent=p + 4096, nlist=3, out=p + 8192):
+        return lib.pvs_ivf_coarse_dev(h, vp(q), nq, d, vp(cent), nlist, vp(out))
+
+    assert coarse() == _ffi.PVS_OK and coarse(nq=0, q=None) == _ffi.PVS_OK
+    for bad in (dict(d=0), dict(nlist=0), dict(nlist=65537), dict(nq=-1), dict(q=None), dict(cent=None), dict(out=None), dict(out=p + 1)):
+        assert coarse(**bad) == _ffi.PVS_ERR_INVALID, bad
+    gpu_ctx.sync()
+    buf.free()
