@@ -172,7 +172,9 @@ int pvs_cosine_dual_dev(pvs_ctx* ctx, const float* d_A, int64_t M, const float* 
                         const float* d_inv_a, const float* d_inv_b, float* d_out, int64_t ldo, float* d_out_t, int64_t ldt);
 
 /* ---------------------------------------------------------------- top-k: pyvisim/eval.py:37-43,75-80,131-132
- * per query row: np.argsort(-scores)[:k].  Order is (score desc, index asc); NaN scores rank last.
+ * per query row: np.argsort(-scores)[:k].  Order is (score desc, index asc); NaN scores rank last, after -inf; -0 and +0 tie.
+ * Returned values: a zero score comes back as +0.0 whatever its sign was, and every NaN as the canonical quiet NaN (0x7fc00000,
+ * float64: 0x7ff8000000000000) whatever its sign and payload were; slots that cannot be filled are idx = -1, val = -inf.
  * pvs_topk_dev consumes a score panel [nq][ncols] (row stride ld) whose column 0 has global index
  * col_offset; with merge != 0 the panel is merged into the running lists already in d_idx/d_val.
  * d_idx: int64 [nq*k], d_val: float32 [nq*k]. */

@@ -6,6 +6,7 @@ across independent rows / centroids / queries.  The device kernels must agree wi
 import numpy as np
 
 import pq_numpy as pq
+import topk_numpy as tk
 
 F = np.float32
 
@@ -68,17 +69,12 @@ def search(table, coarse_terms, nprobe, list_off, ids, codes, inv_q, inv_db, k):
     iq = np.ones(nq, F) if inv_q is None else pq._f32(inv_q)
     idb = np.ones(len(codes), F) if inv_db is None else pq._f32(inv_db)
     plist, pval = probes(coarse_terms, nprobe)
-    idx = np.full((nq, k), -1, np.int64)
-    val = np.full((nq, k), -np.inf, F)
+    idx = np.empty((nq, k), np.int64)
+    val = np.empty((nq, k), F)
     for q in range(nq):
         rows = np.concatenate([np.arange(list_off[l], list_off[l + 1]) for l in plist[q]]).astype(np.int64)
         acc = np.concatenate([np.full(int(list_off[l + 1] - list_off[l]), v, F) for l, v in zip(plist[q], pval[q])]).astype(F)
         for s in range(m):
             acc = acc + table[q, s, :][codes[rows, s].astype(np.int64)]
-        sc = (acc * iq[q]) * idb[rows]
-        orig = ids[rows].astype(np.int64)
-        nan = np.isnan(sc)
-        key = np.where(nan, F(-np.inf), sc) + F(0)                          # -0 and +0 rank alike
-        o = np.lexsort((orig, -key, nan))[:k]
-        idx[q, :len(o)], val[q, :len(o)] = orig[o], sc[o]
+        idx[q], val[q] = tk.rank_row(ids[rows].astype(np.int64), (acc * iq[q]) * idb[rows], k)
     return idx, val

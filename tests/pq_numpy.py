@@ -5,6 +5,8 @@ multiply and one per add, no np.sum, no @ -- vectorised only across independent 
 change any rounding.  The device kernels must agree with this bit for bit."""
 import numpy as np
 
+import topk_numpy as tk
+
 F = np.float32
 
 
@@ -70,18 +72,8 @@ def scores(table, codes, inv_q=None, inv_db=None):
 
 
 def topk(score, k, col_offset=0):
-    """(score descending, global index ascending), NaN last -> idx int64 (nq, k), val f32 (nq, k)."""
-    score = _f32(score)
-    nq, N = score.shape
-    idx = np.empty((nq, k), np.int64)
-    val = np.empty((nq, k), F)
-    cols = np.arange(N, dtype=np.int64)
-    for r in range(nq):
-        nan = np.isnan(score[r])
-        key = np.where(nan, F(-np.inf), score[r]) + F(0)                    # -0 and +0 rank alike
-        o = np.lexsort((cols, -key, nan))[:k]
-        idx[r], val[r] = o + col_offset, score[r][o]
-    return idx, val
+    """(score descending, global index ascending), NaN last -> idx int64 (nq, k), val f32 (nq, k): the rule of topk_numpy."""
+    return tk.topk(_f32(score), k, col_offset)
 
 
 def rescore(Q, X, cand, inv_q=None, inv_db=None):

@@ -213,6 +213,110 @@ def test_zero_centroid_one_list_equals_the_flat_scan(gpu_ctx):
         b.free()
 
 
+# ------------------------------------------------------------------------------------------------ paths no case above reaches
+def _case_with_lists(seed, nq, m, ksub, lists, nlist):
+    """_scan_case with the list of every row given"""
+    rng = np.random.default_rng(seed)
+    N = len(lists)
+    table = (rng.standard_normal((nq, m, ksub)) * np.exp2(rng.integers(-3, 4, (nq, m, 1)))).astype(np.float32)
+    co = rng.standard_normal((nq, nlist)).astype(np.float32)
+    ids, off = iv.sort_into_lists(lists, nlist)
+    codes = rng.integers(0, ksub, (N, m)).astype(np.uint8)
+    inv_q = (0.5 + rng.random(nq)).astype(np.float32)
+    inv_db = (0.5 + rng.random(N)).astype(np.float32)
+    return table, co, off, ids, codes, inv_q, inv_db
+
+
+@pytest.mark.parametrize("nprobe", [128, 129, 301, 1024])
+def test_many_probes(gpu_ctx, nprobe):
+    """nlist = 1100: two probes per lane reach the second wave of the prefix scan at 129 probes, 1024 is the limit.  More than half
+    the lists are empty (runs of empty probes in the binary search over the prefix sums), one list holds more than half the rows."""
+    rng = np.random.default_rng(1800)
+    N, nlist = 3000, 1100
+    lists = rng.choice(rng.permutation(nlist)[:500], N)
+    lists[rng.random(N) < 0.55] = lists[0]
+    case = _case_with_lists(1801, 3, 4, 16, lists, nlist)
+    sizes = np.diff(case[2])
+    assert (sizes == 0).sum() > nlist // 2 and sizes.max() > N // 2
+    for k in (10, 1024):
+        _check(gpu_ctx, case, nprobe, k)
+
+
+@pytest.mark.parametrize("m,ksub", [(160, 256), (148, 256), (372, 100)])
+def test_more_than_one_lds_segment_on_each_load_width(gpu_ctx, m, ksub):
+    """36864 table entries fit one LDS segment.  (160, 256): 16-byte code loads, segments of 144 and 16 sub-spaces; (148, 256): dword
+    loads, 144 and 4; (372, 100): dword loads, 368 and 4, a segment length that is no power of two.  2200 of the 2500 rows sit in
+    one list: the candidate row of a query that probes it is wider than one tile of 2048 slots and is served by two workgroups."""
+    seg_m = 36864 // ksub
+    assert m > seg_m and (m % 16 == 0 and seg_m % 16 == 0) == ((m, ksub) == (160, 256)) and m % 4 == 0 and seg_m % 4 == 0
+    rng = np.random.default_rng(1900 + m)
+    N, nlist = 2500, 7
+    lists = rng.integers(1, nlist - 1, N)
+    lists[rng.permutation(N)[:2200]] = 0
+    case = _case_with_lists(1901 + m, 3, m, ksub, lists, nlist)
+    case[1][0, 0], case[1][1, 0] = 9.0, -9.0                      # query 0 probes the long list first, query 1 last
+    assert np.diff(case[2]).max() == 2200 > 2048
+    for nprobe in (1, 3):
+        for k in (10, 100):
+            _check(gpu_ctx, case, nprobe, k)
+
+
+def test_list_mode_ranking_across_chunks_at_depth(gpu_ctx):
+    """9000 candidates per query are two 8192-slot chunks of the list-mode ranking, with a running list of k = 1000 / 1024 between
+    them; with one probe, query 0 gets the list of 500 rows: fewer than k"""
+    rng = np.random.default_rng(2000)
+    N, nlist = 9000, 2
+    lists = np.zeros(N, np.int64)
+    lists[rng.permutation(N)[:500]] = 1
+    case = _case_with_lists(2001, 3, 4, 16, lists, nlist)
+    case[1][0], case[1][1] = [-1.0, 1.0], [1.0, -1.0]             # query 0 prefers list 1 (500 rows), query 1 list 0
+    for k in (1000, 1024):
+        gi = _check(gpu_ctx, case, 2, k)
+        assert (gi >= 0).all()
+    gi = _check(gpu_ctx, case, 1, 1000)
+    assert (gi[0, :500] >= 0).all() and (gi[0, 500:] == -1).all() and (gi[1] >= 0).all()
+
+
+def test_zero_and_nan_scores_come_back_in_canonical_form(gpu_ctx):
+    """integer tables, all sums exact and <= 0.  Query 0: rows whose codes all pick a -0.0 entry under a -0.0 coarse term score
+    -0.0, rows that pick the +0.0 entry score +0.0; they tie, rank by original index and come back as +0.0.  Query 1: one table
+    entry is a NaN with sign and payload, another is -inf: NaN rows rank after the -inf rows and before the unfilled slots, and
+    come back as the canonical quiet NaN."""
+    rng = np.random.default_rng(2100)
+    N, nlist, m, ksub, nq = 600, 3, 4, 4, 2
+    table = np.empty((nq, m, ksub), np.float32)
+    table[:] = [-0.0, -0.0, -1.0, -2.0]
+    table[0, 0, 0] = 0.0
+    table[1, 2, 3] = -np.inf
+    table[1, 1, 2] = np.nan
+    table[1].reshape(-1).view(np.uint32)[1 * ksub + 2] = 0xffc00123
+    co = np.array([[-0.0, -0.0, -1.0], [-0.0, -1.0, -0.0]], np.float32)
+    ids, off = iv.sort_into_lists(rng.integers(0, 2, N), nlist)   # list 2 is empty
+    codes = rng.integers(0, ksub, (N, m)).astype(np.uint8)
+    case = (table, co, off, ids, codes, None, None)
+    exact = tw.scores(table, codes)                               # stored order
+    s0 = np.full(N, -0.0, np.float32)                             # query 0: the coarse term of lists 0 and 1 is -0.0
+    for s in range(m):
+        s0 = s0 + table[0, s][codes[:, s]]
+    zero = s0 == 0
+    assert (zero & np.signbit(s0)).sum() >= 3 and (zero & ~np.signbit(s0)).sum() >= 3
+    assert np.isnan(exact[1]).sum() > 100 and np.isneginf(exact[1]).sum() > 50
+    for nprobe, k in ((2, 10), (2, 600), (3, 700), (1, 5)):
+        gi, gv = _search(gpu_ctx, *case[:2], nprobe, *case[2:], k)
+        wi, wv = iv.search(*case[:2], nprobe, *case[2:], k)
+        assert np.array_equal(gi, wi) and np.array_equal(_bits(gv), _bits(wv)), (nprobe, k)
+        assert not (_bits(gv) == 0x80000000).any() and (_bits(gv)[np.isnan(gv)] == 0x7fc00000).all()
+        if nprobe == 2 and k == 10:
+            assert not _bits(gv[0]).any()                        # ten zeros, all +0.0
+            both = np.sort(ids[zero].astype(np.int64))[:10]
+            assert gi[0].tolist() == both.tolist()
+        if k >= 600:
+            nan, ninf, unfilled = np.isnan(gv[1]), np.isneginf(gv[1]) & (gi[1] >= 0), gi[1] == -1
+            assert nan.any() and ninf.any() and (k == 600 or unfilled.any())
+            assert np.flatnonzero(ninf).max() < np.flatnonzero(nan).min()
+            assert not unfilled.any() or np.flatnonzero(nan).max() < np.flatnonzero(unfilled).min()
+
+
 # ------------------------------------------------------------------------------------------------ through the class
 @pytest.fixture(scope="module")
 def corpus():
@@ -376,6 +480,8 @@ def test_invalid_arguments_return_an_error_without_a_launch(gpu_ctx):
         assert scan(**bad) == _ffi.PVS_ERR_INVALID, bad
         assert lib.pvs_last_error()
     assert scan(nq=0, idx=None, val=None) == _ffi.PVS_OK               # nq == 0 is a no-op
+    wide = np.arange(1027, dtype=np.int64)                             # nlist = 1026, one row per list: the limit is 1024 probes
+    assert scan(nprobe=1025, nlist=1026, h_off=wide) == _ffi.PVS_ERR_INVALID and lib.pvs_last_error()
 
     def assign(x=p, n=5, d=4, cent=p + 4096, nlist=3, lst=p + 8192, res=p + 12288):
         return lib.pvs_ivf_assign_dev(h, vp(x), n, d, vp(cent), nlist, vp(lst), vp(res))
