@@ -106,9 +106,6 @@ int assign_tiles_for(int K);  // vlad.hip
 
 using namespace pvs;
 
-#define PVS_NEED(p, what) \
-  if (!(p)) PVS_FAIL(PVS_ERR_INVALID, "%s: null %s", __func__, what)
-
 // ================================================================================ context
 PVS_EXPORT int pvs_version(void) { return PVS_VERSION; }
 PVS_EXPORT const char* pvs_last_error(void) { return g_err; }

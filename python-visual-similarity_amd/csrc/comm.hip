@@ -131,11 +131,8 @@ static int load_rccl() {
 
 using namespace pvs;
 
-#define PVS_NEEDC(p, what) \
-  if (!(p)) PVS_FAIL(PVS_ERR_INVALID, "%s: null %s", __func__, what)
-
 PVS_EXPORT int pvs_comm_unique_id(void* out_id) {
-  PVS_NEEDC(out_id, "id");
+  PVS_NEED(out_id, "id");
   PVS_TRY(load_rccl());
   ncclUniqueId id;
   PVS_NCCL(g_rccl.GetUniqueId(&id));
@@ -145,9 +142,9 @@ PVS_EXPORT int pvs_comm_unique_id(void* out_id) {
 }
 
 PVS_EXPORT int pvs_comm_init(pvs_ctx* ctx, int nranks, int rank, const void* unique_id, pvs_comm** out) {
-  PVS_NEEDC(ctx, "ctx");
-  PVS_NEEDC(unique_id, "unique id");
-  PVS_NEEDC(out, "out");
+  PVS_NEED(ctx, "ctx");
+  PVS_NEED(unique_id, "unique id");
+  PVS_NEED(out, "out");
   if (nranks < 1 || rank < 0 || rank >= nranks) PVS_FAIL(PVS_ERR_INVALID, "rank %d of %d", rank, nranks);
   PVS_TRY(load_rccl());
   PVS_HIP(hipSetDevice(ctx->device));
@@ -180,10 +177,10 @@ PVS_EXPORT int pvs_comm_destroy(pvs_comm* c) {
 PVS_EXPORT const char* pvs_comm_library(void) { return g_rccl.path.c_str(); }
 
 PVS_EXPORT int pvs_allgather_dev(pvs_comm* c, const void* d_send, void* d_recv, size_t bytes_per_rank) {
-  PVS_NEEDC(c, "comm");
+  PVS_NEED(c, "comm");
   if (bytes_per_rank == 0) return PVS_OK;
-  PVS_NEEDC(d_send, "send");
-  PVS_NEEDC(d_recv, "recv");
+  PVS_NEED(d_send, "send");
+  PVS_NEED(d_recv, "recv");
   PVS_HIP(hipSetDevice(c->ctx->device));
   // whole 16-B words when the size allows: fewer, wider elements for the ring kernels; bytes otherwise
   if (bytes_per_rank % 4 == 0) PVS_NCCL(g_rccl.AllGather(d_send, d_recv, bytes_per_rank / 4, ncclUint32, c->comm, c->ctx->stream));
@@ -192,10 +189,10 @@ PVS_EXPORT int pvs_allgather_dev(pvs_comm* c, const void* d_send, void* d_recv, 
 }
 
 PVS_EXPORT int pvs_alltoall_dev(pvs_comm* c, const void* d_send, void* d_recv, size_t bytes_per_rank) {
-  PVS_NEEDC(c, "comm");
+  PVS_NEED(c, "comm");
   if (bytes_per_rank == 0) return PVS_OK;
-  PVS_NEEDC(d_send, "send");
-  PVS_NEEDC(d_recv, "recv");
+  PVS_NEED(d_send, "send");
+  PVS_NEED(d_recv, "recv");
   PVS_HIP(hipSetDevice(c->ctx->device));
   const char* s = static_cast<const char*>(d_send);
   char* r = static_cast<char*>(d_recv);
@@ -211,9 +208,9 @@ PVS_EXPORT int pvs_alltoall_dev(pvs_comm* c, const void* d_send, void* d_recv, s
 
 PVS_EXPORT int pvs_sendrecv_dev(pvs_comm* c, int n_ops, const int* peers, const void* const* d_send, const size_t* send_bytes,
                                 void* const* d_recv, const size_t* recv_bytes) {
-  PVS_NEEDC(c, "comm");
+  PVS_NEED(c, "comm");
   if (n_ops <= 0) return PVS_OK;
-  PVS_NEEDC(peers, "peers");
+  PVS_NEED(peers, "peers");
   PVS_HIP(hipSetDevice(c->ctx->device));
   for (int i = 0; i < n_ops; ++i)
     if (peers[i] < 0 || peers[i] >= c->nranks) PVS_FAIL(PVS_ERR_INVALID, "peer %d out of range", peers[i]);
@@ -230,8 +227,8 @@ PVS_EXPORT int pvs_sendrecv_dev(pvs_comm* c, int n_ops, const int* peers, const 
 }
 
 PVS_EXPORT int pvs_allreduce_max_f64(pvs_comm* c, double* h_inout, int count) {
-  PVS_NEEDC(c, "comm");
-  PVS_NEEDC(h_inout, "values");
+  PVS_NEED(c, "comm");
+  PVS_NEED(h_inout, "values");
   if (count < 1 || count > 64) PVS_FAIL(PVS_ERR_INVALID, "1..64 values");
   pvs_ctx* ctx = c->ctx;
   PVS_HIP(hipSetDevice(ctx->device));

@@ -43,6 +43,12 @@ void set_error(const char* fmt, ...);
     if (s__ != PVS_OK) return s__;    \
   } while (0)
 
+// argument checks of the exported entry points
+#define PVS_NEED(p, what) \
+  if (!(p)) PVS_FAIL(PVS_ERR_INVALID, "%s: null %s", __func__, what)
+#define PVS_ALIGNED(p, a, what) \
+  if (reinterpret_cast<uintptr_t>(p) % (a)) PVS_FAIL(PVS_ERR_INVALID, "%s: %s must be %d-byte aligned", __func__, what, (int)(a))
+
 constexpr int WAVE = 64;
 
 enum TimerSlot { T_ASSIGN = 0, T_AGGREGATE = 1, T_GEMM = 2, T_TOPK = 3, T_FPOST = 4, T_FMOM = 5, T_MISC = 6, T_RESCORE = 7 };

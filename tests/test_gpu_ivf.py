@@ -50,7 +50,55 @@ def test_assign_and_residual_match_twin(gpu_ctx, n, d, nlist):
         b.free()
 
 
+@pytest.mark.parametrize("n,d,nlist", [(65, 64, 7), (1000, 5, 255)])
+def test_assignment_and_coarse_terms_equal_a_one_subspace_quantiser(gpu_ctx, n, d, nlist):
+    """one nearest-codeword kernel and one table kernel serve both entry points: the labels of pvs_ivf_assign_dev are the codes of
+    pvs_pq_encode_dev for the quantiser m = 1, ksub = nlist, dsub = d built from the same centroids, the coarse terms are its
+    table, and the residual is x - c[label], one float32 subtraction per element.  Centroid 1 is repeated as the last one."""
+    rng = np.random.default_rng(1050 + n)
+    cent = (rng.standard_normal((1, nlist, d)) * np.exp2(rng.integers(-20, 21, (1, nlist, 1)))).astype(np.float32)
+    cent[:, nlist - 1] = cent[:, 1]
+    x = cent[0][rng.integers(0, nlist, n)]
+    noisy = rng.random(n) < 0.5
+    x[noisy] *= (1 + 0.3 * rng.standard_normal((int(noisy.sum()), d))).astype(np.float32)
+    x[0] = cent[0, nlist - 1]
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    q = rng.standard_normal((3, d)).astype(np.float32)
+    table = gpu_ctx.pq(cent)
+    d_x, d_c, d_q = _up(gpu_ctx, x), _up(gpu_ctx, cent[0]), _up(gpu_ctx, q)
+    d_l, d_r, d_codes = gpu_ctx.buffer(n * 4), gpu_ctx.buffer(n * d * 4), gpu_ctx.buffer(max(n, 16))
+    d_co, d_lut = gpu_ctx.buffer(3 * nlist * 4), gpu_ctx.buffer(3 * nlist * 4)
+    gpu_ctx.ivf_assign_dev(d_x.ptr, n, d, d_c.ptr, nlist, d_l.ptr, d_r.ptr)
+    gpu_ctx.pq_encode_dev(table, d_x.ptr, n, d_codes.ptr)
+    gpu_ctx.ivf_coarse_dev(d_q.ptr, 3, d, d_c.ptr, nlist, d_co.ptr)
+    gpu_ctx.pq_lut_dev(table, d_q.ptr, 3, d_lut.ptr)
+    labels, codes = d_l.download((n,), np.int32), d_codes.download((n,), np.uint8)
+    assert np.array_equal(labels, codes.astype(np.int32))
+    assert np.array_equal(labels, iv.assign(x, cent[0])[0]) and labels[0] == 1 and not (labels == nlist - 1).any()
+    assert np.array_equal(d_co.download((3, nlist), np.float32).view(np.uint32), d_lut.download((3, nlist), np.float32).view(np.uint32))
+    assert np.array_equal(_bits(d_r.download((n, d), np.float32)), _bits(x - cent[0][labels]))
+    table.close()
+    for b in (d_x, d_c, d_q, d_l, d_r, d_codes, d_co, d_lut):
+        b.free()
+
+
 # ------------------------------------------------------------------------------------------------ coarse terms, probes
+@pytest.mark.parametrize("nq,d,nlist", [(3, 2, 1000), (2, 3, 65536)])
+def test_coarse_terms_beyond_one_block_per_subspace(gpu_ctx, nq, d, nlist):
+    """the table kernel splits a sub-space's entries over blocks of 256: 1000 entries are four blocks with a ragged last one,
+    65536 (the limit of nlist) are 256 blocks"""
+    rng = np.random.default_rng(1150 + nq)
+    cent = (rng.standard_normal((nlist, d)) * np.exp2(rng.integers(-6, 7, (nlist, 1)))).astype(np.float32)
+    q = rng.standard_normal((nq, d)).astype(np.float32)
+    d_q, d_c, d_o = _up(gpu_ctx, q), _up(gpu_ctx, cent), gpu_ctx.buffer(nq * nlist * 4 + 16).fill_bytes(0x5A)
+    gpu_ctx.ivf_coarse_dev(d_q.ptr, nq, d, d_c.ptr, nlist, d_o.ptr)
+    got = d_o.download((nq * nlist + 4,), np.float32)
+    assert np.array_equal(_bits(got[:-4].reshape(nq, nlist)), _bits(iv.coarse(q, cent)))
+    assert (got[-4:].view(np.uint8) == 0x5A).all()
+    for b in (d_q, d_c, d_o):
+        b.free()
+
+
 @pytest.mark.parametrize("nq,d,nlist", [(1, 2, 1), (5, 64, 7), (130, 257, 300)])
 def test_coarse_terms_and_probes_match_twin(gpu_ctx, nq, d, nlist):
     rng = np.random.default_rng(1100 + nq)
@@ -86,17 +134,20 @@ def _hand_lists(rng, N, nlist):
     return lists
 
 
-def _search(ctx, table, co, nprobe, off, ids, codes, inv_q, inv_db, k):
-    """the probes by pvs_topk_dev, then pvs_ivf_scan_topk_dev -> (idx, val)"""
+def _search(ctx, table, co, nprobe, off, ids, codes, inv_q, inv_db, k, code_offset=0):
+    """the probes by pvs_topk_dev, then pvs_ivf_scan_topk_dev -> (idx, val); code_offset: the codes start that many bytes into
+    their 16-byte aligned buffer (padded when not 0; otherwise the buffer ends at the last code)"""
     nq, m, ksub = table.shape
     nlist = co.shape[1]
-    bufs = [_up(ctx, table), _up(ctx, co), ctx.buffer(nq * nprobe * 8), ctx.buffer(nq * nprobe * 4), _up(ctx, off), _up(ctx, codes),
+    d_codes = ctx.buffer(codes.nbytes + 64).fill_bytes(0).upload(codes, offset=code_offset) if code_offset else _up(ctx, codes)
+    bufs = [_up(ctx, table), _up(ctx, co), ctx.buffer(nq * nprobe * 8), ctx.buffer(nq * nprobe * 4), _up(ctx, off), d_codes,
             _up(ctx, ids), ctx.buffer(nq * k * 8), ctx.buffer(nq * k * 4)]
+    assert bufs[5].ptr % 16 == 0
     d_t, d_co, d_pi, d_pv, d_off, d_codes, d_ids, d_idx, d_val = bufs
     d_iq = _up(ctx, inv_q) if inv_q is not None else None
     d_id = _up(ctx, inv_db) if inv_db is not None else None
     ctx.topk_dev(d_co.ptr, nq, nlist, nlist, nprobe, 0, False, d_pi.ptr, d_pv.ptr)
-    ctx.ivf_scan_topk_dev(d_t.ptr, nq, m, ksub, d_pi.ptr, d_pv.ptr, nprobe, d_off.ptr, off, nlist, d_codes.ptr, d_ids.ptr,
+    ctx.ivf_scan_topk_dev(d_t.ptr, nq, m, ksub, d_pi.ptr, d_pv.ptr, nprobe, d_off.ptr, off, nlist, d_codes.ptr + code_offset, d_ids.ptr,
                           d_iq.ptr if d_iq else None, d_id.ptr if d_id else None, k, d_idx.ptr, d_val.ptr)
     out = d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
     for b in bufs + [d_iq, d_id]:
@@ -116,9 +167,9 @@ def _scan_case(seed, nq, m, ksub, N, nlist):
     return table, co, off, ids, codes, inv_q, inv_db
 
 
-def _check(ctx, case, nprobe, k):
+def _check(ctx, case, nprobe, k, code_offset=0):
     table, co, off, ids, codes, inv_q, inv_db = case
-    gi, gv = _search(ctx, table, co, nprobe, off, ids, codes, inv_q, inv_db, k)
+    gi, gv = _search(ctx, table, co, nprobe, off, ids, codes, inv_q, inv_db, k, code_offset)
     wi, wv = iv.search(table, co, nprobe, off, ids, codes, inv_q, inv_db, k)
     assert np.array_equal(gi, wi), (nprobe, k)
     assert np.array_equal(_bits(gv), _bits(wv)), (nprobe, k)
@@ -140,6 +191,17 @@ def test_scan_and_ranking_match_twin(gpu_ctx, N, nlist, m, ksub, nq):
             gi = _check(gpu_ctx, case, nprobe, k)
             short = short or bool((gi == -1).any())
     assert short or N >= 4099                                      # k greater than the number of probed rows occurred
+
+
+@pytest.mark.parametrize("code_offset", [0, 4, 1])
+def test_scan_with_a_code_base_that_is_not_aligned(gpu_ctx, code_offset):
+    """m = 16 with the codes 0, 4 and 1 bytes into their buffer: the twin's lists at every offset, whichever load width the host
+    picks from the pointer.  The width itself (16, 4, 1 bytes) cannot be seen from here, a misaligned load returns the same
+    bytes; csrc/bench/scan_plan_check.cpp pins it"""
+    case = _scan_case(1250, 3, 16, 256, 65, 7)
+    for nprobe in (1, 3, 7):
+        for k in (1, 10, 100):
+            _check(gpu_ctx, case, nprobe, k, code_offset)
 
 
 def test_scan_queries_cross_the_query_block(gpu_ctx):

@@ -78,17 +78,22 @@ def test_table_matches_twin(gpu_ctx, m, dsub, ksub):
 
 
 # ------------------------------------------------------------------------------------------------ scan + top-k
-def _scan(ctx, lut, codes, k, inv_q=None, inv_db=None, col_offset=0, merge=False, lists=None):
+def _scan(ctx, lut, codes, k, inv_q=None, inv_db=None, col_offset=0, merge=False, lists=None, code_offset=0):
+    """code_offset: the codes start that many bytes into their (16-byte aligned, padded) buffer"""
     nq, m, ksub = lut.shape
     N = codes.shape[0]
-    d_l, d_c = _up(ctx, lut), _up(ctx, codes)
+    d_l, d_c = _up(ctx, lut), _up(ctx, codes)                      # the buffer ends at the last code
+    if code_offset:
+        d_c.free()
+        d_c = ctx.buffer(codes.nbytes + 64).fill_bytes(0).upload(codes, offset=code_offset)
+    assert d_c.ptr % 16 == 0
     d_iq = _up(ctx, inv_q) if inv_q is not None else None
     d_id = _up(ctx, inv_db) if inv_db is not None else None
     own = lists is None
     if own:
         lists = (ctx.buffer(nq * k * 8 + 64).fill_bytes(0x5A), ctx.buffer(nq * k * 4 + 64).fill_bytes(0x5A))
     d_idx, d_val = lists
-    ctx.pq_scan_topk_dev(d_l.ptr, nq, m, ksub, d_c.ptr, N, d_iq.ptr if d_iq else None, d_id.ptr if d_id else None, k, col_offset,
+    ctx.pq_scan_topk_dev(d_l.ptr, nq, m, ksub, d_c.ptr + code_offset, N, d_iq.ptr if d_iq else None, d_id.ptr if d_id else None, k, col_offset,
                          merge, d_idx.ptr, d_val.ptr)
     idx = d_idx.download((nq * k + 8,), np.int64)
     val = d_val.download((nq * k + 16,), np.float32)
@@ -150,6 +155,42 @@ def test_scan_at_and_across_the_lds_segment_limit(gpu_ctx, m, ksub):
     inv_db = np.ones(N, np.float32)
     for k in (1, 10, 257):
         idx, val, lists = _scan(gpu_ctx, lut, codes, k, None, inv_db)
+        _check_lists(idx, val, lut, codes, k, None, inv_db)
+        for b in lists:
+            b.free()
+
+
+@pytest.mark.parametrize("m,ksub", [(80, 256), (176, 256), (68, 256), (67, 256), (372, 100)])
+def test_scan_on_each_code_load_width(gpu_ctx, m, ksub):
+    """the generic walk (m > 64) on the shapes where the shared plan gives each load width: (80, 256) width 16, one segment;
+    (176, 256) width 16, two segments of 160 + 16 sub-spaces; (68, 256) width 4; (67, 256) single bytes; (372, 100) one segment
+    whose size, 409 sub-spaces, is no multiple of 4: width 4 since the two scans share one rule.  The flat scan reads 4 bytes at
+    a time from width 4 up; which loads a launch took cannot be seen from here, the lists are the twin's on all of them"""
+    rng = np.random.default_rng(450 + m)
+    N = 257
+    lut, codes = _scan_case(rng, 3, m, ksub, N)
+    inv_db = np.ones(N, np.float32)
+    for k in (1, 10, 257):
+        idx, val, lists = _scan(gpu_ctx, lut, codes, k, None, inv_db)
+        _check_lists(idx, val, lut, codes, k, None, inv_db)
+        for b in lists:
+            b.free()
+
+
+@pytest.mark.parametrize("m", [80, 64])
+@pytest.mark.parametrize("code_offset", [0, 4, 1])
+def test_scan_with_a_code_base_that_is_not_aligned(gpu_ctx, m, code_offset):
+    """the codes start 0, 4 or 1 bytes into a 16-byte aligned buffer (padded when offset): the lists are the twin's at every
+    offset, whichever load width the launcher picks from the pointer.  Which width that is cannot be seen from here (a misaligned
+    load returns the same bytes); csrc/bench/scan_plan_check.cpp pins the plan: width 16 / 4 / 1 at m = 80, and at m = 64 the
+    register path at offsets 0 and 4, single bytes at offset 1"""
+    rng = np.random.default_rng(470 + m)
+    N = 257
+    lut, codes = _scan_case(rng, 3, m, 256, N)
+    inv_db = (0.5 + rng.random(N)).astype(np.float32)
+    inv_db[codes_dupes(codes)] = np.float32(1.0)
+    for k in (1, 10, 257):
+        idx, val, lists = _scan(gpu_ctx, lut, codes, k, None, inv_db, code_offset=code_offset)
         _check_lists(idx, val, lut, codes, k, None, inv_db)
         for b in lists:
             b.free()

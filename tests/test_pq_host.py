@@ -242,3 +242,24 @@ def test_eval_rejects_full_ranking_of_a_compact_index():
         ev.retrieve_top_k_similar(np.zeros(4, np.float32), {"a": np.ones(4, np.float32)}, Identity(), k=1, rerank=3)
     with pytest.raises(ValueError, match="rerank=2 must be >= k=3"):           # not clamped up to k: the same error as rank()
         ev.retrieve_top_k_similar(np.zeros(4, np.float32), ci, Identity(), k=3, rerank=2)
+
+
+def test_scan_plan_matches_the_arithmetic_both_scans_carried(tmp_path):
+    """csrc/bench/scan_plan_check.cpp includes only pq_common.hpp, whose host part needs no HIP header: the segment size, the LDS
+    bytes and the code-load width of a scan against the closed forms the flat and the probed scan each carried inline, for the 40960-
+    and 36864-entry budgets, code bases at byte offsets 0, 4 and 1, and the (m, ksub) of the segment-limit cases of both GPU test
+    files; also the (m, ksub) range both scans accept.  Built with the address and undefined-behaviour sanitizers, no GPU."""
+    import os
+    import shutil
+    import subprocess
+
+    from conftest import REPO
+    src = os.path.join(REPO, "python-visual-similarity_amd", "csrc", "bench", "scan_plan_check.cpp")
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler (g++, c++ or clang++) on PATH"
+    exe = str(tmp_path / "scan_plan_check")
+    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", "-o", exe, src], capture_output=True, text=True, timeout=300)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr

@@ -51,7 +51,7 @@ def main():
 
     # real list sizes: k-means on a sample, every row assigned on the device
     rows = rng.standard_normal((n, d), dtype=np.float32)
-    cent = _fit_coarse(ctx, rows[:: max(1, n // 100000)], nlist, np.random.default_rng(15), 10)
+    cent = _fit_coarse(ctx, rows[:: max(1, n // 100000)], nlist, np.random.RandomState(15), 10)
     lists = np.empty(n, np.int32)
     d_c = ctx.buffer(cent.nbytes).upload(cent)
     for r0 in range(0, n, 1 << 17):
