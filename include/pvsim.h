@@ -65,7 +65,11 @@ typedef enum {
   PVS_OPT_FISHER_SCALE = 4,     /* division of a Fisher row by its norm: 0 (default) and 1: a second pass over the rows; 2: inside the      */
                                 /* moments kernel (one workgroup per image; 1.6 % less time, 1.7 x the bytes beyond L2 at configs[2]).     */
                                 /* Same bits.                                                                                             */
-  PVS_OPT_COUNT_ = 5
+  PVS_OPT_TRAIN_BATCH_CHUNKS = 5, /* rows per batch of the training passes (Lloyd step, label sums, Gram, EM step): 0 (default) from the  */
+                                /* workspace byte budgets; v in 1..1024: at most v chunks per batch (chunk = 4096 rows in the Lloyd step  */
+                                /* and the label sums, 8192 in the Gram pass, 2048 in the EM step), so that a test reaches the seam       */
+                                /* between two batches at a few thousand rows.  Same sums: chunks are added in chunk order either way.    */
+  PVS_OPT_COUNT_ = 6
 } pvs_option;
 
 typedef struct pvs_ctx pvs_ctx;

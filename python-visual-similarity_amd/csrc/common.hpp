@@ -80,7 +80,7 @@ struct pvs_ctx {
   // dynamic-LDS limits already raised on this context's device: kernel -> bytes
   std::map<const void*, int> lds_attr;
   // behaviour switches (pvs_set_option); defaults = the product path
-  int opt[PVS_OPT_COUNT_] = {1, 0, 0, 0, 0};
+  int opt[PVS_OPT_COUNT_] = {1, 0, 0, 0, 0, 0};
   unsigned int* d_queue = nullptr;   // image queue head of the fused encode (persistent workgroups)
   unsigned long long* d_fused_stamps = nullptr;   // non-null: fused launches run the stamped diagnostic kernel (pvs_fused_profile)
   // timers
@@ -270,6 +270,12 @@ int launch_fisher(pvs_ctx* ctx, const pvs_gmm* g, const void* d_desc, int kind, 
 
 // training (learn.hip / fisher.hip); x are plain fp32 rows (launch_materialise output), ld = D
 int launch_materialise(pvs_ctx* ctx, const void* d_desc, int kind, int64_t total, int D, float* d_out);
+// chunks per batch of a training pass: `budget` (what the pass's workspace byte budget allows, >= 1) unless
+// PVS_OPT_TRAIN_BATCH_CHUNKS caps it.  Chunk sums are added in chunk order, so the cap moves the batch seams and no sum.
+inline int64_t train_batch_chunks(const pvs_ctx* ctx, int64_t budget) {
+  const int cap = ctx->opt[PVS_OPT_TRAIN_BATCH_CHUNKS];
+  return cap > 0 && cap < budget ? cap : budget;
+}
 int launch_gmm_em_step(pvs_ctx* ctx, const pvs_gmm* g, const float* x, int ld, int64_t total, double* d_stats);
 int launch_kmeans_step(pvs_ctx* ctx, const pvs_codebook* cb, const float* x, int64_t total, int32_t* d_labels,
                        const int32_t* d_prev_labels, double* d_stats, float* d_sqdist);

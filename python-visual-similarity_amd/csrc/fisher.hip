@@ -121,10 +121,12 @@ int launch_pca(pvs_ctx* ctx, const pvs_pca* p, const void* d_desc, int kind, int
 }
 
 // ------------------------------------------------------------------------------------ K4 posterior
-// Block: PR descriptors x all K clusters.  Thread t owns clusters t, t+256, ...; the descriptor slab and its
+// Block: ROWS descriptors x all K clusters.  Thread t owns clusters t, t+256, ...; the descriptor slab and its
 // fp32 squares sit in LDS as fp64 pairs (broadcast reads); the (mu*prec, prec) tables are streamed from L2
 // in [d][k] order so that consecutive threads read consecutive addresses.
-constexpr int POST_ROWS = 32;
+constexpr int POST_ROWS = 32;       // descriptors per block up to POST_K32 clusters
+constexpr int POST_ROWS_WIDE = 16;  // ... above: the block's [rows][K] log-probabilities must fit the CU's 160 KiB of LDS
+constexpr int POST_K32 = 512;       // (64 * 32 * 16 + 32 * 512 * 8 = 160 KiB exactly; 64 * 16 * 16 + 16 * 1024 * 8 = 144 KiB)
 constexpr int POST_DK = 64;      // dims staged per step
 constexpr int POST_KMAX = 1024;  // clusters per block pass = 256 threads x 4
 
@@ -139,29 +141,30 @@ struct PostArgs {
   double* lse;          // [total] or null (training)
 };
 
+template <int ROWS>
 __global__ __launch_bounds__(256) void gmm_posterior_kernel(PostArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  double2* xs = reinterpret_cast<double2*>(smem);                    // [POST_DK][POST_ROWS]  (x, x*x)
-  double* lp = reinterpret_cast<double*>(xs + POST_DK * POST_ROWS);  // [POST_ROWS][K]
+  double2* xs = reinterpret_cast<double2*>(smem);                    // [POST_DK][ROWS]  (x, x*x)
+  double* lp = reinterpret_cast<double*>(xs + POST_DK * ROWS);  // [ROWS][K]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t r0 = (int64_t)blockIdx.x * POST_ROWS;
+  const int64_t r0 = (int64_t)blockIdx.x * ROWS;
   const int nkb = (a.K + 255) / 256;
 
   for (int kb = 0; kb < nkb; ++kb) {
     const int k = kb * 256 + tid;
     const bool kv = k < a.K;
-    double acc[POST_ROWS];
+    double acc[ROWS];
 #pragma unroll
-    for (int r = 0; r < POST_ROWS; ++r) acc[r] = 0.0;
+    for (int r = 0; r < ROWS; ++r) acc[r] = 0.0;
     for (int d0 = 0; d0 < a.D; d0 += POST_DK) {
       __syncthreads();
-      for (int idx = tid; idx < POST_DK * POST_ROWS; idx += 256) {
+      for (int idx = tid; idx < POST_DK * ROWS; idx += 256) {
         const int r = idx / POST_DK, dd = idx % POST_DK;  // consecutive threads -> consecutive dims of a row
         const int d = d0 + dd;
         float x = 0.f;
         if (r0 + r < a.total && d < a.D) x = a.X[(r0 + r) * a.ld + d];
         const float x2 = x * x;                           // squared in fp32, as X**2 on an fp32 array
-        xs[dd * POST_ROWS + r] = make_double2((double)x, (double)x2);
+        xs[dd * ROWS + r] = make_double2((double)x, (double)x2);
       }
       __syncthreads();
       const int dn = min(POST_DK, a.D - d0);
@@ -170,8 +173,8 @@ __global__ __launch_bounds__(256) void gmm_posterior_kernel(PostArgs a) {
           const double m = a.mupT[(int64_t)(d0 + dd) * a.K + k];
           const double p = -0.5 * a.precT[(int64_t)(d0 + dd) * a.K + k];
 #pragma unroll
-          for (int r = 0; r < POST_ROWS; ++r) {
-            const double2 v = xs[dd * POST_ROWS + r];
+          for (int r = 0; r < ROWS; ++r) {
+            const double2 v = xs[dd * ROWS + r];
             acc[r] = fma(v.x, m, fma(v.y, p, acc[r]));
           }
         }
@@ -180,12 +183,12 @@ __global__ __launch_bounds__(256) void gmm_posterior_kernel(PostArgs a) {
     if (kv) {
       const double c = a.cst[k];
 #pragma unroll
-      for (int r = 0; r < POST_ROWS; ++r) lp[r * a.K + k] = acc[r] + c;
+      for (int r = 0; r < ROWS; ++r) lp[r * a.K + k] = acc[r] + c;
     }
   }
   __syncthreads();
   // softmax over k, one wave per row (scipy logsumexp: max, log-sum-exp, subtract, exp)
-  for (int r = wave; r < POST_ROWS; r += 4) {
+  for (int r = wave; r < ROWS; r += 4) {
     if (r0 + r >= a.total) continue;
     double mx = -INFINITY;
     for (int k = lane; k < a.K; k += 64) mx = fmax(mx, lp[r * a.K + k]);
@@ -218,12 +221,17 @@ static int posterior_on(pvs_ctx* ctx, const pvs_gmm* g, const float* x, int ld, 
   hipLaunchKernelGGL(transpose_tables_kernel, dim3((unsigned)((kd + 255) / 256)), dim3(256), 0, ctx->stream, g->d_prec,
                      g->d_mup, g->K, g->D, precT, mupT);
   PostArgs a{x, total, g->D, ld, g->K, mupT, precT, g->d_const, d_resp, d_lse};
-  const size_t lds = (size_t)POST_DK * POST_ROWS * sizeof(double2) + (size_t)POST_ROWS * g->K * sizeof(double);
-  PVS_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gmm_posterior_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  // every (row, cluster) value is the same chain of operations whatever the rows per block, so both instances give the same bits
+  const bool wide = g->K > POST_K32;
+  const int rows = wide ? POST_ROWS_WIDE : POST_ROWS;
+  const size_t lds = (size_t)POST_DK * rows * sizeof(double2) + (size_t)rows * g->K * sizeof(double);
+  const void* fn = wide ? reinterpret_cast<const void*>(gmm_posterior_kernel<POST_ROWS_WIDE>)
+                        : reinterpret_cast<const void*>(gmm_posterior_kernel<POST_ROWS>);
+  PVS_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   ScopedTimer tm(ctx, T_FPOST);
-  hipLaunchKernelGGL(gmm_posterior_kernel, dim3((unsigned)((total + POST_ROWS - 1) / POST_ROWS)), dim3(256), lds,
-                     ctx->stream, a);
+  const dim3 grid((unsigned)((total + rows - 1) / rows));
+  if (wide) hipLaunchKernelGGL(gmm_posterior_kernel<POST_ROWS_WIDE>, grid, dim3(256), lds, ctx->stream, a);
+  else hipLaunchKernelGGL(gmm_posterior_kernel<POST_ROWS>, grid, dim3(256), lds, ctx->stream, a);
   PVS_HIP(hipGetLastError());
   return PVS_OK;
 }
@@ -1001,7 +1009,7 @@ int launch_gmm_em_step(pvs_ctx* ctx, const pvs_gmm* g, const float* x, int ld, i
   constexpr int CHUNK = 2048;
   const int nslab = (K + PM_COLS - 1) / PM_COLS;   // the moments kernel takes 256 components at a time
   const int64_t len = (int64_t)K * 2 * D;
-  const int64_t rows_per_batch = std::max<int64_t>(CHUNK, (((int64_t)2 << 30) / ((int64_t)K * 8)) / CHUNK * CHUNK);
+  const int64_t rows_per_batch = CHUNK * train_batch_chunks(ctx, std::max<int64_t>(1, (((int64_t)2 << 30) / ((int64_t)K * 8)) / CHUNK));
   const int dblocks = (D + MM_DIMS - 1) / MM_DIMS;
   int first = 1;
   for (int64_t t0 = 0; t0 < total; t0 += rows_per_batch) {

@@ -125,7 +125,7 @@ int launch_kmeans_step(pvs_ctx* ctx, const pvs_codebook* cb, const float* x, int
   if (total <= 0) PVS_FAIL(PVS_ERR_INVALID, "k-means needs at least one descriptor");
   if (K > 2048) PVS_FAIL(PVS_ERR_UNSUPPORTED, "K = %d exceeds the device k-means limit (2048)", K);
   const int64_t len = (int64_t)K * D;
-  const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4));
+  const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * train_batch_chunks(ctx, std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4)));
   pvs_norm_params prm{1.0, 2.0, 0.0};
   int first = 1;
   if (D > AGG_D_MAX) {   // long rows: labels, then the per-label residual sums directly in fp64
@@ -186,7 +186,7 @@ int launch_label_sums(pvs_ctx* ctx, const float* x, int64_t total, int D, const 
   if (K > 2048) PVS_FAIL(PVS_ERR_UNSUPPORTED, "K = %d exceeds the device limit (2048)", K);
   if (D > AGG_D_MAX) return launch_label_residual(ctx, x, total, D, d_labels, K, nullptr, square, d_out);
   const int64_t len = (int64_t)K * D;
-  const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4));
+  const int64_t rows_per_batch = (int64_t)LEARN_CHUNK * train_batch_chunks(ctx, std::max<int64_t>(1, ((int64_t)1 << 30) / (len * 4)));
   float* zero = nullptr;
   PVS_TRY(ws_reserve(ctx, WS_PROJECTED, (size_t)len * 4, &zero));
   PVS_HIP(hipMemsetAsync(zero, 0, (size_t)len * 4, ctx->stream));
@@ -285,7 +285,7 @@ int launch_gram(pvs_ctx* ctx, const float* x, int64_t total, int D, double* d_ou
   const int ntile = (D + 63) / 64;
   const int64_t tl = (int64_t)ntile * ntile * 4096;
   const int64_t nchunk_all = (total + GRAM_ROWS - 1) / GRAM_ROWS;
-  const int64_t per_batch = std::max<int64_t>(1, ((int64_t)1 << 30) / (tl * 8));
+  const int64_t per_batch = train_batch_chunks(ctx, std::max<int64_t>(1, ((int64_t)1 << 30) / (tl * 8)));
   double* acc = nullptr;
   PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, (size_t)tl * 8, &acc));
   int first = 1;
