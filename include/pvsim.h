@@ -69,7 +69,10 @@ typedef enum {
                                 /* workspace byte budgets; v in 1..1024: at most v chunks per batch (chunk = 4096 rows in the Lloyd step  */
                                 /* and the label sums, 8192 in the Gram pass, 2048 in the EM step), so that a test reaches the seam       */
                                 /* between two batches at a few thousand rows.  Same sums: chunks are added in chunk order either way.    */
-  PVS_OPT_COUNT_ = 6
+  PVS_OPT_UPDATE_WINDOW_ROWS = 6, /* source rows per window of the in-place pvs_compact_rows_dev: 0 (default) what the staging byte budget  */
+                                /* holds; v in 1..2^20: at most v rows, so that a test reaches a window seam with a few hundred rows.      */
+                                /* Same bytes: the windows move the rows, they compute nothing.                                          */
+  PVS_OPT_COUNT_ = 7
 } pvs_option;
 
 typedef struct pvs_ctx pvs_ctx;
@@ -510,6 +513,60 @@ int pvs_combine_rows_dev(pvs_ctx* ctx, const void* d_X, int64_t N, int64_t L, in
                          const void* d_self /*[n][L] or NULL*/, const void* d_w_self /*[n], NULL = 1*/,
                          const int64_t* d_idx /*[n][r]*/, const void* d_w /*[n][r]*/, int64_t n, int r,
                          void* d_out /*[n][L]*/);
+
+/* ---------------------------------------------------------------- index maintenance: add and remove rows without a rebuild
+ * An index is an ordered sequence of (path, row); the ORIGINAL INDEX of a row is its position in that sequence.
+ *   add      new rows are appended in the order given and get the original indices N, N + 1, ...
+ *   remove   the named rows leave, the others keep their relative order: the original index of a surviving row falls by the number
+ *            of removed rows that stood before it.
+ *   invariant  after any sequence of adds and removes every array of the index equals, byte for byte, the one an index built from
+ *            scratch from the surviving rows in surviving order with the same tables (projection, codebooks, coarse centroids)
+ *            holds.  Updates retrain nothing.
+ * The entry points below are data movement and integer counting: no floating-point arithmetic, no atomics, every output element
+ * written once.  They enqueue on the context's stream and do not wait for it; n == 0 is a no-op except where stated.
+ *
+ *   keep mask      uint8 [n]; entry i != 0 means row i stays.
+ *   keep positions pos int64 [n + 1]: pos[i] = the number of j < i with keep[j] != 0, pos[n] = the number of kept rows.  A scan over
+ *                  tiles of PVS_SCAN_TILE flags in three levels and four launches for any n <= 2^31.
+ *   compaction     out[pos[i]] = rows[i] for every kept i, rows of row_bytes >= 1 bytes each.  Bytes of out past row pos[n] - 1 are
+ *                  not defined.  Rows move 16 bytes at a time where row_bytes and both base addresses are multiples of 16, and 8, 4, 2
+ *                  or 1 byte at a time otherwise: every row length and alignment is served. */
+#define PVS_SCAN_TILE 2048             /* flags of one scan tile; PVS_SCAN_TILE tiles make one block of the second level */
+/* d_keep[i] = 1 for i < n, then 0 at every d_removed[j], j < r (int64; an index outside [0, n) is skipped, repeats are harmless). */
+int pvs_keep_mask_dev(pvs_ctx* ctx, const int64_t* d_removed, int64_t r, int64_t n, uint8_t* d_keep);
+/* d_pos int64 [n + 1]; n == 0 writes pos[0] = 0.  0 <= n <= 2^31.  Uses the workspace for the partial sums. */
+int pvs_keep_positions_dev(pvs_ctx* ctx, const uint8_t* d_keep, int64_t n, int64_t* d_pos);
+/* d_pos as pvs_keep_positions_dev gives it for d_keep.  d_out disjoint from d_rows: one pass over the rows.  d_out == d_rows: in
+ * place.  The rows before `first` are not touched; `first` must not exceed the index of the first removed row (0 is always valid; it
+ * only saves traffic, and is ignored out of place).  The rest moves window by window: the kept rows of source rows [a, b) are
+ * gathered into a staging block of the workspace (at most 64 MiB, or one row; PVS_OPT_UPDATE_WINDOW_ROWS caps the window), then
+ * written to rows [pos[a], pos[b]).  pos[b] <= b, so a window never writes at or beyond the next window's first source row, and
+ * the launches are ordered by the stream: extra device memory does not depend on n.  Any other overlap of d_out with d_rows, and
+ * any overlap of d_out with d_keep or d_pos, is PVS_ERR_INVALID, found on the host before anything is launched. */
+int pvs_compact_rows_dev(pvs_ctx* ctx, const void* d_rows, int64_t n, int64_t row_bytes, const uint8_t* d_keep, const int64_t* d_pos,
+                         int64_t first, void* d_out);
+/* Inverted-list insert (storage of section 14).  The n stored rows (d_codes uint8 [n][m], d_inv_db float32 [n], d_ids int32 [n],
+ * list_off int64 [nlist + 1], in (list, original index) order) and b new rows in ARRIVAL order (d_new_codes [b][m], d_new_inv [b];
+ * new row p gets the id n + p) are merged into the d_out_* arrays of n + b rows, again in (list, original index) order: the rows of
+ * list l are its old rows followed by its new rows in arrival order, because every new id exceeds every old one.  The caller
+ * supplies, from the b list numbers: new_off int64 [nlist + 1], the cumulative count of new rows per list (new_off[0] = 0,
+ * new_off[nlist] = b), and d_perm int32 [b], the new rows sorted by (list, arrival).  h_list_off and h_new_off are HOST copies of
+ * d_list_off and d_new_off: all sizing comes from them and nothing inside the call waits for the device; they must agree.
+ * d_out_list_off[l] = list_off[l] + new_off[l].  n + b < 2^31.  Every output must be disjoint from every input (PVS_ERR_INVALID).
+ * n + b == 0 writes the offsets only. */
+int pvs_ivf_insert_dev(pvs_ctx* ctx, int m, int nlist, const uint8_t* d_codes, const float* d_inv_db, const int32_t* d_ids,
+                       const int64_t* d_list_off, const int64_t* h_list_off, const uint8_t* d_new_codes, const float* d_new_inv,
+                       const int64_t* d_new_off, const int64_t* h_new_off, const int32_t* d_perm, uint8_t* d_out_codes,
+                       float* d_out_inv, int32_t* d_out_ids, int64_t* d_out_list_off);
+/* Inverted-list remove.  d_keep uint8 [n] and d_pos int64 [n + 1] are indexed by ORIGINAL index.  Stored row i survives iff
+ * keep[ids[i]] != 0, its new id is pos[ids[i]], and the survivors keep their stored order: codes, norms and ids are compacted into
+ * the d_out_* arrays (disjoint from the inputs), and d_out_list_off[l] = the number of surviving stored rows before list_off[l].
+ * n < 2^31; n == 0 writes zero offsets. */
+int pvs_ivf_remove_dev(pvs_ctx* ctx, int m, int nlist, int64_t n, const uint8_t* d_codes, const float* d_inv_db, const int32_t* d_ids,
+                       const int64_t* d_list_off, const uint8_t* d_keep, const int64_t* d_pos, uint8_t* d_out_codes, float* d_out_inv,
+                       int32_t* d_out_ids, int64_t* d_out_list_off);
+/* bytes from d_src to d_dst on the context's stream (growing a buffer); overlapping ranges are PVS_ERR_INVALID. */
+int pvs_copy_dev(pvs_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);
 
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,

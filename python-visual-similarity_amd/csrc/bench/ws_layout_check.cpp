@@ -1,6 +1,6 @@
 // Host-only check of workspace.hpp (tests/test_workspace_host.py builds it with -fsanitize=address,undefined and runs it):
 // the generic properties of WsLayout, then four call sites held offset for offset against the closed-form byte arithmetic those sites
-// carried inline before they were written with the layout.  Exit status 0 = every check held.
+// carried inline before they were written with the layout, and the blocks of update.hip against theirs.  Exit status 0 = every check held.
 #include <cstdio>
 #include <memory>
 
@@ -112,6 +112,20 @@ static void sift_site(size_t nc) {
   CHECK(f.bytes == closed + (nc % 2 ? 8 : 0), "SIFT candidate block n_cand=%zu: %zu bytes against %zu", nc, f.bytes, closed);
 }
 
+// the index-maintenance blocks (update.hip): scan partials, and the stored-order mask and positions in front of them
+static void update_sites(size_t n, size_t tile) {
+  const size_t ntiles = (n + tile - 1) / tile;
+  const UpdateScanLayout u = update_scan_layout(ntiles, tile);
+  CHECK(u.tile.off == 0 && u.block.off == al(ntiles * 8) && u.top.off == al(ntiles * 8) + al(tile * 8) &&
+            u.bytes == al(ntiles * 8) + al(tile * 8) + 256,
+        "scan partials n=%zu tile=%zu", n, tile);
+  const IvfRemoveLayout r = ivf_remove_layout(n, ntiles, tile);
+  const size_t o_pos = al(n), o_tile = o_pos + al((n + 1) * 8), o_block = o_tile + al(ntiles * 8), o_top = o_block + al(tile * 8);
+  CHECK(r.keep.off == 0 && r.pos.off == o_pos && r.tile.off == o_tile && r.block.off == o_block && r.top.off == o_top && r.bytes == o_top + 256,
+        "list-remove block n=%zu tile=%zu", n, tile);
+  CHECK(update_stage_bytes(n, 3) == al(n * 3), "staging block of %zu rows", n);
+}
+
 int main() {
   generic_align<256>();
   generic_align<16>();
@@ -134,6 +148,8 @@ int main() {
             kmeanspp_site(total, D, c, t);
             kmeanspp_site(total2, D, c, t);
           }
+  for (size_t N : Ns) update_sites(N, 2048);
+  for (size_t N : rows) update_sites(N, 64);
   for (size_t nc : rows) sift_site(nc);
   for (size_t nc : Ns) sift_site(nc);
 

@@ -66,7 +66,7 @@ struct pvs_ctx {
   bool owns_stream = false;
   int num_cu = 256;
   // grow-only scratch areas (device), one per pvs::WsSlot: who reserves which, and when a pointer into one dies, is the table in workspace.hpp
-  static constexpr int NWS = 17;
+  static constexpr int NWS = 18;
   void* ws[NWS] = {};
   size_t ws_bytes[NWS] = {};
   // cached tile lists of the similarity GEMM, one per GEMM model (cosine.hip): a context is one device + one stream, so the
@@ -80,7 +80,7 @@ struct pvs_ctx {
   // dynamic-LDS limits already raised on this context's device: kernel -> bytes
   std::map<const void*, int> lds_attr;
   // behaviour switches (pvs_set_option); defaults = the product path
-  int opt[PVS_OPT_COUNT_] = {1, 0, 0, 0, 0, 0};
+  int opt[PVS_OPT_COUNT_] = {1, 0, 0, 0, 0, 0, 0};
   unsigned int* d_queue = nullptr;   // image queue head of the fused encode (persistent workgroups)
   unsigned long long* d_fused_stamps = nullptr;   // non-null: fused launches run the stamped diagnostic kernel (pvs_fused_profile)
   // timers

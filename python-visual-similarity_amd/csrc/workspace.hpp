@@ -8,7 +8,7 @@ struct pvs_ctx;
 
 namespace pvs {
 
-// A context keeps 17 grow-only blocks of device memory (pvs_ctx::ws).  ws_reserve(ctx, slot, bytes, &p) hands out the slot's block,
+// A context keeps 18 grow-only blocks of device memory (pvs_ctx::ws).  ws_reserve(ctx, slot, bytes, &p) hands out the slot's block,
 // and when the block is too small it waits for the stream, FREES the block and allocates a larger one.  Hence the rule:
 //
 //   A pointer into a slot is dead once anything that may reserve the same slot has been called; re-reserve after such a call.
@@ -37,10 +37,12 @@ namespace pvs {
 //   WS_MATCH_TABLE    match.hip: upload_pairs, pvs_match_u8_dev
 //   WS_VERIFY_POINTS, WS_VERIFY_SMALL    match.hip: pvs_verify_dev
 //   WS_IVF_CANDIDATES ivf.hip: pvs_ivf_scan_topk_dev (candidate scores | candidate ids of one query block)
+//   WS_UPDATE         update.hip: pvs_keep_positions_dev (scan partials), pvs_compact_rows_dev in place (staging rows of one window),
+//                     pvs_ivf_insert_dev (source of every merged row), pvs_ivf_remove_dev (stored keep mask | positions | scan partials)
 enum WsSlot : int {
   WS_STAGE_IN = 0, WS_SCRATCH = 1, WS_PANEL_OUT = 2, WS_PROJECTED = 3, WS_AUX_ROWS = 4, WS_FP16_ROWS = 5, WS_LISTS = 6, WS_NB_NORMS = 7,
   WS_NB_F64_ROWS = 8, WS_DSIFT_TABLE = 9, WS_SIFT_PYRAMID = 10, WS_SIFT_TABLES = 11, WS_SIFT_KEYPOINTS = 12, WS_MATCH_TABLE = 13,
-  WS_VERIFY_POINTS = 14, WS_VERIFY_SMALL = 15, WS_IVF_CANDIDATES = 16
+  WS_VERIFY_POINTS = 14, WS_VERIFY_SMALL = 15, WS_IVF_CANDIDATES = 16, WS_UPDATE = 17
 };
 
 int ws_reserve(pvs_ctx* ctx, WsSlot which, size_t bytes, void** out);   // api.hip
@@ -151,6 +153,30 @@ struct IvfCandLayout {
 inline IvfCandLayout ivf_cand_layout(size_t QB, size_t W) {
   WsLayout<> l;
   return {l.add<float>(QB * W), l.add<int32_t>(QB * W), l.bytes()};
+}
+
+// pvs_keep_positions_dev, WS_UPDATE: kept flags per tile, per block of `tile` tiles (at most `tile` blocks), and the total
+struct UpdateScanLayout {
+  WsPiece<int64_t> tile, block, top;
+  size_t bytes;
+};
+inline UpdateScanLayout update_scan_layout(size_t ntiles, size_t tile) {
+  WsLayout<> l;
+  return {l.add<int64_t>(ntiles), l.add<int64_t>(tile), l.add<int64_t>(1), l.bytes()};
+}
+
+// pvs_compact_rows_dev in place, WS_UPDATE: the kept rows of one source window
+constexpr size_t update_stage_bytes(size_t window_rows, size_t row_bytes) { return ws_round(window_rows * row_bytes); }
+
+// pvs_ivf_remove_dev, WS_UPDATE: keep mask and positions in stored order, then the scan's partials
+struct IvfRemoveLayout {
+  WsPiece<uint8_t> keep;
+  WsPiece<int64_t> pos, tile, block, top;
+  size_t bytes;
+};
+inline IvfRemoveLayout ivf_remove_layout(size_t n, size_t ntiles, size_t tile) {
+  WsLayout<> l;
+  return {l.add<uint8_t>(n), l.add<int64_t>(n + 1), l.add<int64_t>(ntiles), l.add<int64_t>(tile), l.add<int64_t>(1), l.bytes()};
 }
 
 }  // namespace pvs

@@ -26,6 +26,8 @@ OPT_ASSIGN_PREFILTER, OPT_VLAD_PATH, OPT_TOPK_SELECT_ONLY, OPT_AGG_VARIANT, OPT_
 OPT_TRAIN_BATCH_CHUNKS = 5        # 0: training batches from the byte budgets; 1..1024: at most that many chunks per batch
 PIX_U8_RGB, PIX_U8_GRAY, PIX_F32_RGB, PIX_F32_GRAY = 0, 1, 2, 3          # pvs_pixel_kind
 DSIFT_U8, DSIFT_F32, DSIFT_F32_RAW, DSIFT_F32_QUANT = 0, 1, 2, 3                         # pvs_dsift_out
+OPT_UPDATE_WINDOW_ROWS = 6        # 0: windows of the in-place row compaction from the staging byte budget; 1..2^20: at most that many rows
+SCAN_TILE = 2048                  # PVS_SCAN_TILE of include/pvsim.h
 COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
 VLAD_PATH_AUTO, VLAD_PATH_GATHER, VLAD_PATH_STREAM, VLAD_PATH_FUSED = 0, 1, 2, 3
 TIMER_NAMES = ("assign", "aggregate", "cosine_gemm", "topk", "fisher_posterior", "fisher_moments", "misc", "rescore")
@@ -129,6 +131,12 @@ SIGNATURES = {
     "pvs_ivf_coarse_dev": [_vp, _vp, _i64, _int, _vp, _int, _vp],
     "pvs_ivf_scan_topk_dev": [_vp, _vp, _i64, _int, _int, _vp, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp],
     "pvs_combine_rows_dev": [_vp, _vp, _i64, _i64, _int, _vp, _vp, _vp, _vp, _i64, _int, _vp],
+    "pvs_keep_mask_dev": [_vp, _vp, _i64, _i64, _vp],
+    "pvs_keep_positions_dev": [_vp, _vp, _i64, _vp],
+    "pvs_compact_rows_dev": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp],
+    "pvs_ivf_insert_dev": [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pvs_ivf_remove_dev": [_vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pvs_copy_dev": [_vp, _vp, _vp, _sz],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

@@ -261,7 +261,9 @@ class CompactIndex:
 
     `projection` is None (d = L), a PCAModel (its components_ are used; no mean is subtracted) or an array (d, L);
     `projected` are the projected float32 rows (N, d), kept only for exact re-ranking (`rank(..., rerank=R)`).
-    The arrays are uploaded on first use."""
+    The arrays are uploaded on first use.  `add` and `remove` change the resident index without a rebuild:
+    new rows go through the entry points `fit` uses, rows move on the device, nothing is retrained, and every array and ranking
+    equals those of an index constructed from the surviving rows in surviving order with the same tables."""
 
     def __init__(self, paths, codes, inv_norms, quantizer, projection=None, projected=None, ctx=None):
         if not isinstance(quantizer, ProductQuantizer):
@@ -512,6 +514,155 @@ class CompactIndex:
             d_x.free()
             d_y.free()
 
+    # ---- updates
+    def _serials(self) -> dict:
+        """{path: serial number}.  A row's serial is fixed when it joins and serials rise with the original index, so the original
+        index of a row is the rank of its serial among the live ones (`self._live`, ascending): a remove deletes entries and
+        renumbers nothing, which keeps the interpreter's share of an update O(b) or O(r) beside one array copy."""
+        if getattr(self, "_serial", None) is None:
+            n = len(self._paths)
+            self._serial, self._live, self._next_serial = {p: i for i, p in enumerate(self._paths)}, np.arange(n, dtype=np.int64), n
+        return self._serial
+
+    def _check_new(self, source):
+        """-> (paths, float32 host rows (b, input_dim), the DeviceIndex they are resident in or None); touches no device"""
+        from .index import DeviceIndex
+        resident = source if isinstance(source, DeviceIndex) else None
+        paths = [str(p) for p in source.keys()]
+        if resident is not None:
+            mat = resident.matrix
+        else:
+            mat = np.array(list(source.values())) if paths else np.zeros((0, self.input_dim), np.float32)
+        mat = _f32_rows(mat, "new vectors")
+        if mat.shape[1] != self.input_dim:
+            raise ValueError(f"new vectors have {mat.shape[1]} dimensions, the index takes {self.input_dim}")
+        known, seen = self._serials(), set()
+        for p in paths:
+            if p in known:
+                raise ValueError(f"{p!r} is already indexed: remove it first")
+            if p in seen:
+                raise ValueError(f"{p!r} is named twice in one add")
+            seen.add(p)
+        self._check_size(len(self) + len(paths))
+        return paths, mat, resident
+
+    def _check_size(self, n: int) -> None:
+        pass
+
+    def _reserve_rows(self, dev: dict, name: str, row_bytes: int, used: int, need: int) -> None:
+        """room for `need` rows in dev[name], growing geometrically; the first `used` rows are copied on the device"""
+        buf = dev[name]
+        if buf.nbytes >= need * row_bytes:
+            return
+        new = self.context.buffer(max(need, 2 * (buf.nbytes // row_bytes)) * row_bytes)
+        if used:
+            self.context.copy_dev(new.ptr, buf.ptr, used * row_bytes)
+        dev[name] = new
+        buf.free()
+
+    def reserve(self, n: int) -> None:
+        """Room for n rows in the device buffers an `add` appends to (codes and norms of a flat index, the kept projected rows)."""
+        dev, used = self._device(), len(self)
+        for name, row_bytes in self._appended(dev):
+            self._reserve_rows(dev, name, row_bytes, used, int(n))
+
+    def _appended(self, dev: dict):
+        """(buffer name, bytes per row) of the arrays that grow by appending"""
+        q = self.quantizer
+        return [("codes", q.m), ("inv", 4)] + ([("projected", q.d * 4)] if self._keep else [])
+
+    def _encode_new(self, mat, resident, d_codes: int, d_inv: int, d_proj, d_lists, take):
+        """The b new rows through project -> row_inv_norms_dev -> (ivf_assign_dev + residual) -> pq_encode_dev, in chunks: codes
+        to d_codes, norms to d_inv, the projected rows to d_proj (or nowhere), list numbers to d_lists (an IVF index).  Raw device
+        addresses; `take(nbytes)` hands out temporaries the caller frees."""
+        ctx, dev, pq = self.context, self._device(), self.quantizer
+        d, m, L, table = pq.d, pq.m, self.input_dim, pq.table()
+        d_res = take(min(mat.shape[0], _CHUNK_ROWS) * d * 4) if d_lists is not None else None
+        for r0 in range(0, mat.shape[0], _CHUNK_ROWS):
+            rn = min(_CHUNK_ROWS, mat.shape[0] - r0)
+            src = resident._db.ptr + r0 * L * 4 if resident is not None else take(rn * L * 4).upload(mat[r0:r0 + rn]).ptr
+            if self._w is None and d_proj is None:
+                y = src                                            # no projection: the rows themselves, where they are
+            else:
+                y = d_proj + r0 * d * 4 if d_proj is not None else take(rn * d * 4).ptr
+                if self._w is None:
+                    ctx.copy_dev(y, src, rn * d * 4)
+                else:
+                    ctx.cosine_dev(src, rn, dev["w"].ptr, d, L, None, None, y, d)
+            ctx.row_inv_norms_dev(y, rn, d, d_inv + r0 * 4)
+            if d_lists is None:
+                ctx.pq_encode_dev(table, y, rn, d_codes + r0 * m)
+            else:
+                ctx.ivf_assign_dev(y, rn, d, dev["cent"].ptr, self.nlist, d_lists + r0 * 4, d_res.ptr)
+                ctx.pq_encode_dev(table, d_res.ptr, rn, d_codes + r0 * m)
+
+    def add(self, source) -> None:
+        """Append new images: `source` is {path: vector of input_dim} or a DeviceIndex whose resident rows are read in place.  They
+        get the original indices N, N + 1, ... in the order given.  A path that is already indexed is a ValueError, raised before
+        anything changes.  The projection, the codebooks (and the coarse centroids) stay as they are."""
+        paths, mat, resident = self._check_new(source)
+        if not paths:
+            return
+        dev, n, b = self._device(), len(self), len(paths)
+        temps = []
+
+        def take(nbytes):
+            temps.append(self.context.buffer(max(nbytes, 16)))
+            return temps[-1]
+
+        try:
+            for name, row_bytes in self._appended(dev):
+                self._reserve_rows(dev, name, row_bytes, n, n + b)
+            self._append(dev, mat, resident, n, take)
+        finally:
+            for t in temps:
+                t.free()
+        serial = self._serials()
+        for i, p in enumerate(paths):
+            serial[p] = self._next_serial + i
+        self._live = np.concatenate([self._live, np.arange(self._next_serial, self._next_serial + b, dtype=np.int64)])
+        self._next_serial += b
+        self._paths.extend(paths)
+        self._drop_caches(dev)
+
+    def _append(self, dev, mat, resident, n, take) -> None:
+        q = self.quantizer
+        self._encode_new(mat, resident, dev["codes"].ptr + n * q.m, dev["inv"].ptr + n * 4,
+                         dev["projected"].ptr + n * q.d * 4 if self._keep else None, None, take)
+
+    def remove(self, paths) -> None:
+        """The named images leave, the others keep their relative order; the original index of a survivor falls by the number of
+        removed rows before it.  An unknown path is a KeyError, a path named twice a ValueError, both raised before anything changes."""
+        from .index import _compact_list, _keep_positions, _removed_indices
+        paths = [paths] if isinstance(paths, str) else [str(p) for p in paths]
+        serial = self._serials()
+        idx = np.searchsorted(self._live, _removed_indices(paths, serial))       # serials -> original indices, ascending
+        if idx.size == 0:
+            return
+        ctx, dev, n = self.context, self._device(), len(self)
+        keep, pos = _keep_positions(ctx, idx, n)
+        try:
+            self._remove_stored(ctx, dev, n, idx, keep, pos)
+            if self._keep:
+                ctx.compact_rows_dev(dev["projected"].ptr, n, self.quantizer.d * 4, keep.ptr, pos.ptr, dev["projected"].ptr, first=int(idx[0]))
+        finally:
+            keep.free(), pos.free()
+        self._paths = _compact_list(self._paths, idx)
+        for p in paths:
+            del serial[p]
+        self._live = np.delete(self._live, idx)
+        self._drop_caches(dev)
+
+    def __delitem__(self, path) -> None:
+        self.remove([path])
+
+    def _remove_stored(self, ctx, dev, n, idx, keep, pos) -> None:
+        for name, row_bytes in (("codes", self.quantizer.m), ("inv", 4)):
+            ctx.compact_rows_dev(dev[name].ptr, n, row_bytes, keep.ptr, pos.ptr, dev[name].ptr, first=int(idx[0]))
+
+    def _drop_caches(self, dev) -> None:
+        """what was derived from the arrays an update has changed"""
+
     # ---- search
     def rank(self, query_vecs, k: int, rerank: int = 0):
         """-> (idx (nq, k) int64, val (nq, k) float32): the ADC ranking (score descending, index ascending); with rerank=R >= k
@@ -675,6 +826,18 @@ class IVFCompactIndex(CompactIndex):
             raise ValueError(f"ids must be a permutation of 0 .. {n - 1}")
         self._centroids, self._list_off, self._ids = np.ascontiguousarray(cent), off, np.ascontiguousarray(ids, dtype=np.int32)
 
+    @property
+    def _ids(self) -> np.ndarray:
+        """host copy of the stored rows' original indices: downloaded when `save`, a property or a check needs it after an update"""
+        if self._ids_host is None:
+            n = len(self)
+            self._ids_host = self._dev["ids"].download((n,), np.int32) if n else np.zeros(0, np.int32)
+        return self._ids_host
+
+    @_ids.setter
+    def _ids(self, ids):
+        self._ids_host = ids
+
     @classmethod
     def fit(cls, source, nlist: int, m: int = 64, n_components=None, projection=None, ksub: int = 256, keep_projected: bool = False,
             random_state=None, train=None, ctx=None, max_iter: int = 25) -> "IVFCompactIndex":
@@ -723,6 +886,57 @@ class IVFCompactIndex(CompactIndex):
             orig[self._ids] = stored
             dev["inv_orig"] = self.context.buffer(max(orig.nbytes, 16)).upload(orig)
         return dev["inv_orig"]
+
+    # ---- updates
+    def _check_size(self, n: int) -> None:
+        if n >= 2 ** 31:
+            raise ValueError(f"an IVF compact index holds fewer than 2^31 rows, got {n}")
+
+    def _appended(self, dev: dict):
+        """the stored arrays are merged into fresh buffers by every insert; only the kept rows grow by appending"""
+        return [("projected", self.quantizer.d * 4)] if self._keep else []
+
+    def _swap_stored(self, dev, codes, inv, ids, off, list_off) -> None:
+        for name, new in (("codes", codes), ("inv", inv), ("ids", ids), ("list_off", off)):
+            dev[name].free()
+            dev[name] = new
+        self._list_off, self._ids_host = list_off, None
+
+    def _append(self, dev, mat, resident, n, take) -> None:
+        """encode the new rows, sort their list numbers on the host (b entries), merge old and new storage on the device"""
+        ctx, q, nlist, b = self.context, self.quantizer, self.nlist, mat.shape[0]
+        d_codes, d_inv, d_lists = take(b * q.m), take(b * 4), take(b * 4)
+        self._encode_new(mat, resident, d_codes.ptr, d_inv.ptr, dev["projected"].ptr + n * q.d * 4 if self._keep else None, d_lists.ptr,
+                         take)
+        perm, new_off = _sort_into_lists(d_lists.download((b,), np.int32), nlist)
+        d_perm, d_new_off = take(perm.nbytes).upload(perm), take(new_off.nbytes).upload(new_off)
+        out = [ctx.buffer(max(nbytes, 16)) for nbytes in ((n + b) * q.m, (n + b) * 4, (n + b) * 4, (nlist + 1) * 8)]
+        try:
+            ctx.ivf_insert_dev(q.m, nlist, dev["codes"].ptr, dev["inv"].ptr, dev["ids"].ptr, dev["list_off"].ptr, self._list_off,
+                               d_codes.ptr, d_inv.ptr, d_new_off.ptr, new_off, d_perm.ptr, *(o.ptr for o in out))
+        except BaseException:
+            for o in out:
+                o.free()
+            raise
+        self._swap_stored(dev, *out, self._list_off + new_off)
+
+    def _remove_stored(self, ctx, dev, n, idx, keep, pos) -> None:
+        q, nlist, left = self.quantizer, self.nlist, n - idx.size
+        out = [ctx.buffer(max(nbytes, 16)) for nbytes in (left * q.m, left * 4, left * 4, (nlist + 1) * 8)]
+        try:
+            ctx.ivf_remove_dev(q.m, nlist, n, dev["codes"].ptr, dev["inv"].ptr, dev["ids"].ptr, dev["list_off"].ptr, keep.ptr, pos.ptr,
+                               *(o.ptr for o in out))
+            list_off = out[3].download((nlist + 1,), np.int64)
+        except BaseException:
+            for o in out:
+                o.free()
+            raise
+        self._swap_stored(dev, *out, list_off)
+
+    def _drop_caches(self, dev) -> None:
+        if dev.get("inv_orig") is not None:                # the norms in original order: remade on the next re-ranking
+            dev["inv_orig"].free()
+            dev["inv_orig"] = None
 
     # ---- search
     def rank(self, query_vecs, k: int, nprobe: int, rerank: int = 0):

@@ -465,6 +465,41 @@ class Context:
         check(_ffi.lib().pvs_combine_rows_dev(self.handle, ptr(d_x), N, L, int(bool(is_f64)), ptr(d_self), ptr(d_w_self), ptr(d_idx),
                                               ptr(d_w), n, r, ptr(d_out)))
 
+    # index maintenance
+    SCAN_TILE = _ffi.SCAN_TILE
+
+    def copy_dev(self, d_dst, d_src, nbytes):
+        check(_ffi.lib().pvs_copy_dev(self.handle, ptr(d_dst), ptr(d_src), int(nbytes)))
+
+    def keep_mask_dev(self, d_removed, r, n, d_keep):
+        """pvs_keep_mask_dev: keep[i] = 1 for i < n, then 0 at the r int64 indices of d_removed"""
+        check(_ffi.lib().pvs_keep_mask_dev(self.handle, ptr(d_removed), int(r), int(n), ptr(d_keep)))
+
+    def keep_positions_dev(self, d_keep, n, d_pos):
+        """pvs_keep_positions_dev: pos int64 (n + 1,), pos[i] = kept entries before i, pos[n] = the total"""
+        check(_ffi.lib().pvs_keep_positions_dev(self.handle, ptr(d_keep), int(n), ptr(d_pos)))
+
+    def compact_rows_dev(self, d_rows, n, row_bytes, d_keep, d_pos, d_out, first=0):
+        """pvs_compact_rows_dev: out[pos[i]] = rows[i] for kept i; d_out == d_rows compacts in place, leaving rows [0, first) alone"""
+        check(_ffi.lib().pvs_compact_rows_dev(self.handle, ptr(d_rows), int(n), int(row_bytes), ptr(d_keep), ptr(d_pos), int(first),
+                                              ptr(d_out)))
+
+    def ivf_insert_dev(self, m, nlist, d_codes, d_inv, d_ids, d_list_off, h_list_off, d_new_codes, d_new_inv, d_new_off, h_new_off,
+                       d_perm, d_out_codes, d_out_inv, d_out_ids, d_out_list_off):
+        """h_list_off, h_new_off: the host copies of the two offset arrays, C-contiguous int64 of nlist + 1 entries"""
+        h, hn = np.ascontiguousarray(h_list_off, dtype=np.int64), np.ascontiguousarray(h_new_off, dtype=np.int64)
+        if h.shape != (nlist + 1,) or hn.shape != (nlist + 1,):
+            raise ValueError(f"h_list_off and h_new_off must have nlist + 1 = {nlist + 1} entries, got shapes {h.shape}, {hn.shape}")
+        check(_ffi.lib().pvs_ivf_insert_dev(self.handle, int(m), int(nlist), ptr(d_codes), ptr(d_inv), ptr(d_ids), ptr(d_list_off), ptr(h),
+                                            ptr(d_new_codes), ptr(d_new_inv), ptr(d_new_off), ptr(hn), ptr(d_perm), ptr(d_out_codes),
+                                            ptr(d_out_inv), ptr(d_out_ids), ptr(d_out_list_off)))
+
+    def ivf_remove_dev(self, m, nlist, n, d_codes, d_inv, d_ids, d_list_off, d_keep, d_pos, d_out_codes, d_out_inv, d_out_ids,
+                       d_out_list_off):
+        check(_ffi.lib().pvs_ivf_remove_dev(self.handle, int(m), int(nlist), int(n), ptr(d_codes), ptr(d_inv), ptr(d_ids), ptr(d_list_off),
+                                            ptr(d_keep), ptr(d_pos), ptr(d_out_codes), ptr(d_out_inv), ptr(d_out_ids),
+                                            ptr(d_out_list_off)))
+
     def f32_to_f16_dev(self, d_src, n, d_dst):
         check(_ffi.lib().pvs_f32_to_f16_dev(self.handle, ptr(d_src), n, ptr(d_dst)))
 

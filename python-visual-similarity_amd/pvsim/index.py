@@ -45,6 +45,55 @@ def load_shards(directory: str):
     return vecs, [q for p in parts for q in p[2]]
 
 
+def _removed_indices(paths, pos: dict) -> np.ndarray:
+    """paths to remove -> their indices, ascending int64; KeyError for an unknown path, ValueError for one named twice"""
+    paths = [paths] if isinstance(paths, str) else list(paths)
+    seen = set()
+    for p in paths:
+        if p not in pos:
+            raise KeyError(p)
+        if p in seen:
+            raise ValueError(f"{p!r} is named twice in one remove")
+        seen.add(p)
+    return np.sort(np.array([pos[p] for p in paths], dtype=np.int64))
+
+
+def _keep_positions(ctx, idx: np.ndarray, n: int):
+    """ascending removed indices -> (keep mask uint8 (n,), positions int64 (n + 1,)) as device buffers: idx.size indices go up"""
+    d_idx = ctx.buffer(idx.nbytes).upload(idx)
+    keep, pos = ctx.buffer(max(n, 16)), ctx.buffer((n + 1) * 8)
+    try:
+        ctx.keep_mask_dev(d_idx.ptr, idx.size, n, keep.ptr)
+        ctx.keep_positions_dev(keep.ptr, n, pos.ptr)
+    except BaseException:
+        keep.free(), pos.free()
+        raise
+    finally:
+        d_idx.free()
+    return keep, pos
+
+
+def _compact_host_rows(buf: np.ndarray, n: int, idx: np.ndarray) -> None:
+    """rows idx (ascending) leave the first n rows of buf, in place: one block move per run of kept rows"""
+    dst = int(idx[0])
+    bounds = np.append(idx, n)
+    for j in range(idx.size):
+        a, b = int(bounds[j]) + 1, int(bounds[j + 1])
+        if b > a:
+            buf[dst:dst + b - a] = buf[a:b]
+            dst += b - a
+
+
+def _compact_list(items: list, idx: np.ndarray) -> list:
+    """the list without the entries at idx (ascending): one slice per run of kept entries"""
+    out, prev = [], 0
+    for i in idx.tolist():
+        out.extend(items[prev:i])
+        prev = i + 1
+    out.extend(items[prev:])
+    return out
+
+
 class DeviceIndex(Mapping):
     """An encoding map {image_path: vector} whose vectors ALSO live on the GPU, uploaded and normalised once.
 
@@ -56,7 +105,10 @@ class DeviceIndex(Mapping):
     and scores, bit for bit, as with the dict).  dtype rule of the reference (pyvisim/_utils.py:312-330): float32 scores iff the
     database AND the queries are float32, float64 otherwise.
     `rank_expanded` re-queries with the first results folded into the query, and `augmented` builds the index whose rows have their
-    neighbours folded in (pvsim/expand.py); both sum whole rows on the device."""
+    neighbours folded in (pvsim/expand.py); both sum whole rows on the device.
+    `add`, `remove` / `del index[path]` and `reserve` change the resident index without a rebuild: rows move
+    on the device, and after any sequence of them every array and every ranking equals those of DeviceIndex(dict of the surviving
+    rows in surviving order), bit for bit."""
 
     def __init__(self, encoding_map, ctx=None):
         from .engine import default_context
@@ -65,11 +117,11 @@ class DeviceIndex(Mapping):
         mat = np.array(list(encoding_map.values()))                      # as the reference builds it (eval.py:28)
         if mat.ndim != 2:
             raise ValueError("DeviceIndex needs one vector of the same length per entry")
-        self._host = np.ascontiguousarray(mat, dtype=np.float32 if mat.dtype == np.float32 else np.float64)
-        n, L = self._host.shape
-        self._db = self.ctx.buffer(max(self._host.nbytes, 16))
+        self._hbuf = np.ascontiguousarray(mat, dtype=np.float32 if mat.dtype == np.float32 else np.float64)
+        n, L = self._hbuf.shape
+        self._db = self.ctx.buffer(max(self._hbuf.nbytes, 16))
         if n and L:
-            self._db.upload(self._host)
+            self._db.upload(self._hbuf)
         self._finish()
 
     @classmethod
@@ -78,17 +130,47 @@ class DeviceIndex(Mapping):
         the Mapping serves and computes the norms with the kernel every index uses."""
         self = cls.__new__(cls)
         self.ctx, self._paths, self._db = ctx, list(paths), d_rows
-        self._host = d_rows.download((n, L), dtype) if n and L else np.zeros((n, L), dtype)
+        self._hbuf = d_rows.download((n, L), dtype) if n and L else np.zeros((n, L), dtype)
         self._finish()
         return self
 
+    @property
+    def _shape(self):
+        """(N, L) without touching the host mirror"""
+        return len(self._paths), self._hbuf.shape[1]
+
+    @property
+    def _host(self) -> np.ndarray:
+        """The first N rows of the host mirror.  A remove leaves the mirror as it was and notes what left (moving a gigabyte of host
+        rows would cost a hundred times what the device's compaction costs); adds behind it are noted too.  The notes are applied
+        here, in order, when someone asks for host rows."""
+        if self._pending:
+            n = self._mirror_rows
+            for op, arg in self._pending:
+                if op == "remove":
+                    _compact_host_rows(self._hbuf, n, arg)
+                    n -= arg.size
+                else:
+                    self._grow_mirror(n, n + arg.shape[0])
+                    self._hbuf[n:n + arg.shape[0]] = arg
+                    n += arg.shape[0]
+            self._pending, self._mirror_rows = [], n
+        return self._hbuf[:self._mirror_rows]
+
+    def _grow_mirror(self, used: int, need: int) -> None:
+        if need > self._hbuf.shape[0]:
+            grown = np.empty((max(need, self._cap), self._hbuf.shape[1]), self._hbuf.dtype)
+            grown[:used] = self._hbuf[:used]
+            self._hbuf = grown
+
     def _finish(self):
-        n, L = self._host.shape
+        n, L = self._shape
+        self._pending, self._mirror_rows, self._cap = [], n, n      # host-mirror notes, rows the mirror holds, rows the device buffers hold
         self._pos = {p: i for i, p in enumerate(self._paths)}
-        self._inv = self.ctx.buffer(max(n, 1) * self._host.itemsize)
+        self._inv = self.ctx.buffer(max(n, 1) * self._hbuf.itemsize)
         self._inv_host = None
         if n and L:
-            if self._host.dtype == np.float32:
+            if self._hbuf.dtype == np.float32:
                 self.ctx.row_inv_norms_dev(self._db.ptr, n, L, self._inv.ptr)
             else:
                 self.ctx.row_inv_norms_f64_dev(self._db.ptr, n, L, self._inv.ptr)
@@ -112,14 +194,98 @@ class DeviceIndex(Mapping):
     def inv_norms(self) -> np.ndarray:
         """(N,) host copy of the device's 1 / ||row||, in the index's dtype (downloaded once)."""
         if self._inv_host is None:
-            n, L = self._host.shape
-            self._inv_host = self._inv.download((n,), self._host.dtype) if n and L else np.zeros(n, self._host.dtype)
+            n, L = self._shape
+            self._inv_host = self._inv.download((n,), self._hbuf.dtype) if n and L else np.zeros(n, self._hbuf.dtype)
         return self._inv_host
+
+    # ---- updates (DESIGN.md section 15)
+    @property
+    def capacity(self) -> int:
+        """rows the device buffers hold without growing (the host mirror follows when it is next written)"""
+        return self._cap
+
+    def reserve(self, n: int) -> None:
+        """Room for n rows in the device row buffer and the norms, and in the host mirror (no-op when they already hold that many)."""
+        n = int(n)
+        used, L = self._shape
+        if n <= self._cap:
+            return
+        isz = self._hbuf.dtype.itemsize
+        for name, row_bytes in (("_db", L * isz), ("_inv", isz)):
+            old = getattr(self, name)
+            new = self.ctx.buffer(max(n * row_bytes, 16))
+            if used and row_bytes:
+                self.ctx.copy_dev(new.ptr, old.ptr, used * row_bytes)
+            setattr(self, name, new)
+            old.free()
+        self._cap = n
+        if not self._pending:
+            self._grow_mirror(used, n)
+
+    def add(self, encoding_map) -> None:
+        """Append the entries of {path: vector} in their order: they get the indices N, N + 1, ....  A path that is already indexed is
+        a ValueError, raised before anything changes (there is no in-place replace: remove first).  The rows go up once, and their
+        norms come from the kernel every index uses."""
+        paths = list(encoding_map.keys())
+        if not paths:
+            return
+        clash = [p for p in paths if p in self._pos]
+        if clash:
+            raise ValueError(f"{clash[0]!r} is already indexed ({len(clash)} such path(s)): remove it first")
+        n, L = self._shape
+        dt = self._hbuf.dtype
+        new = np.array(list(encoding_map.values()))
+        if new.ndim != 2 or new.shape[1] != L:
+            raise ValueError(f"new vectors must have the index's length {L}, got an array of shape {new.shape}")
+        if dt == np.float32 and new.dtype != np.float32:
+            raise TypeError(f"a float32 index takes float32 vectors, got {new.dtype}")
+        new = np.ascontiguousarray(new, dtype=dt)
+        b = new.shape[0]
+        if n + b > self._cap:
+            self.reserve(max(n + b, 2 * self._cap))
+        if self._pending:                                           # the mirror is behind: this add joins the notes
+            self._pending.append(("add", new))
+        else:
+            self._grow_mirror(n, n + b)
+            self._hbuf[n:n + b] = new
+            self._mirror_rows = n + b
+        if L:
+            isz = dt.itemsize
+            self._db.upload(new, offset=n * L * isz)
+            (self.ctx.row_inv_norms_dev if dt == np.float32 else self.ctx.row_inv_norms_f64_dev)(
+                self._db.ptr + n * L * isz, b, L, self._inv.ptr + n * isz)
+        for i, p in enumerate(paths):
+            self._pos[p] = n + i
+        self._paths.extend(paths)
+        self._inv_host = None
+
+    def remove(self, paths) -> None:
+        """The named entries leave; the others keep their order, as `del d[k]` on the dict does.  An unknown path is a KeyError, a
+        path named twice a ValueError, both raised before anything changes.  Rows and norms are compacted in place on the device."""
+        idx = _removed_indices(paths, self._pos)
+        if idx.size == 0:
+            return
+        n, L = self._shape
+        isz = self._hbuf.dtype.itemsize
+        if L:
+            keep, pos = _keep_positions(self.ctx, idx, n)
+            try:
+                self.ctx.compact_rows_dev(self._db.ptr, n, L * isz, keep.ptr, pos.ptr, self._db.ptr, first=int(idx[0]))
+                self.ctx.compact_rows_dev(self._inv.ptr, n, isz, keep.ptr, pos.ptr, self._inv.ptr, first=int(idx[0]))
+            finally:
+                keep.free(), pos.free()
+        self._pending.append(("remove", idx))
+        self._paths = _compact_list(self._paths, idx)
+        self._pos = {p: i for i, p in enumerate(self._paths)}
+        self._inv_host = None
+
+    def __delitem__(self, path) -> None:
+        self.remove([path])
 
     def _rank_dev(self, d_q: int, nq: int, k: int, want_inv: bool = False):
         """`rank` of nq rows of the index's dtype that are on the device (raw pointer) -> (idx, val[, 1 / ||q|| (nq,)])."""
-        n, L = self._host.shape
-        dt = self._host.dtype
+        n, L = self._shape
+        dt = self._hbuf.dtype
         isz = dt.itemsize
         d_invq = self.ctx.buffer(max(nq, 1) * isz)
         d_idx = self.ctx.buffer(nq * k * 8)
@@ -142,10 +308,10 @@ class DeviceIndex(Mapping):
 
     def _inv_norms_dev(self, d_q: int, nq: int) -> np.ndarray:
         """1 / ||row|| of nq device rows of the index's dtype, by the kernel the rankings use -> host (nq,)"""
-        dt = self._host.dtype
+        dt = self._hbuf.dtype
         d_inv = self.ctx.buffer(max(nq, 1) * dt.itemsize)
         try:
-            (self.ctx.row_inv_norms_dev if dt == np.float32 else self.ctx.row_inv_norms_f64_dev)(d_q, nq, self._host.shape[1], d_inv.ptr)
+            (self.ctx.row_inv_norms_dev if dt == np.float32 else self.ctx.row_inv_norms_f64_dev)(d_q, nq, self._shape[1], d_inv.ptr)
             return d_inv.download((nq,), dt)
         finally:
             d_inv.free()
@@ -153,13 +319,13 @@ class DeviceIndex(Mapping):
     def rank(self, query_vecs: np.ndarray, k: int):
         """-> (idx (nq, k) int64, val (nq, k)) of the queries against the resident database; 1 <= k <= N."""
         q = np.asarray(query_vecs)
-        n, L = self._host.shape
+        n, L = self._shape
         if q.ndim != 2 or q.shape[1] != L:
             raise ValueError("query and database dimensions differ")
-        f32 = self._host.dtype == np.float32 and q.dtype == np.float32
-        if not f32 and self._host.dtype == np.float32:                   # mixed dtypes: float64 scores from the host copies
+        f32 = self._hbuf.dtype == np.float32 and q.dtype == np.float32
+        if not f32 and self._hbuf.dtype == np.float32:                   # mixed dtypes: float64 scores from the host copies
             return self.ctx.cosine_topk_f64(q, self._host, int(k))
-        q = np.ascontiguousarray(q, dtype=self._host.dtype)
+        q = np.ascontiguousarray(q, dtype=self._hbuf.dtype)
         d_q = self.ctx.buffer(max(q.nbytes, 16)).upload(q)
         try:
             return self._rank_dev(d_q.ptr, q.shape[0], int(k))
@@ -173,18 +339,18 @@ class DeviceIndex(Mapping):
         inv = self.inv_norms
         filled = idx >= 0
         w = expansion_weights(val, scheme, alpha) * inv[np.where(filled, idx, 0)] if inv.size else np.zeros_like(val)
-        return np.ascontiguousarray(np.where(filled, w, self._host.dtype.type(0)))
+        return np.ascontiguousarray(np.where(filled, w, self._hbuf.dtype.type(0)))
 
     def _combine(self, d_self, w_self, idx, w, d_out):
         """pvs_combine_rows_dev of the resident rows: lists and weights go up, the rows stay where they are"""
         n, r = idx.shape
-        N, L = self._host.shape
+        N, L = self._shape
         bufs = [self.ctx.buffer(max(a.nbytes, 16)) for a in (w_self, idx, w)]
         try:
             for b, a in zip(bufs, (w_self, idx, w)):
                 if a.size:
                     b.upload(a)
-            self.ctx.combine_rows_dev(self._db.ptr, N, L, self._host.dtype == np.float64, d_self, bufs[0].ptr,
+            self.ctx.combine_rows_dev(self._db.ptr, N, L, self._hbuf.dtype == np.float64, d_self, bufs[0].ptr,
                                       bufs[1].ptr if r else None, bufs[2].ptr if r else None, n, r, d_out)
         finally:
             for b in bufs:
@@ -203,8 +369,8 @@ class DeviceIndex(Mapping):
         if not isinstance(qe, QueryExpansion):
             raise TypeError("qe must be a pvsim.expand.QueryExpansion")
         q = np.asarray(query_vecs)
-        N, L = self._host.shape
-        dt = self._host.dtype
+        N, L = self._shape
+        dt = self._hbuf.dtype
         if q.ndim != 2 or q.shape[1] != L:
             raise ValueError("query and database dimensions differ")
         if dt == np.float32 and q.dtype != np.float32:
@@ -250,13 +416,14 @@ class DeviceIndex(Mapping):
         """Database-side augmentation: a new DeviceIndex with the same paths in the same order, whose row i is
         x_i / |x_i| + sum_j w_j x_j / |x_j| over the min(r, N - 1) nearest other rows of this index (w_j from expansion_weights
         of their similarities to row i; "linear" falls from 1 to 1 / r with the rank).  Rows are ranked `block` at a time against
-        the whole index; only the lists and weights cross to the host.  This index is left as it is."""
+        the whole index; only the lists and weights cross to the host.  This index is left as it is.  The result is a separate
+        index: a later `add` or `remove` on this one does not reach it."""
         from .expand import _check_count, _check_scheme, drop_self
         _check_count("r", r)
         _check_count("block", block)
         _check_scheme(scheme, alpha)
-        N, L = self._host.shape
-        dt = self._host.dtype
+        N, L = self._shape
+        dt = self._hbuf.dtype
         d_new = self.ctx.buffer(max(N * L * dt.itemsize, 16))
         if N and L:
             kk = min(int(r), N - 1) + 1
