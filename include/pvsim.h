@@ -568,6 +568,72 @@ int pvs_ivf_remove_dev(pvs_ctx* ctx, int m, int nlist, int64_t n, const uint8_t*
 /* bytes from d_src to d_dst on the context's stream (growing a buffer); overlapping ranges are PVS_ERR_INVALID. */
 int pvs_copy_dev(pvs_ctx* ctx, void* d_dst, const void* d_src, size_t bytes);
 
+/* ---------------------------------------------------------------- diffusion re-ranking on the kNN graph
+ * Zhou et al. (NIPS 2003), Iscen et al. (CVPR 2017): the query's first results are spread over the neighbour graph of the whole
+ * database by solving (I - alpha S) f = y, and the database is ranked by f.  ALL arithmetic below is float64; every multiply, add,
+ * subtract and divide is rounded on its own (never an fma), in the stated order, so that a restatement with element operations gives
+ * the same bits.  A float32 similarity is upcast exactly.  N < 2^31 everywhere.
+ *
+ * GRAPH, from the rankings of every row against the index to depth kg + 1, 1 <= kg <= N - 1, integer 0 <= gamma <= 8:
+ *   drop self  from the list of row i the first slot that holds i leaves, or the last slot where there is none: nbr int32 [N][kg]
+ *              (an index outside [0, N) is stored as -1 and never counts) and sim [N][kg].
+ *   affinity   a[i][t] = max(sim[i][t], 0) multiplied by itself gamma - 1 times, left to right (gamma = 0: 1; a NaN counts as 0).
+ *   mutual     w[i][t] = min(a[i][t], a[j][u]) with j = nbr[i][t] and u the FIRST slot of row j that holds i; +0 without such a
+ *              slot.  The min is taken at both ends, so W is symmetric to the bit.
+ *   degrees    deg[i] = +0, then + w[i][t] for t ascending.  r[i] = 1 / sqrt(deg[i]), correctly rounded both, and 0 where deg[i] = 0.
+ *   entries    s[i][t] = w[i][t] * (r[i] * r[j]): the product of the two r first, so S is symmetric to the bit.
+ * The graph is nbr plus s in fixed-width rows; there is no CSR and no transpose.
+ *
+ * RIGHT-HAND SIDE, from the rankings idx / val [C][kq] of C queries, 1 <= kq <= N: Y float64 [N][C] (columns innermost) is zero
+ * except Y[idx[c][j]][c] = the affinity of val[c][j] (the same product); slots outside [0, N) are skipped.
+ *
+ * SOLVE (I - alpha S) x = y per column by conjugate gradients, 0 < alpha < 1:
+ *   x = 0; r = y; p = y; rr = dot(r, r); yy = rr; thr = (tol * tol) * yy
+ *   up to maxiter times:
+ *     column c takes the step iff rr[c] > thr[c] (false for a NaN) and it has not been retired
+ *     Ap[i] = p[i] - alpha * (sum_t s[i][t] * p[nbr[i][t]])    the sum from +0, t ascending; a slot with nbr outside [0, N) reads +0
+ *     pAp = dot(p, Ap); pAp <= 0 (or a NaN) retires the column for good, before anything of it is written
+ *     a = rr / pAp; x = x + a * p; r = r - a * Ap; rn = dot(r, r); b = rn / rr; p = r + b * p; rr = rn
+ *   a column that does not step is not written at all.
+ *   dot(u, v) of a column: the N products u[i] * v[i], padded with +0 to a multiple of PVS_DIFFUSE_DOT_BLOCK rows; inside each block
+ *   of that many consecutive rows the fixed tree  v[0:h] += v[h:2h]  for h = 128, 64, .., 1; the block results added from +0 in
+ *   ascending block order.
+ * So a column's result depends on that column alone: neither the number of columns of a call, nor the kernel's column width, nor how
+ * often the host looks at the flags changes a bit.
+ *
+ * Every entry point checks its arguments on the host before anything is launched (PVS_ERR_INVALID: sizes out of the ranges above,
+ * a missing pointer, arrays that overlap, a work buffer that is too small), enqueues on the context's stream, and is timed on slot 6. */
+#define PVS_DIFFUSE_DOT_BLOCK 256
+#define PVS_DIFFUSE_MAX_COLUMNS 65536  /* columns of one pvs_diffuse_cg_dev call */
+/* Lists of rows row0 .. row0 + b - 1: d_idx int64 [b][kg + 1], d_val float32 or float64 [b][kg + 1] (val_f64) -> rows row0 .. of
+ * d_nbr int32 [N][kg] and d_a float64 [N][kg] (drop self + affinity). */
+int pvs_graph_affinity_dev(pvs_ctx* ctx, const int64_t* d_idx, const void* d_val, int val_f64, int64_t b, int kg, int64_t row0,
+                           int64_t N, int gamma, int32_t* d_nbr, double* d_a);
+/* d_w float64 [N][kg] (the mutual pass: one lane per entry scans the partner's kg slots) */
+int pvs_graph_mutual_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_a, int64_t N, int kg, double* d_w);
+/* d_deg, d_r float64 [N] */
+int pvs_graph_degrees_dev(pvs_ctx* ctx, const double* d_w, int64_t N, int kg, double* d_deg, double* d_r);
+/* d_s float64 [N][kg] */
+int pvs_graph_normalise_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_w, const double* d_r, int64_t N, int kg, double* d_s);
+/* d_idx int64 [C][kq], d_val float32 or float64 [C][kq] -> d_Y float64 [N][C], zeroed here first.  C == 0 is a no-op. */
+int pvs_diffuse_rhs_dev(pvs_ctx* ctx, const int64_t* d_idx, const void* d_val, int val_f64, int64_t C, int kq, int64_t N, int gamma,
+                        double* d_Y);
+/* Host arithmetic: bytes of the work buffer of one pvs_diffuse_cg_dev call over C columns (three vectors of N C, the block partials,
+ * a few numbers per column). */
+int pvs_diffuse_workspace(int64_t N, int64_t C, size_t* bytes);
+/* d_Y, d_X float64 [N][C]; d_steps int32 [C], d_rr, d_yy float64 [C]: steps taken, the last rr and yy of every column.  d_work: at
+ * least pvs_diffuse_workspace(N, C) bytes, 256-byte aligned, the caller's; no workspace slot of the context is used.  width: the
+ * kernel's column width, 0 (chosen from C), 1, 4, 16 or 64 -- every width gives the same bits.  The host reads one int (columns that
+ * still step) before the first step and then every check_every >= 1 steps, and stops launching when it is 0; it waits for the
+ * stream only there.  maxiter == 0 gives x = 0 and rr = yy. */
+int pvs_diffuse_cg_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_s, int64_t N, int kg, const double* d_Y, int64_t C,
+                       double alpha, double tol, int maxiter, int check_every, int width, void* d_work, size_t work_bytes,
+                       double* d_X, int32_t* d_steps, double* d_rr, double* d_yy);
+/* The float64 ranking kernels behind every float64 top-k: d_scores [nq][ld], the first ncols columns of a row ranked by (score
+ * descending, column ascending, NaN last; -0 ranks and returns as +0) to depth 1 <= k <= ncols -> d_idx int64 [nq][k], d_val
+ * float64 [nq][k].  Timed on slot 3. */
+int pvs_rank_f64_dev(pvs_ctx* ctx, const double* d_scores, int64_t nq, int64_t ncols, int64_t ld, int k, int64_t* d_idx, double* d_val);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

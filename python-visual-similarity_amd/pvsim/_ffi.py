@@ -29,6 +29,7 @@ DSIFT_U8, DSIFT_F32, DSIFT_F32_RAW, DSIFT_F32_QUANT = 0, 1, 2, 3                
 OPT_UPDATE_WINDOW_ROWS = 6        # 0: windows of the in-place row compaction from the staging byte budget; 1..2^20: at most that many rows
 SCAN_TILE = 2048                  # PVS_SCAN_TILE of include/pvsim.h
 COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
+DIFFUSE_DOT_BLOCK, DIFFUSE_MAX_COLUMNS = 256, 65536   # PVS_DIFFUSE_DOT_BLOCK, PVS_DIFFUSE_MAX_COLUMNS of include/pvsim.h
 VLAD_PATH_AUTO, VLAD_PATH_GATHER, VLAD_PATH_STREAM, VLAD_PATH_FUSED = 0, 1, 2, 3
 TIMER_NAMES = ("assign", "aggregate", "cosine_gemm", "topk", "fisher_posterior", "fisher_moments", "misc", "rescore")
 
@@ -137,6 +138,14 @@ SIGNATURES = {
     "pvs_ivf_insert_dev": [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pvs_ivf_remove_dev": [_vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pvs_copy_dev": [_vp, _vp, _vp, _sz],
+    "pvs_graph_affinity_dev": [_vp, _vp, _vp, _int, _i64, _int, _i64, _i64, _int, _vp, _vp],
+    "pvs_graph_mutual_dev": [_vp, _vp, _vp, _i64, _int, _vp],
+    "pvs_graph_degrees_dev": [_vp, _vp, _i64, _int, _vp, _vp],
+    "pvs_graph_normalise_dev": [_vp, _vp, _vp, _vp, _i64, _int, _vp],
+    "pvs_diffuse_rhs_dev": [_vp, _vp, _vp, _int, _i64, _int, _i64, _int, _vp],
+    "pvs_diffuse_workspace": [_i64, _i64, C.POINTER(_sz)],
+    "pvs_diffuse_cg_dev": [_vp, _vp, _vp, _i64, _int, _vp, _i64, C.c_double, C.c_double, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp],
+    "pvs_rank_f64_dev": [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

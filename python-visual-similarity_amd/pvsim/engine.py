@@ -12,7 +12,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT, check, norm_params, ptr
 
-__all__ = ["Context", "default_context", "pack_descriptors", "dsift_count", "dsift_frames", "sift_workspace", "DESC_F32", "DESC_F32_ROOTSIFT", "DESC_U8_ROOTSIFT"]
+__all__ = ["Context", "default_context", "pack_descriptors", "dsift_count", "dsift_frames", "sift_workspace", "diffuse_workspace", "DESC_F32", "DESC_F32_ROOTSIFT", "DESC_U8_ROOTSIFT"]
 
 
 def pack_descriptors(desc_list, dim: int, dtype=np.float32):
@@ -50,6 +50,13 @@ def sift_workspace(h: int, w: int, n_octave_layers: int = 3, upsample: bool = Tr
     nbytes, rows = C.c_size_t(), C.c_int64()
     check(_ffi.lib().pvs_sift_workspace(int(h), int(w), int(n_octave_layers), int(bool(upsample)), C.byref(nbytes), C.byref(rows)))
     return int(nbytes.value), int(rows.value)
+
+
+def diffuse_workspace(n: int, columns: int) -> int:
+    """pvs_diffuse_workspace: bytes of the work buffer of one pvs_diffuse_cg_dev call over `columns` columns; host arithmetic."""
+    nbytes = C.c_size_t()
+    check(_ffi.lib().pvs_diffuse_workspace(int(n), int(columns), C.byref(nbytes)))
+    return int(nbytes.value)
 
 
 class _Handle:
@@ -464,6 +471,40 @@ class Context:
         """pvs_combine_rows_dev: out[i] = w_self[i] self[i] + sum_j w[i][j] X[idx[i][j]] in list order, slots outside [0, N) skipped"""
         check(_ffi.lib().pvs_combine_rows_dev(self.handle, ptr(d_x), N, L, int(bool(is_f64)), ptr(d_self), ptr(d_w_self), ptr(d_idx),
                                               ptr(d_w), n, r, ptr(d_out)))
+
+    # diffusion re-ranking (DESIGN.md section 16)
+    def graph_affinity_dev(self, d_idx, d_val, val_f64, b, kg, row0, N, gamma, d_nbr, d_a):
+        """pvs_graph_affinity_dev: lists (b, kg + 1) of rows row0.. -> rows row0.. of nbr int32 (N, kg) and a float64 (N, kg)"""
+        check(_ffi.lib().pvs_graph_affinity_dev(self.handle, ptr(d_idx), ptr(d_val), int(bool(val_f64)), int(b), int(kg), int(row0), int(N),
+                                                int(gamma), ptr(d_nbr), ptr(d_a)))
+
+    def graph_mutual_dev(self, d_nbr, d_a, N, kg, d_w):
+        """pvs_graph_mutual_dev: w = min of the two affinities where both rows list each other, +0 elsewhere"""
+        check(_ffi.lib().pvs_graph_mutual_dev(self.handle, ptr(d_nbr), ptr(d_a), int(N), int(kg), ptr(d_w)))
+
+    def graph_degrees_dev(self, d_w, N, kg, d_deg, d_r):
+        """pvs_graph_degrees_dev: deg = sum of a row's w in slot order, r = 1 / sqrt(deg) (0 where deg = 0)"""
+        check(_ffi.lib().pvs_graph_degrees_dev(self.handle, ptr(d_w), int(N), int(kg), ptr(d_deg), ptr(d_r)))
+
+    def graph_normalise_dev(self, d_nbr, d_w, d_r, N, kg, d_s):
+        """pvs_graph_normalise_dev: s[i][t] = w[i][t] * (r[i] * r[nbr[i][t]])"""
+        check(_ffi.lib().pvs_graph_normalise_dev(self.handle, ptr(d_nbr), ptr(d_w), ptr(d_r), int(N), int(kg), ptr(d_s)))
+
+    def diffuse_rhs_dev(self, d_idx, d_val, val_f64, C_, kq, N, gamma, d_y):
+        """pvs_diffuse_rhs_dev: query lists (C, kq) -> Y float64 (N, C), zero except the affinities of the list entries"""
+        check(_ffi.lib().pvs_diffuse_rhs_dev(self.handle, ptr(d_idx), ptr(d_val), int(bool(val_f64)), int(C_), int(kq), int(N), int(gamma),
+                                             ptr(d_y)))
+
+    def diffuse_cg_dev(self, d_nbr, d_s, N, kg, d_y, C_, alpha, tol, maxiter, check_every, width, d_work, work_bytes, d_x, d_steps, d_rr,
+                       d_yy):
+        """pvs_diffuse_cg_dev: conjugate gradients on (I - alpha S) x = y for C columns (N, C); steps int32, rr, yy per column"""
+        check(_ffi.lib().pvs_diffuse_cg_dev(self.handle, ptr(d_nbr), ptr(d_s), int(N), int(kg), ptr(d_y), int(C_), float(alpha), float(tol),
+                                            int(maxiter), int(check_every), int(width), ptr(d_work), int(work_bytes), ptr(d_x), ptr(d_steps),
+                                            ptr(d_rr), ptr(d_yy)))
+
+    def rank_f64_dev(self, d_scores, nq, ncols, ld, k, d_idx, d_val):
+        """pvs_rank_f64_dev: rows of float64 scores -> the k best columns by (score descending, column ascending, NaN last)"""
+        check(_ffi.lib().pvs_rank_f64_dev(self.handle, ptr(d_scores), int(nq), int(ncols), int(ld), int(k), ptr(d_idx), ptr(d_val)))
 
     # index maintenance (DESIGN.md section 15)
     SCAN_TILE = _ffi.SCAN_TILE

@@ -85,6 +85,25 @@ def _no_compact_expansion(all_vectors, expand):
         raise ValueError("query expansion needs the full-precision rows: use a dict or a DeviceIndex, not a CompactIndex")
 
 
+def _rank_diffused(query_vecs: np.ndarray, index, k: int | None, diffuse, expand=None, rerank: int = 0, nprobe=None):
+    """_rank through a pvsim.Diffusion graph: the graph's own index only, and none of the other re-ranking options"""
+    from .diffusion import Diffusion
+    from .index import DeviceIndex
+    if not isinstance(diffuse, Diffusion):
+        raise TypeError("diffuse must be a pvsim.Diffusion")
+    if not isinstance(index, DeviceIndex):
+        raise TypeError("diffuse= needs the pvsim.index.DeviceIndex the graph was built on, not a dict or a compact index")
+    if diffuse.index is not index:
+        raise ValueError("diffuse= needs the DeviceIndex the graph was built on: this graph belongs to another index")
+    if expand is not None or rerank or nprobe is not None:
+        raise ValueError("diffuse= excludes expand=, rerank= and nprobe=")
+    n = len(index)
+    kk = n if k is None else max(0, min(int(k), n))
+    if query_vecs.shape[0] == 0 or kk == 0:
+        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float64)
+    return diffuse.rank(query_vecs, kk)
+
+
 def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None, resident=None, rerank: int = 0, nprobe=None):
     """-> (indices (nq, k') int64, scores (nq, k')) with k' = min(k, N) (k=None: all N)."""
     if all_vectors is None:                                     # a CompactIndex: no host matrix
@@ -128,17 +147,23 @@ def _rank_maybe_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths,
 
 
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
-                           k: int = 5, rerank: int = 0, expand=None, nprobe=None) -> list[tuple[str, float]]:
+                           k: int = 5, rerank: int = 0, expand=None, nprobe=None, diffuse=None) -> list[tuple[str, float]]:
     """[(image_path, similarity)] of the k most similar database entries, best first.  `rerank=R` (CompactIndex only): the
     ADC top-R re-ranked by the exact cosine of the kept projected rows.  `expand`: a pvsim.expand.QueryExpansion; the list is
     then the ranking of the expanded query (dict or DeviceIndex; a dict is uploaded for the call).  `nprobe` (IVFCompactIndex
-    only, and required there): the inverted lists scanned; the list is shorter than k when they hold fewer rows."""
+    only, and required there): the inverted lists scanned; the list is shorter than k when they hold fewer rows.  `diffuse`: a
+    pvsim.Diffusion graph built on `dataset` (a DeviceIndex); the list is then the diffusion ranking and its float64 scores, and
+    `rerank`, `expand` and `nprobe` are excluded."""
+    if diffuse is not None:
+        _rank_diffused(np.zeros((0, 0)), dataset, 0, diffuse, expand, rerank, nprobe)          # refuse before anything is encoded
     all_vectors, all_paths, resident = _vectors_and_paths(dataset)
     _no_compact_expansion(all_vectors, expand)
     query_vector = encoder.encode(uploaded_image)
     if query_vector.ndim == 1:
         query_vector = query_vector.reshape(1, -1)
-    if all_vectors is None:                                     # a CompactIndex: the only index that can re-rank
+    if diffuse is not None:
+        idx, val = _rank_diffused(query_vector[:1], dataset, k, diffuse)
+    elif all_vectors is None:                                     # a CompactIndex: the only index that can re-rank
         idx, val = _rank_compact(query_vector[:1], resident, k, rerank, nprobe)
     else:
         if rerank:
@@ -202,15 +227,20 @@ def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: i
 
 
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None) -> float:
+              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None, diffuse=None) -> float:
     """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
-    there) as in retrieve_top_k_similar."""
+    there) and `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) as in retrieve_top_k_similar."""
+    if diffuse is not None:
+        _rank_diffused(np.zeros((0, 0)), encoding_map, 0, diffuse, expand, rerank, nprobe)     # refuse before anything is encoded
     all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
     _no_compact_expansion(all_vectors, expand)
     labels = list(image_labels)
     q = _first_rows(encoder, images)
-    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
+    if diffuse is not None:
+        idx, _ = _rank_diffused(q, encoding_map, k, diffuse)
+    else:
+        idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
     db_labels = [path_labels_dict[p] for p in all_paths]
     aps = []
     for row, true_label in zip(idx, labels):
@@ -224,16 +254,21 @@ def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encodin
 
 
 def top_k_accuracy(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-                   path_labels_dict: dict[str, int], encoder, k: int, expand=None, rerank: int = 0, nprobe=None) -> float:
+                   path_labels_dict: dict[str, int], encoder, k: int, expand=None, rerank: int = 0, nprobe=None, diffuse=None) -> float:
     """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
-    there) as in retrieve_top_k_similar."""
+    there) and `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) as in retrieve_top_k_similar."""
+    if diffuse is not None:
+        _rank_diffused(np.zeros((0, 0)), encoding_map, 0, diffuse, expand, rerank, nprobe)     # refuse before anything is encoded
     all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
     _no_compact_expansion(all_vectors, expand)
     images = list(images)
     labels = list(image_labels)
     q = _first_rows(encoder, images)
-    idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
+    if diffuse is not None:
+        idx, _ = _rank_diffused(q, encoding_map, k, diffuse)
+    else:
+        idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
     db_labels = [path_labels_dict[p] for p in all_paths]
     correct = sum(1 for row, true_label in zip(idx, labels) if any(i >= 0 and db_labels[i] == true_label for i in row))
     return float(correct / len(images))

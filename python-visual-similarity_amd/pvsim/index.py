@@ -108,7 +108,8 @@ class DeviceIndex(Mapping):
     neighbours folded in (pvsim/expand.py); both sum whole rows on the device.
     `add`, `remove` / `del index[path]` and `reserve` change the resident index without a rebuild: rows move
     on the device, and after any sequence of them every array and every ranking equals those of DeviceIndex(dict of the surviving
-    rows in surviving order), bit for bit."""
+    rows in surviving order), bit for bit.  `modifications` counts them: a pvsim.Diffusion graph is a snapshot of the rows it was built
+    from and refuses to rank once the count has moved."""
 
     def __init__(self, encoding_map, ctx=None):
         from .engine import default_context
@@ -167,6 +168,7 @@ class DeviceIndex(Mapping):
         n, L = self._shape
         self._pending, self._mirror_rows, self._cap = [], n, n      # host-mirror notes, rows the mirror holds, rows the device buffers hold
         self._pos = {p: i for i, p in enumerate(self._paths)}
+        self.modifications = 0                                      # adds and removes since construction
         self._inv = self.ctx.buffer(max(n, 1) * self._hbuf.itemsize)
         self._inv_host = None
         if n and L:
@@ -258,6 +260,7 @@ class DeviceIndex(Mapping):
             self._pos[p] = n + i
         self._paths.extend(paths)
         self._inv_host = None
+        self.modifications += 1
 
     def remove(self, paths) -> None:
         """The named entries leave; the others keep their order, as `del d[k]` on the dict does.  An unknown path is a KeyError, a
@@ -278,12 +281,14 @@ class DeviceIndex(Mapping):
         self._paths = _compact_list(self._paths, idx)
         self._pos = {p: i for i, p in enumerate(self._paths)}
         self._inv_host = None
+        self.modifications += 1
 
     def __delitem__(self, path) -> None:
         self.remove([path])
 
-    def _rank_dev(self, d_q: int, nq: int, k: int, want_inv: bool = False):
-        """`rank` of nq rows of the index's dtype that are on the device (raw pointer) -> (idx, val[, 1 / ||q|| (nq,)])."""
+    def _rank_dev_buffers(self, d_q: int, nq: int, k: int):
+        """the ranking behind `_rank_dev` with the lists left on the device -> (1 / ||q|| (nq,), idx int64 (nq, k), val (nq, k)), three
+        DeviceBuffers the caller frees"""
         n, L = self._shape
         dt = self._hbuf.dtype
         isz = dt.itemsize
@@ -300,6 +305,17 @@ class DeviceIndex(Mapping):
             else:
                 self.ctx.row_inv_norms_f64_dev(d_q, nq, L, d_invq.ptr)
                 self.ctx.cosine_topk_f64_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
+        except BaseException:
+            for b in (d_invq, d_idx, d_val):
+                b.free()
+            raise
+        return d_invq, d_idx, d_val
+
+    def _rank_dev(self, d_q: int, nq: int, k: int, want_inv: bool = False):
+        """`rank` of nq rows of the index's dtype that are on the device (raw pointer) -> (idx, val[, 1 / ||q|| (nq,)])."""
+        dt = self._hbuf.dtype
+        d_invq, d_idx, d_val = self._rank_dev_buffers(d_q, nq, k)
+        try:
             out = d_idx.download((nq, k), np.int64), d_val.download((nq, k), dt)
             return out + (d_invq.download((nq,), dt),) if want_inv else out
         finally:
