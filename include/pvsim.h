@@ -634,6 +634,61 @@ int pvs_diffuse_cg_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_s, in
  * float64 [nq][k].  Timed on slot 3. */
 int pvs_rank_f64_dev(pvs_ctx* ctx, const double* d_scores, int64_t nq, int64_t ncols, int64_t ld, int k, int64_t* d_idx, double* d_val);
 
+/* ---------------------------------------------------------------- local-descriptor retrieval: ASMK* 
+ * The aggregated selective match kernel with binary signatures (Tolias, Avrithis, Jegou, ICCV 2013; Hamming embedding: Jegou,
+ * Douze, Schmid, ECCV 2008): a large vocabulary, per image and visual word ONE B-bit signature of the summed residual, an inverted
+ * file over words, and a score that sums a selectivity function of the Hamming distance over the words two images share.
+ *
+ * ENTRIES of an image with descriptor rows x_j (j in CSR order, any pvs_desc_kind; x_j[t] is the value the encoders use: the
+ * RootSIFT kinds give what pvs_materialise_dev gives) and labels l_j (pvs_kmeans_predict_dev) against centroids c [K][D]:
+ *   the entries are the image's distinct labels in ascending order.  For the entry of word w:
+ *   V[t]   starts at +0 and adds (x_j[t] - c_w[t]) for j ascending over the rows with l_j = w: one float32 subtraction and one
+ *          float32 addition, each rounded on its own.
+ *   z[t]   with a projection P float32 [B][D]: starts at +0 and adds P[t][u] * V[u] for u ascending, a multiply then an add, never
+ *          an fma.  Without one (P NULL, which needs B == D): z = V.
+ *   bits   bit t of the signature is 1 iff z[t] >= 0 (a NaN gives 0).  A sum that starts at +0 never ends at -0, so a row that sits
+ *          on its centroid gives all ones.  Bit t lies in uint32 word t / 32 at position t % 32.
+ *   limits B in {32, 64, 96, 128}, 1 <= D <= 128, 1 <= K <= 65536.  An image of more than 8192 rows is PVS_ERR_UNSUPPORTED; an
+ *          image of 0 rows has 0 entries.
+ *
+ * INTEGER WEIGHTS, computed by the caller in float64:
+ *   sel    int32 [B + 1]: with u = 1 - 2 h / B, sel[h] = rint(1023 u^alpha) where u > tau, 0 otherwise (alpha > 0, 0 <= tau < 1).
+ *   wt     int32 [K]: 0 for a word no database image holds, otherwise clip(rint(64 ln(N / df_w)), 1, 1023) with df_w the number of
+ *          database images that hold w; 64 for every held word when idf is off.
+ *   gamma  gamma(X) = float32(1 / sqrt(float64(sum over the entries of X of 1023 wt[w]))), 0 for an image without entries (or
+ *          whose sum is 0).  With it an image scores 1 against itself.
+ *
+ * SCORE of query Q against image X:
+ *   acc    = sum over the words w that Q and X share of wt[w] * sel[popcount(sig_Q(w) xor sig_X(w))], in uint32, exact: the caller
+ *            refuses a query whose sum of 1023 wt[w] reaches 2^32 (4104 entries are always safe).  Integer sums do not depend on
+ *            the order, so the scan may be cut anywhere and every cut gives the same bits.
+ *   score  = (float32(acc) * gamma(Q)) * gamma(X): the conversion rounds to nearest even, the two multiplies are rounded separately.
+ *
+ * STORAGE: entries sorted by (word, image): word_off int64 [K + 1], ent_img int32 [E] (ascending inside a word, each image at most
+ * once per word), ent_sig uint32 [E][B / 32], gamma_db float32 [N].
+ * The entry points enqueue on the context's stream and do not wait for it. */
+/* cb gives c, K and D.  d_offsets int64 [n_images + 1] are the CSR offsets of the rows (offsets[0] = 0) and h_offsets their HOST
+ * copy: all checks and sizing come from it; the two must agree.  d_labels int32 [total_desc], every label in [0, K) (a
+ * precondition).  d_proj float32 [bits][D] or NULL.  Image i writes its entries to the slots offsets[i] .. offsets[i] + count[i] - 1
+ * of d_ent_word int32 [total_desc] and d_ent_sig uint32 [total_desc][bits / 32], and count[i] to d_ent_count int32 [n_images]: an
+ * image cannot have more entries than rows, so there is no capacity protocol.  Slots beyond count[i] are left unwritten.  Timed on
+ * slot 1. */
+int pvs_asmk_aggregate_dev(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, int desc_kind, const int64_t* d_offsets,
+                           const int64_t* h_offsets, int64_t n_images, int64_t total_desc, const int32_t* d_labels,
+                           const float* d_proj, int bits, int32_t* d_ent_word, uint32_t* d_ent_sig, int32_t* d_ent_count);
+/* Query q holds the entries h_q_off[q] .. h_q_off[q + 1] - 1 of d_q_word int32 / d_q_sig uint32 [.][bits / 32] (h_q_off: HOST int64
+ * [nq + 1], non-decreasing); a query word outside [0, K) is skipped.  d_word_off, d_ent_img, d_ent_sig, d_gamma_db: the storage
+ * above for N < 2^31 images; d_wt int32 [K], d_sel int32 [bits + 1], d_gamma_q float32 [nq].  Signature arrays are 16-byte aligned
+ * at bits = 128, 8-byte at 64, 4-byte otherwise.  d_scores float32 [nq][ld], ld >= N: every column < N of every row is written
+ * exactly once, with +0 where nothing is shared; columns >= N are untouched.  A workgroup serves one query and a slice of
+ * consecutive images: slice_images = 0 leaves the slice to the host (about two workgroups per compute unit, no slice below 1024
+ * images), otherwise it is a multiple of 64 in 64..32768 -- every value gives the same bits.  No global atomics, no float atomics.
+ * The ranking is pvs_topk_dev on the panel.  Timed on slot 2. */
+int pvs_asmk_score_dev(pvs_ctx* ctx, int64_t nq, const int64_t* h_q_off, const int32_t* d_q_word, const uint32_t* d_q_sig, int bits,
+                       int K, const int64_t* d_word_off, const int32_t* d_ent_img, const uint32_t* d_ent_sig, int64_t N,
+                       const int32_t* d_wt, const int32_t* d_sel, const float* d_gamma_q, const float* d_gamma_db, int slice_images,
+                       float* d_scores, int64_t ld);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

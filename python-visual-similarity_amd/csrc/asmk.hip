@@ -1,0 +1,395 @@
+// Local-descriptor retrieval: the aggregated selective match kernel with binary signatures, ASMK* of Tolias,
+// Avrithis and Jegou (ICCV 2013), on top of Jegou's Hamming embedding.
+//   pvs_asmk_aggregate_dev   rows + labels of a batch of images -> per image its entries (visual word, B-bit signature of the summed
+//                            residual), words ascending
+//   pvs_asmk_score_dev       the entries of nq queries x an inverted file over words -> the score panel [nq][N]; the ranking is
+//                            pvs_topk_dev on that panel
+// Every value is DEFINED in include/pvsim.h: the residual sum is float32 in row order with separate roundings (this unit is compiled
+// with -ffp-contract=off), the score is a sum of integers, exact in uint32, so the scan may be cut anywhere and may use atomics.
+// tests/asmk_numpy.py restates both.
+#include <algorithm>
+
+#include "common.hpp"
+#include "desc_load.hpp"
+
+namespace pvs {
+
+constexpr int ASMK_THREADS = 512;
+constexpr int ASMK_WAVES = ASMK_THREADS / WAVE;
+constexpr int ASMK_MAX_ROWS = 8192;            // rows of one image: 8192 keys of 8 bytes are 64 KiB of LDS
+constexpr int ASMK_MAX_D = 128;
+constexpr int ASMK_MAX_SLICE = 32768;          // uint32 accumulators of one workgroup: 128 KiB
+constexpr int64_t ASMK_MIN_SLICE = 1024;       // images a workgroup serves at least when the host chooses (the rule of section 14)
+constexpr int ASMK_QUERY_BLOCK = 128;          // queries of one launch: their entry offsets travel as kernel arguments
+
+// ------------------------------------------------------------------------------------------------- aggregate
+// One workgroup per image.  LDS: keys uint64 [npad] (label << 32 | row), heads uint16 [npad] (first position of every run of equal
+// labels), then P transposed float [D][B] when there is a projection.  The keys are sorted by a bitonic network; the padding keys
+// (all ones) sort last.  Wave v takes the runs v, v + 8, ...: lanes over t, rows in ascending j (the low half of the key).
+template <int KIND>
+__global__ __launch_bounds__(ASMK_THREADS) void asmk_aggregate_kernel(const void* __restrict__ X, int D,
+                                                                       const int64_t* __restrict__ offsets,
+                                                                       const int32_t* __restrict__ labels,
+                                                                       const float* __restrict__ cent, int K,
+                                                                       const float* __restrict__ P, int B, int npad,
+                                                                       int32_t* __restrict__ ent_word, uint32_t* __restrict__ ent_sig,
+                                                                       int32_t* __restrict__ ent_count) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char asmk_lds[];
+  __shared__ int stmp[ASMK_WAVES];
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(asmk_lds);
+  unsigned short* heads = reinterpret_cast<unsigned short*>(asmk_lds + (size_t)npad * 8);
+  float* Pt = reinterpret_cast<float*>(asmk_lds + (size_t)npad * 10);   // npad is a multiple of 64: 4-byte aligned
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t img = blockIdx.x;
+  const int64_t r0 = offsets[img];
+  const int n = (int)min((int64_t)npad, offsets[img + 1] - r0);   // the host has checked n <= npad
+  if (n <= 0) {
+    if (tid == 0) ent_count[img] = 0;
+    return;
+  }
+  if (P != nullptr)
+    for (int i = tid; i < B * D; i += ASMK_THREADS) {
+      const int t = i / D, u = i - t * D;
+      Pt[u * B + t] = P[i];
+    }
+  for (int i = tid; i < npad; i += ASMK_THREADS)
+    keys[i] = i < n ? ((unsigned long long)(unsigned)labels[r0 + i] << 32) | (unsigned)i : ~0ull;
+  __syncthreads();
+  for (int k = 2; k <= npad; k <<= 1)
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < npad; i += ASMK_THREADS) {
+        const int o = i ^ j;
+        if (o > i) {
+          const unsigned long long a = keys[i], b = keys[o];
+          if ((a > b) == ((i & k) == 0)) {
+            keys[i] = b;
+            keys[o] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+
+  // ---- run heads: thread `tid` owns the positions [tid per, (tid + 1) per)
+  const int per = npad / ASMK_THREADS > 0 ? npad / ASMK_THREADS : 1;
+  const int p_lo = tid * per, p_hi = min(p_lo + per, n);
+  int mine = 0;
+  for (int p = p_lo; p < p_hi; ++p) mine += (p == 0 || (keys[p] >> 32) != (keys[p - 1] >> 32)) ? 1 : 0;
+  int incl = mine;
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const int o = __shfl_up(incl, s, 64);
+    if (lane >= s) incl += o;
+  }
+  if (lane == 63) stmp[wave] = incl;
+  __syncthreads();
+  int before = incl - mine, E = 0;
+  for (int w = 0; w < ASMK_WAVES; ++w) {
+    if (w < wave) before += stmp[w];
+    E += stmp[w];
+  }
+  for (int p = p_lo; p < p_hi; ++p)
+    if (p == 0 || (keys[p] >> 32) != (keys[p - 1] >> 32)) heads[before++] = (unsigned short)p;
+  __syncthreads();
+  if (tid == 0) ent_count[img] = E;
+
+  const int W = B >> 5;
+  const bool two = D > 64;
+  for (int e = wave; e < E; e += ASMK_WAVES) {
+    const int p0 = heads[e], p1 = e + 1 < E ? (int)heads[e + 1] : n;
+    const int w = (int)(keys[p0] >> 32);
+    const float* c = cent + (size_t)min(max(w, 0), K - 1) * D;
+    const float c0 = lane < D ? c[lane] : 0.f, c1 = two && lane + 64 < D ? c[lane + 64] : 0.f;
+    float v0 = 0.f, v1 = 0.f;
+    for (int p = p0; p < p1; ++p) {
+      const int64_t row = r0 + (int64_t)(unsigned)(keys[p] & 0xffffffffull);
+      float x0 = lane < D ? load1<KIND>(X, row, D, lane) : 0.f;
+      float x1 = two && lane + 64 < D ? load1<KIND>(X, row, D, lane + 64) : 0.f;
+      if (DescTraits<KIND>::rootsift) {
+        const RootsiftRow<KIND> rr(wave_sum_xor(x0 + x1, 64));   // the row sum of materialise_kernel: lane-strided, then the butterfly
+        x0 = rr(x0);
+        x1 = rr(x1);
+      }
+      v0 = v0 + (x0 - c0);
+      v1 = v1 + (x1 - c1);
+    }
+    float z0 = v0, z1 = v1;
+    if (P != nullptr) {
+      z0 = 0.f;
+      z1 = 0.f;
+      const int t0 = min(lane, B - 1), t1 = min(lane + 64, B - 1);   // lanes beyond B compute a value nobody reads
+      const int d0 = min(D, 64);
+      for (int u = 0; u < d0; ++u) {
+        const float vu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v0), u));
+        z0 = z0 + Pt[u * B + t0] * vu;
+        z1 = z1 + Pt[u * B + t1] * vu;
+      }
+      for (int u = 64; u < D; ++u) {
+        const float vu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v1), u - 64));
+        z0 = z0 + Pt[u * B + t0] * vu;
+        z1 = z1 + Pt[u * B + t1] * vu;
+      }
+    }
+    const unsigned long long m0 = __ballot(z0 >= 0.f), m1 = __ballot(z1 >= 0.f);
+    const int64_t slot = r0 + e;
+    if (lane == 0) ent_word[slot] = w;
+    if (lane < W) {
+      const unsigned long long m = lane < 2 ? m0 : m1;
+      ent_sig[slot * W + lane] = (unsigned)(lane & 1 ? m >> 32 : m);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------- score
+struct AsmkQueryOffsets {
+  int64_t o[ASMK_QUERY_BLOCK + 1];   // entry offsets of the launch's queries
+  int64_t first;                     // global index of its first query
+};
+
+// the first p in [a, b) with img[p] >= key, b without one; img ascending in [a, b).  One lane's own search: 64 entries of a query
+// are searched side by side, so the dependent loads of a search are paid once per 64 entries.
+__device__ __forceinline__ int64_t asmk_lower_bound(const int32_t* __restrict__ img, int64_t a, int64_t b, int key) {
+  while (a < b) {
+    const int64_t m = a + ((b - a) >> 1);
+    if (img[m] < key) a = m + 1;
+    else b = m;
+  }
+  return a;
+}
+
+__device__ __forceinline__ int64_t asmk_shfl64(int64_t v, int src) {
+  const int lo = __shfl((int)(v & 0xffffffff), src, 64), hi = __shfl((int)(v >> 32), src, 64);
+  return ((int64_t)hi << 32) | (unsigned)lo;
+}
+
+template <int W>
+__device__ __forceinline__ void asmk_load_sig(const uint32_t* __restrict__ p, uint32_t (&s)[W]) {
+  if constexpr (W == 4) {
+    const uint4 v = *reinterpret_cast<const uint4*>(p);
+    s[0] = v.x, s[1] = v.y, s[2] = v.z, s[3] = v.w;
+  } else if constexpr (W == 2) {
+    const uint2 v = *reinterpret_cast<const uint2*>(p);
+    s[0] = v.x, s[1] = v.y;
+  } else {
+#pragma unroll
+    for (int i = 0; i < W; ++i) s[i] = p[i];
+  }
+}
+
+// Workgroup (g, q) of a grid (G, queries of the launch) serves query q and the images [g S, min((g + 1) S, N)).  acc[S] in LDS.
+// A wave takes 64 of the query's entries at a time.  First every lane finds, by two searches of its own, the part of one entry's
+// list that falls into the slice (the lists are sorted by image).  Then the wave walks the 64 parts: GW lanes per part and 64 / GW
+// parts side by side, GW = 16, 32 or 64 by the longest part of the batch, with coalesced reads of id and signature, xor, popcount,
+// a sel look-up and one LDS atomic add per entry.  After one barrier the slice is converted, scaled and stored.
+template <int W>
+__global__ __launch_bounds__(ASMK_THREADS) void asmk_score_kernel(AsmkQueryOffsets qo, const int32_t* __restrict__ q_word,
+                                                                   const uint32_t* __restrict__ q_sig, int K,
+                                                                   const int64_t* __restrict__ word_off,
+                                                                   const int32_t* __restrict__ ent_img,
+                                                                   const uint32_t* __restrict__ ent_sig, int N,
+                                                                   const int32_t* __restrict__ wt, const int32_t* __restrict__ sel,
+                                                                   const float* __restrict__ gamma_q,
+                                                                   const float* __restrict__ gamma_db, int S,
+                                                                   float* __restrict__ scores, int64_t ld) {
+  extern __shared__ __attribute__((aligned(16))) unsigned int asmk_acc[];
+  __shared__ unsigned int sel_s[W * 32 + 1];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int q = blockIdx.y;
+  const int s0 = blockIdx.x * S;
+  const int sn = min(S, N - s0);
+  for (int i = tid; i < sn; i += ASMK_THREADS) asmk_acc[i] = 0u;
+  for (int i = tid; i <= W * 32; i += ASMK_THREADS) sel_s[i] = (unsigned)sel[i];
+  __syncthreads();
+
+  const int64_t e0 = qo.o[q], e1 = qo.o[q + 1];
+  for (int64_t eb = e0 + (int64_t)wave * 64; eb < e1; eb += (int64_t)ASMK_WAVES * 64) {
+    const int64_t e = eb + lane;
+    int64_t lo = 0;
+    int cnt = 0;
+    unsigned wgt = 0u;
+    if (e < e1) {
+      const int w = q_word[e];
+      if (w >= 0 && w < K) {
+        wgt = (unsigned)wt[w];
+        const int64_t a = word_off[w], b = word_off[w + 1];
+        if (wgt != 0u && b > a) {
+          lo = asmk_lower_bound(ent_img, a, b, s0);
+          // an image appears once per word: the slice holds at most sn entries of this list
+          cnt = (int)(asmk_lower_bound(ent_img, lo, min(b, lo + sn), s0 + sn) - lo);
+        }
+      }
+    }
+    int longest = cnt;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) longest = max(longest, __shfl_xor(longest, m, 64));
+    const int gshift = longest <= 16 ? 4 : (longest <= 32 ? 5 : 6);
+    const int GW = 1 << gshift, grp = lane >> gshift, gl = lane & (GW - 1), ngrp = 64 >> gshift;
+    unsigned long long live = __ballot(cnt > 0);
+    while (live) {
+      int mine = -1;
+      for (int g = 0; g < ngrp && live; ++g) {
+        const int l = __builtin_ctzll(live);
+        live &= live - 1;
+        if (g == grp) mine = l;
+      }
+      const int src = mine < 0 ? lane : mine;
+      const int64_t plo = asmk_shfl64(lo, src);
+      const int pn = __shfl(cnt, src, 64);
+      const unsigned pw = (unsigned)__shfl((int)wgt, src, 64);
+      const int n = mine < 0 ? 0 : pn;
+      if (n > 0) {
+        uint32_t qs[W];
+        asmk_load_sig<W>(q_sig + (eb + src) * W, qs);
+        for (int t = gl; t < n; t += GW) {
+          const int64_t p = plo + t;
+          const unsigned i = (unsigned)(ent_img[p] - s0);
+          uint32_t xs[W];
+          asmk_load_sig<W>(ent_sig + p * W, xs);
+          int h = 0;
+#pragma unroll
+          for (int u = 0; u < W; ++u) h += __popc(xs[u] ^ qs[u]);
+          if (i < (unsigned)sn) atomicAdd(&asmk_acc[i], pw * sel_s[h]);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const float gq = gamma_q[qo.first + q];
+  float* out = scores + (qo.first + q) * ld + s0;
+  for (int i = tid; i < sn; i += ASMK_THREADS) out[i] = __fmul_rn(__fmul_rn((float)asmk_acc[i], gq), gamma_db[s0 + i]);
+}
+
+}  // namespace pvs
+
+using namespace pvs;
+
+static int asmk_check_bits(const char* fn, int bits) {
+  if (bits != 32 && bits != 64 && bits != 96 && bits != 128) PVS_FAIL(PVS_ERR_INVALID, "%s: bits must be 32, 64, 96 or 128 (got %d)", fn, bits);
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_asmk_aggregate_dev(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, int desc_kind, const int64_t* d_offsets,
+                                      const int64_t* h_offsets, int64_t n_images, int64_t total_desc, const int32_t* d_labels,
+                                      const float* d_proj, int bits, int32_t* d_ent_word, uint32_t* d_ent_sig, int32_t* d_ent_count) {
+  PVS_NEED(ctx, "ctx");
+  PVS_NEED(cb, "codebook");
+  PVS_TRY(asmk_check_bits(__func__, bits));
+  if (desc_kind != PVS_DESC_F32 && desc_kind != PVS_DESC_F32_ROOTSIFT && desc_kind != PVS_DESC_U8_ROOTSIFT)
+    PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: unknown descriptor kind %d", desc_kind);
+  const int D = cb->D, K = cb->K;
+  if (D < 1 || D > ASMK_MAX_D) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: need 1 <= D <= %d (got %d)", ASMK_MAX_D, D);
+  if (K < 1 || K > 65536) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: need 1 <= K <= 65536 (got %d)", K);
+  if (!d_proj && bits != D) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: without a projection bits must equal D (bits=%d, D=%d)", bits, D);
+  if (n_images < 0 || total_desc < 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: negative sizes");
+  if (n_images >= ((int64_t)1 << 31)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: need n_images < 2^31");
+  if (n_images == 0) return PVS_OK;
+  PVS_NEED(d_offsets, "offsets");
+  PVS_NEED(h_offsets, "host offsets");
+  PVS_NEED(d_ent_count, "entry counts");
+  if (h_offsets[0] != 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: offsets[0] must be 0");
+  int64_t longest = 0;
+  for (int64_t i = 0; i < n_images; ++i) {
+    const int64_t n = h_offsets[i + 1] - h_offsets[i];
+    if (n < 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: offsets must not decrease (image %lld)", (long long)i);
+    longest = std::max(longest, n);
+  }
+  if (h_offsets[n_images] != total_desc)
+    PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_aggregate_dev: offsets end at %lld but total_desc is %lld", (long long)h_offsets[n_images],
+             (long long)total_desc);
+  if (longest > ASMK_MAX_ROWS)
+    PVS_FAIL(PVS_ERR_UNSUPPORTED, "pvs_asmk_aggregate_dev: an image of %lld rows exceeds %d", (long long)longest, ASMK_MAX_ROWS);
+  if (total_desc > 0) {
+    PVS_NEED(d_desc, "descriptors");
+    PVS_NEED(d_labels, "labels");
+    PVS_NEED(d_ent_word, "entry words");
+    PVS_NEED(d_ent_sig, "entry signatures");
+  }
+  PVS_ALIGNED(d_offsets, 8, "offsets");
+  PVS_ALIGNED(d_labels, 4, "labels");
+  PVS_ALIGNED(d_ent_word, 4, "entry words");
+  PVS_ALIGNED(d_ent_sig, 4, "entry signatures");
+  PVS_ALIGNED(d_ent_count, 4, "entry counts");
+  if (desc_kind != PVS_DESC_U8_ROOTSIFT) PVS_ALIGNED(d_desc, 4, "descriptors");
+  if (d_proj) PVS_ALIGNED(d_proj, 4, "projection");
+  PVS_HIP(hipSetDevice(ctx->device));
+  int npad = 64;
+  while (npad < longest) npad <<= 1;
+  const size_t lds = (size_t)npad * 10 + (d_proj ? (size_t)bits * D * sizeof(float) : 0);
+  ScopedTimer t(ctx, T_AGGREGATE);
+  return dispatch_desc_kind(desc_kind, [&](auto k) -> int {
+    return launch_lds(ctx, asmk_aggregate_kernel<decltype(k)::value>, dim3((unsigned)n_images), dim3(ASMK_THREADS), lds, d_desc, D,
+                      d_offsets, d_labels, (const float*)cb->d_cent, K, d_proj, bits, npad, d_ent_word, d_ent_sig, d_ent_count);
+  });
+}
+
+PVS_EXPORT int pvs_asmk_score_dev(pvs_ctx* ctx, int64_t nq, const int64_t* h_q_off, const int32_t* d_q_word, const uint32_t* d_q_sig,
+                                  int bits, int K, const int64_t* d_word_off, const int32_t* d_ent_img, const uint32_t* d_ent_sig,
+                                  int64_t N, const int32_t* d_wt, const int32_t* d_sel, const float* d_gamma_q, const float* d_gamma_db,
+                                  int slice_images, float* d_scores, int64_t ld) {
+  PVS_NEED(ctx, "ctx");
+  PVS_TRY(asmk_check_bits(__func__, bits));
+  if (K < 1 || K > 65536) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: need 1 <= K <= 65536 (got %d)", K);
+  if (nq < 0 || N < 0 || N >= ((int64_t)1 << 31)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: need nq >= 0 and 0 <= N < 2^31");
+  if (ld < N) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: ld = %lld is below N = %lld", (long long)ld, (long long)N);
+  if (slice_images != 0 && (slice_images < 64 || slice_images > ASMK_MAX_SLICE || slice_images % 64))
+    PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: slice_images must be 0 or a multiple of 64 in 64..%d (got %d)", ASMK_MAX_SLICE, slice_images);
+  if (nq == 0 || N == 0) return PVS_OK;
+  PVS_NEED(h_q_off, "host query offsets");
+  for (int64_t q = 0; q < nq; ++q)
+    if (h_q_off[q] < 0 || h_q_off[q + 1] < h_q_off[q])
+      PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: query offsets must be non-negative and must not decrease (query %lld)", (long long)q);
+  if (h_q_off[nq] > h_q_off[0]) {
+    PVS_NEED(d_q_word, "query words");
+    PVS_NEED(d_q_sig, "query signatures");
+  }
+  PVS_NEED(d_word_off, "word offsets");
+  PVS_NEED(d_ent_img, "entry images");
+  PVS_NEED(d_ent_sig, "entry signatures");
+  PVS_NEED(d_wt, "word weights");
+  PVS_NEED(d_sel, "selectivity table");
+  PVS_NEED(d_gamma_q, "query normalisers");
+  PVS_NEED(d_gamma_db, "database normalisers");
+  PVS_NEED(d_scores, "scores");
+  const int W = bits / 32;
+  const int sig_align = W == 4 ? 16 : (W == 2 ? 8 : 4);
+  PVS_ALIGNED(d_q_word, 4, "query words");
+  PVS_ALIGNED(d_q_sig, sig_align, "query signatures");
+  PVS_ALIGNED(d_word_off, 8, "word offsets");
+  PVS_ALIGNED(d_ent_img, 4, "entry images");
+  PVS_ALIGNED(d_ent_sig, sig_align, "entry signatures");
+  PVS_ALIGNED(d_wt, 4, "word weights");
+  PVS_ALIGNED(d_sel, 4, "selectivity table");
+  PVS_ALIGNED(d_gamma_q, 4, "query normalisers");
+  PVS_ALIGNED(d_gamma_db, 4, "database normalisers");
+  PVS_ALIGNED(d_scores, 4, "scores");
+  PVS_HIP(hipSetDevice(ctx->device));
+
+  for (int64_t q0 = 0; q0 < nq; q0 += ASMK_QUERY_BLOCK) {
+    const int64_t qn = std::min<int64_t>(ASMK_QUERY_BLOCK, nq - q0);
+    int64_t S = slice_images;
+    if (S == 0) {
+      // about two workgroups per compute unit over the query block, no slice below ASMK_MIN_SLICE images
+      const int64_t want = (2 * (int64_t)ctx->num_cu + qn - 1) / qn;
+      const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>(want, N / ASMK_MIN_SLICE));
+      S = std::min<int64_t>(ASMK_MAX_SLICE, ((N + G0 - 1) / G0 + 63) / 64 * 64);
+    }
+    const int64_t G = (N + S - 1) / S;
+    AsmkQueryOffsets qo;
+    for (int64_t q = 0; q <= ASMK_QUERY_BLOCK; ++q) qo.o[q] = h_q_off[q0 + std::min(q, qn)];
+    qo.first = q0;
+    ScopedTimer t(ctx, T_GEMM);   // the scoring slot, as the scans of the compact index
+    const dim3 grid((unsigned)G, (unsigned)qn), block(ASMK_THREADS);
+    const size_t lds = (size_t)S * sizeof(unsigned int);
+#define PVS_ASMK_SCORE(WORDS)                                                                                                        \
+  PVS_TRY(launch_lds(ctx, asmk_score_kernel<WORDS>, grid, block, lds, qo, d_q_word, d_q_sig, K, d_word_off, d_ent_img, d_ent_sig, (int)N, \
+                     d_wt, d_sel, d_gamma_q, d_gamma_db, (int)S, d_scores, ld))
+    switch (W) {
+      case 1: PVS_ASMK_SCORE(1); break;
+      case 2: PVS_ASMK_SCORE(2); break;
+      case 3: PVS_ASMK_SCORE(3); break;
+      default: PVS_ASMK_SCORE(4); break;
+    }
+#undef PVS_ASMK_SCORE
+  }
+  return PVS_OK;
+}

@@ -8,6 +8,7 @@
     from pvsim import IVFCompactIndex                  # the same cut into inverted lists: a query scans nprobe of nlist lists
     from pvsim import QueryExpansion                   # query expansion / database-side augmentation on a DeviceIndex
     from pvsim import Diffusion                        # diffusion re-ranking on the kNN graph of a DeviceIndex
+    from pvsim import ASMKIndex                        # local-descriptor retrieval: ASMK* with binary signatures, an inverted file
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -19,7 +20,8 @@ from ._errors import CapacityError
 from .compact import CompactIndex, IVFCompactIndex, ProductQuantizer
 from .expand import QueryExpansion
 from .diffusion import Diffusion
+from .asmk import ASMKIndex
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion"]
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion", "ASMKIndex"]

@@ -146,6 +146,8 @@ SIGNATURES = {
     "pvs_diffuse_workspace": [_i64, _i64, C.POINTER(_sz)],
     "pvs_diffuse_cg_dev": [_vp, _vp, _vp, _i64, _int, _vp, _i64, C.c_double, C.c_double, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp],
     "pvs_rank_f64_dev": [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp],
+    "pvs_asmk_aggregate_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp],
+    "pvs_asmk_score_dev": [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _i64],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

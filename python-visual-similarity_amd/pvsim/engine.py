@@ -506,6 +506,29 @@ class Context:
         """pvs_rank_f64_dev: rows of float64 scores -> the k best columns by (score descending, column ascending, NaN last)"""
         check(_ffi.lib().pvs_rank_f64_dev(self.handle, ptr(d_scores), int(nq), int(ncols), int(ld), int(k), ptr(d_idx), ptr(d_val)))
 
+    # local-descriptor retrieval, ASMK* (DESIGN.md section 17)
+    def asmk_aggregate_dev(self, cb, d_desc, kind, d_offsets, h_offsets, n_images, total_desc, d_labels, d_proj, bits, d_ent_word,
+                           d_ent_sig, d_ent_count):
+        """pvs_asmk_aggregate_dev: rows + labels -> per image its (word, signature) entries in the slots offsets[i] .. and their
+        count.  h_offsets: the host copy of the CSR offsets, int64 (n_images + 1,)"""
+        h = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        if h.shape != (int(n_images) + 1,):
+            raise ValueError(f"h_offsets must have n_images + 1 = {int(n_images) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_aggregate_dev(self.handle, cb.handle, ptr(d_desc), int(kind), ptr(d_offsets), ptr(h), int(n_images),
+                                                int(total_desc), ptr(d_labels), ptr(d_proj), int(bits), ptr(d_ent_word), ptr(d_ent_sig),
+                                                ptr(d_ent_count)))
+
+    def asmk_score_dev(self, nq, h_q_off, d_q_word, d_q_sig, bits, K, d_word_off, d_ent_img, d_ent_sig, N, d_wt, d_sel, d_gamma_q,
+                       d_gamma_db, d_scores, ld, slice_images=0):
+        """pvs_asmk_score_dev: the entries of nq queries x the inverted file -> the score panel (nq, ld), columns < N written.
+        h_q_off: host int64 (nq + 1,), the entry offsets of the queries"""
+        h = np.ascontiguousarray(h_q_off, dtype=np.int64)
+        if h.shape != (int(nq) + 1,):
+            raise ValueError(f"h_q_off must have nq + 1 = {int(nq) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_score_dev(self.handle, int(nq), ptr(h), ptr(d_q_word), ptr(d_q_sig), int(bits), int(K), ptr(d_word_off),
+                                            ptr(d_ent_img), ptr(d_ent_sig), int(N), ptr(d_wt), ptr(d_sel), ptr(d_gamma_q),
+                                            ptr(d_gamma_db), int(slice_images), ptr(d_scores), int(ld)))
+
     # index maintenance (DESIGN.md section 15)
     SCAN_TILE = _ffi.SCAN_TILE
 
