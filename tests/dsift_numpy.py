@@ -231,9 +231,59 @@ def classify(raw64: np.ndarray):
 
 
 @functools.lru_cache(maxsize=None)
+def edge_inputs():
+    """name -> image of the edge shapes (not part of the default yardsticks), named by shape: exact fits of one descriptor
+    (5 s - 1 pixels: the support touches all four borders), remainders 0 on both axes, and shapes for bin sizes 1 to 3, step 1
+    and sixteen sizes.  uint8 gray and RGB and float32 RGB in turn."""
+    u8 = lambda h, w, seed, ch: np.rint(texture(h, w, seed, ch)).astype(np.uint8)
+    return {
+        "e19x19": u8(19, 19, 61, 1), "e39x39": u8(39, 39, 62, 3), "e89x105": u8(89, 105, 63, 1),
+        "e27x35": texture(27, 35, 64, 3).astype(np.float32), "e75x83": u8(75, 83, 65, 3), "e87x95": u8(87, 95, 66, 1),
+        "e23x31": u8(23, 31, 67, 3), "e59x67": u8(59, 67, 68, 1), "e40x52": texture(40, 52, 69, 3).astype(np.float32),
+        "e83x90": u8(83, 90, 70, 1),
+    }
+
+
+SIXTEEN = tuple(range(1, 17))
+# (input, sizes, step) of the edge comparisons.  e19x19 / e39x39 / e89x105: one descriptor per axis that fits exactly (89 x 105 at
+# s = 18, step 16: one down, two across, both border columns); e27x35: remainder 0 on both axes, six rows; e75x83 / e87x95: the
+# single-descriptor LDS regime (s = 12 / 16) with remainder 0 on both axes, no image has that for both sizes at step 8 (59 and 79
+# differ by 4 mod 8); e23x31: bin sizes 1 to 3 at step 1, 1,085 rows; e59x67: step 1 across the 8 x 8 tile cap and the single-
+# descriptor regime; e40x52: odd sizes at step 3; e83x90: DS_MAX_SIZES = 16 sizes; rect at step 8: the contrast-threshold case
+EDGE_CASES = (("e19x19", (4,), 8), ("e39x39", (8,), 8), ("e89x105", (18,), 16), ("e27x35", (4,), 8), ("e75x83", (12,), 8),
+              ("e87x95", (16,), 8), ("e23x31", (1, 2, 3), 1), ("e59x67", (4, 12), 1), ("e40x52", (2, 5, 7), 3),
+              ("e83x90", SIXTEEN, 8), ("rect", (4, 8), 8))
+
+
+def image(name: str) -> np.ndarray:
+    return inputs()[name] if name in inputs() else edge_inputs()[name]
+
+
+@functools.lru_cache(maxsize=None)
 def twin_pair(name: str, sizes, step: int):
-    img = inputs()[name]
+    img = image(name)
     return dense_sift(img, step, sizes, np.float64), dense_sift(img, step, sizes, np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_yardsticks():
+    """(E, E_raw) of `yardsticks`, over EDGE_CASES alone"""
+    return _yardsticks(EDGE_CASES)
+
+
+@functools.lru_cache(maxsize=None)
+def contrast_case():
+    """-> (threshold, float64 row norms, band) for `rect` at sizes (4, 8), step 8: the threshold lies about the lower quartile of the
+    non-zero row norms, in the middle of the widest gap between neighbouring norms there, so that no row is within `band` =
+    8 E_raw top sqrt(128) of it (a row's norm moves by at most sqrt(128) times the error of an accumulator)."""
+    t64, _ = twin_pair("rect", (4, 8), 8)
+    n = np.sqrt((t64.raw * t64.raw).sum(axis=1))
+    nz = np.sort(n[n > 0])
+    q = len(nz) // 4
+    lo = max(q - 8, 0)
+    k = lo + int(np.argmax(np.diff(nz[lo:q + 9])))
+    band = 8.0 * edge_yardsticks()[1] * float(np.abs(t64.raw).max()) * np.sqrt(128.0)
+    return float(0.5 * (nz[k] + nz[k + 1])), n, band
 
 
 @functools.lru_cache(maxsize=None)
@@ -241,8 +291,12 @@ def yardsticks():
     """(E, E_raw) over all inputs and parameter sets: the largest |twin(float32) - twin(float64)| on the normalised rows of
     the strong rows, and on the raw accumulators of all rows relative to the image's largest accumulator.  Involves no code
     under test."""
+    return _yardsticks(tuple(cases()))
+
+
+def _yardsticks(case_list):
     e = e_raw = 0.0
-    for name, sizes, step in cases():
+    for name, sizes, step in case_list:
         if True:
             t64, t32 = twin_pair(name, sizes, step)
             if t64.raw.shape[0] == 0:

@@ -341,7 +341,7 @@ def sift(image: np.ndarray, prm=DEFAULT, dtype=np.float64, tau: float = 0.0):
         rows = [rows[k] for k in keep]
     raw = np.array([r["raw"] for r in rows], dtype=dtype).reshape(-1, 128)
     v1, v = ds.normalise(raw, dtype)
-    return SimpleNamespace(rows=rows, cands=cands, raw=raw, v1=v1, v=v, u8=ds.quantise(v), dog_max=dog_max, pyr=pyr,
+    return SimpleNamespace(rows=rows, cands=cands, raw=raw, v1=v1, v=v, u8=ds.quantise(v), dog_max=dog_max, pyr=pyr, prm=prm,
                            keys=np.array([r["key"] for r in rows], dtype=np.int64).reshape(-1, 5),
                            frames=np.array([r["frame"] for r in rows], dtype=np.float64).reshape(-1, 6),
                            oct_pos=np.array([r["oct_pos"] for r in rows], dtype=np.float64).reshape(-1, 3))
@@ -381,26 +381,123 @@ def inputs():
 TEXTURED = ("tex_rgb", "tex_gray", "f32_rgb")
 
 
-@functools.lru_cache(maxsize=None)
-def twin32(name: str):
-    return sift(inputs()[name], DEFAULT, np.float32)
+def planted(h: int, w: int, blobs, base: float = 50.0) -> np.ndarray:
+    """float32 gray, integer valued: slightly elongated (1.25 : 1), sheared (0.2) Gaussian blobs (cy, cx, std b, amplitude) on a
+    flat ground.  The shear gives every blob a defined orientation, with two peaks in its histogram."""
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    img = np.full((h, w), base)
+    for cy, cx, b, amp in blobs:
+        img += amp * np.exp(-((yy - cy) ** 2 / (2.0 * (1.25 * b) ** 2) + (xx - cx - 0.2 * (yy - cy)) ** 2 / (2.0 * b * b)))
+    assert img.max() <= 255.0
+    return np.rint(img).astype(np.float32)
+
+
+# The ladder (64 x 96, enlarged to 128 x 192: octaves of 128, 64, 32 and 16 rows).  Centres are in input pixels; octave-0 pixel a
+# is input pixel a / 2 - 0.25.  Small blobs (b = 1.3) land in octave 0, b ~ 3 in octave 1, b ~ 6 in octave 2, b = 11 in octave 3.
+#   (15.75, 15.75)  octave-0 pixel (32, 32): the first pixel of blur tile (1, 1)
+#   (16.15, 47.9)   octave-0 pixel (33, 96): raster index 33 * 192 + 96 = 6432, detect block 25, while (32, 32) is index 6176,
+#                   block 24: two candidates of one layer on either side of the block boundary at index 6400
+#   (2.25, 40.3)    octave-0 row 5: on the 5-pixel margin itself
+#   (5.2, 80.3)     octave-0 row 11
+LADDER = ((15.75, 15.75, 1.3, 110.0), (16.15, 47.9, 1.3, 110.0), (47.8, 16.1, 1.3, 110.0), (5.2, 80.3, 1.3, 110.0),
+          (58.9, 90.6, 1.3, 110.0), (2.25, 40.3, 1.3, 110.0), (31.7, 63.6, 2.8, 80.0), (40.2, 34.9, 3.0, 80.0),
+          (24.3, 31.2, 5.8, 60.0), (36.5, 74.0, 5.6, 60.0), (30.0, 50.0, 11.0, 40.0))
+LADDER_TILE_CORNER = (0, 32, 32)         # (octave, y, x) of integer extrema the ladder must have
+LADDER_MARGIN = (0, 5, 81)
+LADDER_ROW_11 = (0, 11, 161)
+LADDER_BLOCK_PAIR = ((0, 32, 32), (0, 33, 96))
+DETECT_BLOCK = 256                        # pixels of one (octave, layer) per block of the extremum kernel, in raster order
+BLUR_TILE = 32
 
 
 @functools.lru_cache(maxsize=None)
-def _twin64_plain(name: str):
-    return sift(inputs()[name], DEFAULT, np.float64)
+def edge_inputs():
+    """name -> image of the edge cases (not part of the default yardsticks): the ladder above; tiny8 / tiny8w, 8 x 8 and 8 x 13 with
+    one blob, a single octave of exactly 16 rows after the enlargement; thin, 7 x 40, no octave; odd, a 37 x 53 texture whose
+    octaves are 74 -> 37 -> 18 rows (37 -> 18 without the enlargement): an odd octave is halved; pair, two identical blobs 48
+    pixels apart, whose rows tie in response; blobs43 / blobs155, `blobs_f32_gray` with other seeds, for the parameter values at
+    which that input (and the textures) excuse more than the cap with the case's own yardsticks."""
+    return {
+        "ladder": planted(64, 96, LADDER),
+        "tiny8": planted(8, 8, ((3.75, 3.75, 1.3, 110.0),)),
+        "tiny8w": planted(8, 13, ((3.75, 6.25, 1.3, 110.0),)),
+        "thin": planted(7, 40, ((3.0, 20.0, 1.3, 110.0),)),
+        "odd": np.rint(ds.texture(37, 53, 85, 1)).astype(np.uint8),
+        "pair": planted(48, 96, ((23.6, 24.1, 1.3, 110.0), (23.6, 72.1, 1.3, 110.0))),
+        "blobs43": np.rint(blobs(128, 128, 43)).astype(np.float32),
+        "blobs155": np.rint(blobs(128, 128, 155)).astype(np.float32),
+    }
+
+
+PLANTED = ("ladder", "tiny8", "tiny8w", "pair")      # their decision band must be empty; textured inputs may excuse 5 %
+BAND_CAP = 0.05
+
+
+def edge_cases():
+    """[(input name, parameters)]: every comparison beyond the default parameters on `inputs()`"""
+    P = params
+    return [("tex_rgb", P(sigma=1.2)), ("blobs43", P(sigma=2.4)), ("tex_rgb", P(upsample=False)),
+            ("tex_rgb", P(upsample=False, n_octave_layers=4, sigma=2.1)), ("tex_gray", P(n_octave_layers=2)),
+            ("blobs_f32_gray", P(n_octave_layers=1)),                  # blur radius 45: the twin runs it, the device refuses it
+            ("blobs_f32_gray", P(n_octave_layers=1, sigma=1.15)),      # radius 32: L = 1 within the supported blur
+            ("blobs155", P(n_octave_layers=8)),                        # 8 is the largest L
+            ("blobs_f32_gray", P(edge_threshold=3.0)), ("blobs_f32_gray", P(contrast_threshold=0.09)),
+            ("blobs43", P(sigma=4.1)),                                 # the largest sigma with radius 32 at L = 3
+            ("ladder", DEFAULT), ("ladder", P(n_octave_layers=2)), ("ladder", P(n_octave_layers=5)), ("ladder", P(upsample=False)),
+            ("tiny8", DEFAULT), ("tiny8w", DEFAULT), ("thin", DEFAULT), ("odd", DEFAULT), ("odd", P(upsample=False)),
+            ("pair", DEFAULT)]
+
+
+def case_id(case) -> str:
+    name, prm = case
+    d = [f"{k}={v}" for k, v, w in zip(("nfeatures", "L", "C", "r", "sigma", "upsample"), prm_key(prm), prm_key(DEFAULT)) if v != w]
+    return name + ("[" + ",".join(d) + "]" if d else "")
+
+
+MAX_RADIUS = 32                           # the blur radius the device supports (DESIGN section 10: tile + halo within 48 KiB)
+
+
+def band_cap(name: str) -> float:
+    return 0.0 if name in PLANTED else BAND_CAP
+
+
+def blur_radius(prm) -> int:
+    """the largest blur radius of the pyramid"""
+    base, inc = layer_sigmas(prm)
+    return max(int(np.ceil(4.0 * s - 1e-12)) for s in [base] + inc)
+
+
+def prm_key(prm):
+    """The parameters as a hashable tuple, in the argument order of `params`."""
+    return (prm.nfeatures, prm.L, prm.C, prm.r, prm.sigma, prm.upsample)
+
+
+def is_default(prm) -> bool:
+    return prm_key(prm) == prm_key(DEFAULT)
+
+
+def image(name: str) -> np.ndarray:
+    return inputs()[name] if name in inputs() else edge_inputs()[name]
 
 
 @functools.lru_cache(maxsize=None)
-def yardsticks():
-    """float32 twin against float64 twin over all inputs, on keypoints with equal keys: E_dog (DoG values, relative to the image's
-    largest), E_off (refinement offsets of all refined candidates: octave pixels and layer units), E_pos (the same on keypoints
-    only: what the frames carry), E_scl (relative scale of keypoints), E_angle (degrees), E_q / E_det (edge quantity q and the
-    2 x 2 determinant, relative to the square of the largest DoG), E_contr (interpolated value, relative), E_hist (smoothed orientation histogram, relative to its largest bin), E_desc (normalised
-    rows).  Involves no code under test."""
+def _twin32(name: str, key):
+    return sift(image(name), params(*key), np.float32)
+
+
+def twin32(name: str, prm=DEFAULT):
+    return _twin32(name, prm_key(prm))
+
+
+@functools.lru_cache(maxsize=None)
+def _twin64_plain(name: str, key=prm_key(DEFAULT)):
+    return sift(image(name), params(*key), np.float64)
+
+
+def _measure(pairs):
+    """The yardsticks of `yardsticks` over (float64 twin, float32 twin) pairs."""
     e = dict(dog=0.0, off=0.0, pos=0.0, scl=0.0, angle=0.0, q=0.0, det=0.0, hist=0.0, desc=0.0, contr=0.0)
-    for name in inputs():
-        a, b = _twin64_plain(name), twin32(name)
+    for a, b in pairs:
         if not a.pyr or a.dog_max < 1.0:          # a constant image has no DoG scale to relate to (and no candidates)
             continue
         for Ga, Gb in zip(a.pyr, b.pyr):
@@ -430,16 +527,49 @@ def yardsticks():
 
 
 @functools.lru_cache(maxsize=None)
-def twin64(name: str):
-    """float64 twin with the near-candidates of the decision band recorded"""
-    plain = _twin64_plain(name)
-    t = sift(inputs()[name], DEFAULT, np.float64, tau=BAND * yardsticks()["dog"] * plain.dog_max)
+def _yardsticks(name, key):
+    names = list(inputs()) if name is None else [name]
+    return _measure((_twin64_plain(n, key), _twin32(n, key)) for n in names)
+
+
+def yardsticks(name=None, prm=DEFAULT):
+    """float32 twin against float64 twin, on keypoints with equal keys: E_dog (DoG values, relative to the image's
+    largest), E_off (refinement offsets of all refined candidates: octave pixels and layer units), E_pos (the same on keypoints
+    only: what the frames carry), E_scl (relative scale of keypoints), E_angle (degrees), E_q / E_det (edge quantity q and the
+    2 x 2 determinant, relative to the square of the largest DoG), E_contr (interpolated value, relative), E_hist (smoothed orientation histogram, relative to its largest bin), E_desc (normalised
+    rows).  Involves no code under test.
+
+    The default parameters on one of `inputs()` (or no name): the yardsticks over all of `inputs()`, as always.  Any other case
+    (an input of `edge_inputs()`, or non-default parameters) has its own: its float32 twin against its float64 twin."""
+    if is_default(prm) and (name is None or name in inputs()):
+        return _yardsticks(None, prm_key(DEFAULT))
+    return _yardsticks(name, prm_key(prm))
+
+
+@functools.lru_cache(maxsize=None)
+def _twin64(name: str, key):
+    prm = params(*key)
+    plain = _twin64_plain(name, key)
+    e = yardsticks(name, prm)
+    t = sift(image(name), prm, np.float64, tau=BAND * e["dog"] * plain.dog_max)
     assert np.array_equal(t.keys, plain.keys)
+    t.e = e
     return t
 
 
+def twin64(name: str, prm=DEFAULT):
+    """float64 twin of the case (input, parameters) with the near-candidates of the decision band recorded; `.e` holds the
+    case's yardsticks and `.prm` its parameters, which the band helpers below take from there unless told otherwise"""
+    return _twin64(name, prm_key(prm))
+
+
 # ------------------------------------------------------------------------------------------ decision band
-def cand_excused(c, dog_max: float, e=None) -> bool:
+def _of(t, prm, e):
+    """(prm, e) of a twin result unless given: a plain `sift()` result has its parameters but only the default yardsticks"""
+    return prm or t.prm, e or getattr(t, "e", None) or yardsticks()
+
+
+def cand_excused(c, dog_max: float, e=None, prm=DEFAULT) -> bool:
     """One of the candidate's decisions up to the keypoint lies within BAND yardsticks of its threshold (float64 twin only)."""
     e = e or yardsticks()
     tau = BAND * e["dog"] * dog_max
@@ -448,7 +578,7 @@ def cand_excused(c, dog_max: float, e=None) -> bool:
     if c.get("m_off", np.inf) <= BAND * e["off"]:
         return True
     if "q" in c:
-        if abs(abs(c["contr"]) - float(np.float32(255.0 * DEFAULT.C / DEFAULT.L))) <= BAND * e["contr"] * dog_max:
+        if abs(abs(c["contr"]) - float(np.float32(255.0 * prm.C / prm.L))) <= BAND * e["contr"] * dog_max:
             return True
         if c["status"] in ("edge", "keypoint") and (abs(c["q"]) <= BAND * e["q"] * dog_max ** 2
                                                     or abs(c["det2"]) <= BAND * e["det"] * dog_max ** 2):
@@ -470,37 +600,39 @@ def bin_excused(c, b: int, e=None) -> bool:
     return near_peak and not decided
 
 
-def row_excused(t, j: int) -> bool:
+def row_excused(t, j: int, prm=None, e=None) -> bool:
+    prm, e = _of(t, prm, e)
     r = t.rows[j]
-    return cand_excused(r["rec"], t.dog_max) or bin_excused(r["rec"], r["key"][4])
+    return cand_excused(r["rec"], t.dog_max, e, prm) or bin_excused(r["rec"], r["key"][4], e)
 
 
-def band_share(t) -> float:
+def band_share(t, prm=None, e=None) -> float:
     n = len(t.rows)
-    return sum(row_excused(t, j) for j in range(n)) / n if n else 0.0
+    return sum(row_excused(t, j, prm, e) for j in range(n)) / n if n else 0.0
 
 
-def key_excused(t, key) -> bool:
+def key_excused(t, key, prm=None, e=None) -> bool:
     """May a row with this key appear in / be missing from another arithmetic's output?  Looked up in the float64 twin t."""
+    prm, e = _of(t, prm, e)
     for c in t.cands:
         if c["key"] == tuple(key[:4]):
-            if cand_excused(c, t.dog_max):
+            if cand_excused(c, t.dog_max, e, prm):
                 return True
-            return "hist" in c and bin_excused(c, int(key[4]))
+            return "hist" in c and bin_excused(c, int(key[4]), e)
     return False
 
 
-def compare_keys(t64, keys_other):
+def compare_keys(t64, keys_other, prm=None, e=None):
     """-> (keys only in t64 not excused, keys only in the other not excused)"""
     a = {tuple(k) for k in t64.keys.tolist()}
     b = {tuple(k) for k in np.asarray(keys_other).reshape(-1, 5).tolist()}
-    return ([k for k in sorted(a - b) if not key_excused(t64, k)], [k for k in sorted(b - a) if not key_excused(t64, k)])
+    return ([k for k in sorted(a - b) if not key_excused(t64, k, prm, e)], [k for k in sorted(b - a) if not key_excused(t64, k, prm, e)])
 
 
-def match_frames(t64, frames, prm=DEFAULT):
+def match_frames(t64, frames, prm=DEFAULT, e=None):
     """Match keyless frames (n, 6) to the float64 twin's rows: same octave, position / size / angle within BAND yardsticks.
     -> (index of the twin row for every frame, -1 if none; the deviations of the matched ones)"""
-    e = yardsticks()
+    e = e or yardsticks()
     f = np.asarray(frames, dtype=np.float64).reshape(-1, 6)
     idx = np.full(len(f), -1, dtype=np.int64)
     dev = dict(pos=0.0, angle=0.0, size=0.0)
@@ -528,9 +660,10 @@ def match_frames(t64, frames, prm=DEFAULT):
     return idx, dev
 
 
-def frame_excused(t64, frame, prm=DEFAULT) -> bool:
+def frame_excused(t64, frame, prm=DEFAULT, e=None) -> bool:
     """An unmatched frame is excused when an excused candidate of the float64 twin was visited within two octave pixels of it
     (a different move of the refinement ends at most there), or when its keypoint exists and the angle's bin is in the band."""
+    e = e or yardsticks()
     u = 2.0 if prm.upsample else 1.0
     o = int(frame[5])
     sc = 2.0 ** o / u
@@ -542,8 +675,8 @@ def frame_excused(t64, frame, prm=DEFAULT) -> bool:
             continue
         if not any(abs(x - xo) <= 2.0 and abs(y - yo) <= 2.0 for _, y, x in c["visited"]):
             continue
-        if cand_excused(c, t64.dog_max):
+        if cand_excused(c, t64.dog_max, e, prm):
             return True
-        if "hist" in c and any(bin_excused(c, (b + d) % 36) for d in (-1, 0, 1)):
+        if "hist" in c and any(bin_excused(c, (b + d) % 36, e) for d in (-1, 0, 1)):
             return True
     return False

@@ -126,6 +126,62 @@ def test_twin_yardstick_and_input_conditions():
     assert seen_zero and seen_weak and seen_small
 
 
+def test_edge_yardstick_and_conditions():
+    """E and E_raw over the edge cases of tests/test_gpu_dsift_edges.py alone, and what those comparisons rest on: the shapes are
+    the edges they are named for, no weak rows outside `rect`, excused uint8 entries <= 5 %, every float32-vs-float64 uint8
+    mismatch inside the band."""
+    e, e_raw = tw.edge_yardsticks()
+    d, d_raw = tw.yardsticks()
+    print(f"edge cases: E = {e:.3e}  E_raw = {e_raw:.3e}   (default cases: E = {d:.3e}  E_raw = {d_raw:.3e})")
+    assert 0 < e and 8 * e < 1e-4                                            # sanity ceilings only
+    assert 0 < e_raw < 1e-5
+    assert set(tw.inputs()).isdisjoint(tw.edge_inputs())
+    for name, sizes, step in tw.EDGE_CASES:
+        img = tw.image(name)
+        h, w = img.shape[:2]
+        t64, t32 = tw.twin_pair(name, sizes, step)
+        assert t64.raw.shape[0] == tw.count(h, w, step, sizes) > 0
+        zero, weak, strong = tw.classify(t64.raw)
+        assert name == "rect" or not (weak.any() or zero.any())
+        keep = zero | strong
+        excused = tw.excused_entries(t64, 8 * e)[keep]
+        one_e, one_raw = tw._yardsticks(((name, sizes, step),))
+        print(f"{name} sizes={sizes} step={step}: rows {len(zero)} weak {weak.sum()} E {one_e:.2e} E_raw {one_raw:.2e} "
+              f"excused {100 * excused.mean():.2f} %")
+        assert excused.mean() <= 0.05, (name, sizes)
+        diff = np.abs(t64.u8[keep].astype(np.int32) - t32.u8[keep].astype(np.int32))
+        assert diff.max() <= 1 and not (diff.astype(bool) & ~excused).any()
+    rem = lambda name, s, step: tuple((x - 5 * s + 1) % step for x in tw.image(name).shape[:2])
+    for name, s in (("e19x19", 4), ("e39x39", 8)):                           # exactly 5 s - 1: one descriptor, all four borders
+        assert tw.image(name).shape[:2] == (5 * s - 1, 5 * s - 1) and tw.count(5 * s - 1, 5 * s - 1, 8, (s,)) == 1
+    assert tw.image("e89x105").shape == (89, 105) and len(tw.grid(89, 18, 16)) == 1 and len(tw.grid(105, 18, 16)) == 2
+    assert rem("e89x105", 18, 16) == (0, 0) and rem("e27x35", 4, 8) == (0, 0) and tw.count(27, 35, 8, (4,)) == 6
+    assert rem("e75x83", 12, 8) == (0, 0) and rem("e87x95", 16, 8) == (0, 0)      # the single-descriptor regime, remainder 0
+    assert tw.count(23, 31, 1, (1, 2, 3)) == 1085
+    assert len(tw.grid(59, 4, 1)) > 8 * 4 and len(tw.grid(67, 12, 1)) == 9       # beyond the 8 x 8 tile cap; s = 12: one per tile
+    assert len(tw.SIXTEEN) == 16 and min(tw.image("e83x90").shape) >= 5 * 16 - 1
+    from pvsim import engine
+    assert engine.dsift_count(83, 90, 8, tw.SIXTEEN) == tw.count(83, 90, 8, tw.SIXTEEN)
+    with pytest.raises(NotImplementedError):
+        engine.dsift_count(83, 90, 8, tuple(range(1, 18)))                        # DS_MAX_SIZES = 16
+
+
+def test_contrast_threshold_sits_between_the_row_norms():
+    thr, norms, band = tw.contrast_case()
+    nz = np.sort(norms[norms > 0])
+    near = float(np.abs(norms - thr).min())
+    print(f"rect sizes (4, 8) step 8: {len(norms)} rows, norms 0 .. {norms.max():.1f}, quartiles of the non-zero ones "
+          f"{np.quantile(nz, (0.25, 0.5, 0.75)).round(1).tolist()}; threshold {thr:.3f}, nearest norm {near:.3f} away, band {band:.4f}")
+    assert near > band                                                        # no row of the twin may flip
+    assert nz[len(nz) // 4 - 8] < thr < nz[len(nz) // 4 + 9]                  # about the lower quartile
+    below = (norms <= thr) & (norms > 0)
+    assert below.sum() >= len(nz) // 8 and (norms > thr).sum() >= len(nz) // 2
+    for dtype in (np.float64, np.float32):
+        t = tw.dense_sift(tw.image("rect"), 8, (4, 8), dtype, contrast_threshold=thr)
+        assert np.array_equal(~t.v.any(axis=1), norms <= thr) and np.array_equal(~t.u8.any(axis=1), norms <= thr)
+        assert t.raw.any(axis=1)[below].all()                                 # the accumulators are not touched
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 def test_twin_mirror_property(dtype):
     """(W - 5 s + 1) % step == 0: the flipped image gives the same rows with x0 reversed, i -> 3 - i, o -> (4 - o) mod 8."""

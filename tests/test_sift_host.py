@@ -123,6 +123,114 @@ def test_nfeatures_keeps_the_strongest_in_order():
     assert np.array_equal(part.keys, full.keys[sorted(order)])
 
 
+@pytest.mark.parametrize("case", tw.edge_cases(), ids=tw.case_id)
+def test_edge_case_twins_agree_outside_the_band_and_yardsticks_are_printed(case):
+    """Every case of tests/test_gpu_sift_edges.py: its own yardsticks (float32 twin against float64 twin of this input and these
+    parameters), the two twins equal outside the band, and the band within its cap: empty on a planted input, 5 % on a texture."""
+    name, prm = case
+    e = tw.yardsticks(name, prm)
+    t64, t32 = tw.twin64(name, prm), tw.twin32(name, prm)
+    assert t64.e is e and tw.prm_key(t64.prm) == tw.prm_key(prm)
+    only64, only32 = tw.compare_keys(t64, t32.keys)
+    share = tw.band_share(t64)
+    print(f"{tw.case_id(case)}: {len(t64.rows)} keypoints (float64), {len(t32.rows)} (float32), octaves {sorted(set(t64.keys[:, 0].tolist()))}, "
+          f"blur radius {tw.blur_radius(prm)}, band share {100 * share:.2f} % (cap {100 * tw.band_cap(name):.0f} %)")
+    print("    yardsticks:", {k: f"{v:.3e}" for k, v in e.items()})
+    assert not only64 and not only32
+    assert share <= tw.band_cap(name)
+    if name == "thin":
+        assert not t64.pyr and not t64.rows and not any(e.values())
+        return
+    assert len(t64.rows) >= (100 if name in tw.TEXTURED else 2)
+    assert 0 < e["dog"] < 1e-4 and 0 < e["desc"] < 1e-3 and 0 < e["pos"] < 5e-3 and 0 < e["off"] < 5e-3          # sanity ceilings only
+    assert 0 < e["angle"] < 0.05 and 0 < e["hist"] < 1e-3 and 0 < e["q"] < 1e-2 and 0 < e["scl"] < 1e-3 and 0 < e["contr"] < 1e-4
+    kb = {tuple(k): j for j, k in enumerate(t32.keys.tolist())}
+    ja, jb = map(list, zip(*[(j, kb[tuple(k)]) for j, k in enumerate(t64.keys.tolist()) if tuple(k) in kb]))
+    assert np.abs(t64.u8[ja].astype(int) - t32.u8[jb].astype(int)).max() <= 1
+    # the contrast line follows the case's parameters: a keypoint is at or above 255 C / L, a contrast reject below
+    thr = float(np.float32(255.0 * prm.C / prm.L))
+    assert all(abs(c["contr"]) >= thr for c in t64.cands if c["status"] == "keypoint")
+    assert all(abs(c["contr"]) < thr for c in t64.cands if c["status"] == "contrast")
+
+
+def test_default_cases_keep_their_yardsticks():
+    """The default parameters on the six inputs share the yardsticks over those six, whatever else has been measured."""
+    e = tw.yardsticks()
+    for name in tw.inputs():
+        assert tw.yardsticks(name) is e and tw.yardsticks(name, tw.params()) is e and tw.twin64(name).e is e
+    assert tw.yardsticks("ladder") is not e and tw.yardsticks("tex_rgb", tw.params(sigma=1.2)) is not e
+    assert set(tw.inputs()).isdisjoint(tw.edge_inputs())
+
+
+def test_the_ladder_reaches_every_octave_and_seam():
+    """What the ladder is planted for, from the float64 twin alone."""
+    img = tw.image("ladder")
+    assert img.shape == (64, 96) and img.dtype == np.float32 and np.array_equal(img, np.rint(img))
+    t = tw.twin64("ladder")
+    assert [g.shape[1:] for g in t.pyr] == [(128, 192), (64, 96), (32, 48), (16, 24)]
+    for prm in (tw.DEFAULT, tw.params(n_octave_layers=2), tw.params(n_octave_layers=5)):
+        tp = tw.twin64("ladder", prm)
+        assert set(tp.keys[:, 0].tolist()) == {0, 1, 2, 3}, prm.L                  # every octave, the 16-row one included
+        assert tw.band_share(tp) == 0.0
+    assert set(tw.twin64("ladder", tw.params(upsample=False)).keys[:, 0].tolist()) == {0, 1, 2}
+    at = {(o, y, x): i for o, i, y, x, _ in t.keys.tolist()}
+    assert tw.LADDER_TILE_CORNER in at and tw.LADDER_TILE_CORNER[1] % tw.BLUR_TILE == 0 and tw.LADDER_TILE_CORNER[2] % tw.BLUR_TILE == 0
+    assert tw.LADDER_MARGIN in at and tw.LADDER_MARGIN[1] == tw.BORDER             # on the margin itself
+    assert tw.LADDER_ROW_11 in at and tw.LADDER_ROW_11[1] == 11
+    (oa, ya, xa), (ob, yb, xb) = tw.LADDER_BLOCK_PAIR
+    w0 = t.pyr[0].shape[2]
+    assert oa == ob == 0 and at[(oa, ya, xa)] == at[(ob, yb, xb)]                  # one layer,
+    assert (ya * w0 + xa) // tw.DETECT_BLOCK + 1 == (yb * w0 + xb) // tw.DETECT_BLOCK   # neighbouring detect blocks
+    two_rows = sum(1 for c in t.cands if len(c.get("peaks", ())) >= 2)
+    print(f"ladder: {len(t.rows)} rows of {sum(c['status'] == 'keypoint' for c in t.cands)} keypoints, {two_rows} with several orientations; "
+          f"keys {t.keys.tolist()}")
+    assert two_rows >= 6
+
+
+def test_tiny_thin_odd_and_pair_are_what_they_are_planted_for():
+    for name, shape in (("tiny8", (16, 16)), ("tiny8w", (16, 26))):
+        t = tw.twin64(name)
+        assert [g.shape[1:] for g in t.pyr] == [shape]                                # one octave of exactly 16 rows
+        assert len(t.rows) == 2 and t.keys[0, :4].tolist() == t.keys[1, :4].tolist()  # one keypoint, two orientations
+        assert tw.band_share(t) == 0.0
+    assert tw.image("thin").shape == (7, 40) and not tw.twin64("thin").pyr and not tw.twin32("thin").rows
+    odd = tw.twin64("odd")
+    assert [g.shape[1] for g in odd.pyr] == [74, 37, 18] and [g.shape[2] for g in odd.pyr] == [106, 53, 26]
+    assert 2 in odd.keys[:, 0]                                                        # keypoints beyond the odd octave that is halved
+    odd1 = tw.twin64("odd", tw.params(upsample=False))
+    assert [g.shape[1:] for g in odd1.pyr] == [(37, 53), (18, 26)] and 1 in odd1.keys[:, 0]
+    pair = tw.twin32("pair")
+    resp = np.float32(pair.frames[:, 4])
+    print(f"pair: float32 responses {resp.tolist()}, keys {pair.keys.tolist()}")
+    assert len(resp) == 4 and len(set(resp.tolist())) == 1                            # bit-equal: all four rows tie
+    assert pair.keys[2, 3] - pair.keys[0, 3] == 2 * 48 and tw.band_share(tw.twin64("pair")) == 0.0
+
+
+@pytest.mark.parametrize("name", ["ladder", "pair"])
+def test_nfeatures_cuts_through_ties_in_row_order(name):
+    """Every n up to the row count, with the cuts between the two rows of one keypoint and between the two equal blobs."""
+    for dtype in (np.float64, np.float32):
+        full = tw.sift(tw.image(name), tw.DEFAULT, dtype)
+        m = len(full.rows)
+        resp = np.float32(full.frames[:, 4])
+        order = sorted(range(m), key=lambda k: (-resp[k], k))
+        assert sum(resp[order[k]] == resp[order[k + 1]] for k in range(m - 1)) >= (3 if name == "pair" else 6)
+        for n in range(1, m + 1):
+            part = tw.sift(tw.image(name), tw.params(nfeatures=n), dtype)
+            assert np.array_equal(part.keys, full.keys[sorted(order[:n])]), n
+            assert np.array_equal(part.u8, full.u8[sorted(order[:n])]), n
+
+
+def test_blur_radius_limits_of_the_cases():
+    P = tw.params
+    assert tw.blur_radius(tw.DEFAULT) == 13
+    assert tw.blur_radius(P(sigma=4.1)) == tw.MAX_RADIUS == 32 and tw.blur_radius(P(sigma=4.15)) == 33
+    wr = tw.BLUR_TILE + 2 * tw.MAX_RADIUS
+    assert (wr * wr + wr * tw.BLUR_TILE) * 4 == 48 * 1024                              # tile + halo and the row pass: exactly 48 KiB
+    assert tw.blur_radius(P(n_octave_layers=1)) == 45 and tw.blur_radius(P(n_octave_layers=1, sigma=1.15)) == 32
+    assert len(tw.gaussian_taps(tw.layer_sigmas(P(sigma=4.1))[1][-1])) == 65
+
+
 def test_host_api_validation_repr_and_symbols():
     from pvsim import CapacityError, _ffi
     from pvsim.engine import sift_workspace
