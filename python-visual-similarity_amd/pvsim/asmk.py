@@ -108,18 +108,13 @@ def device_entries(ctx, cb, d_rows, offsets, kind, d_proj, bits):
     n, total, W = len(offsets) - 1, int(offsets[-1]), bits // 32
     if n == 0 or total == 0:
         return np.zeros(n + 1, np.int64), np.zeros(0, np.int32), np.zeros((0, W), np.uint32)
-    bufs = [ctx.buffer(total * 4), ctx.buffer(total * 4), ctx.buffer(total * 4 * W), ctx.buffer(n * 4), ctx.buffer((n + 1) * 8)]
-    d_lab, d_word, d_sig, d_cnt, d_off = bufs
-    try:
-        d_off.upload(offsets)
+    with ctx.scratch() as tmp:
+        d_lab, d_word, d_sig, d_cnt, d_off = tmp(total * 4), tmp(total * 4), tmp(total * 4 * W), tmp(n * 4), tmp.upload(offsets)
         ctx.kmeans_predict_dev(cb, d_rows, kind, total, d_lab.ptr)
         ctx.asmk_aggregate_dev(cb, d_rows, kind, d_off.ptr, offsets, n, total, d_lab.ptr, d_proj, bits, d_word.ptr, d_sig.ptr, d_cnt.ptr)
         counts = d_cnt.download((n,), np.int32).astype(np.int64)
         words = d_word.download((total,), np.int32)
         sigs = d_sig.download((total, W), np.uint32)
-    finally:
-        for b in bufs:
-            b.free()
     ent_off = np.zeros(n + 1, np.int64)
     np.cumsum(counts, out=ent_off[1:])
     slot = np.arange(total, dtype=np.int64) - np.repeat(offsets[:-1], np.diff(offsets))     # position of a slot inside its image
@@ -205,13 +200,12 @@ class ASMKIndex:
             raise NotImplementedError(f"an image of more than {MAX_ROWS} rows cannot be indexed")
         ctx = local.ctx
         cb = ctx.codebook(cent)
-        d_proj = ctx.buffer(projection.nbytes).upload(projection) if projection is not None else None
         try:
-            ent_off, words, sigs = device_entries(ctx, cb, local.rows.ptr, local.offsets, desc_kind, d_proj.ptr if d_proj else None, bits)
+            with ctx.scratch() as tmp:
+                d_proj = tmp.upload(projection).ptr if projection is not None else None
+                ent_off, words, sigs = device_entries(ctx, cb, local.rows.ptr, local.offsets, desc_kind, d_proj, bits)
         finally:
             cb.close()
-            if d_proj is not None:
-                d_proj.free()
         N = len(local)
         word_off, ent_img, ent_sig = invert(ent_off, words, sigs, K)
         wt = word_weights(np.diff(word_off), N, idf)          # an image holds a word at most once: df = the length of the list
@@ -235,18 +229,13 @@ class ASMKIndex:
         ctx = local.ctx
         keep = np.zeros(total, np.uint8)
         keep[np.random.RandomState(random_state).permutation(total)[:want]] = 1
-        bufs = [ctx.buffer(want * 128), ctx.buffer(want * 128 * 4), ctx.buffer(total), ctx.buffer((total + 1) * 8)]
-        stage, out, d_keep, d_pos = bufs
-        try:
-            d_keep.upload(keep)                                # the sampled rows, in index order, gathered by the row compaction
+        with ctx.scratch() as tmp:                             # the sampled rows, in index order, gathered by the row compaction
+            stage, out, d_keep, d_pos = tmp(want * 128), tmp(want * 128 * 4), tmp.upload(keep), tmp((total + 1) * 8)
             ctx.keep_positions_dev(d_keep.ptr, total, d_pos.ptr)
             ctx.compact_rows_dev(local.rows.ptr, total, 128, d_keep.ptr, d_pos.ptr, stage.ptr)
             ctx.materialise_dev(stage.ptr, kind, 128, want, out.ptr)
             ctx.sync()
             model = learn.fit_kmeans(learn.DeviceRows(ctx, want, 128, out), int(n_words), max_iter=max_iter, random_state=random_state)
-        finally:
-            for b in bufs:
-                b.free()
         return cls.build(local, model, random_state=random_state, **build_kwargs)
 
     # -------------------------------------------------------------------------------------------------- access
@@ -293,7 +282,7 @@ class ASMKIndex:
             dev = {"cb": ctx.codebook(self.centroids)}
             for name in ("word_off", "ent_img", "ent_sig", "gamma_db", "wt", "sel", "projection"):
                 a = getattr(self, name)
-                dev[name] = None if a is None else ctx.buffer(max(a.nbytes, 16)).upload(a) if a.nbytes else ctx.buffer(16)
+                dev[name] = None if a is None else ctx.buffer(a.nbytes).upload(a) if a.nbytes else ctx.buffer(0)
             self._dev = dev
         return self._dev
 
@@ -344,14 +333,9 @@ class ASMKIndex:
         gq = gammas(ent_off, words, self.wt)
         ctx, dev = self.ctx, self._resident()
         qb = int(max(1, min(nq, PANEL_BYTES // (4 * N))))
-        bufs = [ctx.buffer(max(words.nbytes, 16)), ctx.buffer(max(sigs.nbytes, 16)), ctx.buffer(nq * 4), ctx.buffer(qb * N * 4),
-                ctx.buffer(nq * kk * 8), ctx.buffer(nq * kk * 4)]
-        d_word, d_sig, d_gq, d_panel, d_idx, d_val = bufs
-        try:
-            if len(words):
-                d_word.upload(words)
-                d_sig.upload(sigs)
-            d_gq.upload(gq)
+        with ctx.scratch() as tmp:
+            d_word, d_sig, d_gq = tmp.upload(words), tmp.upload(sigs), tmp.upload(gq)
+            d_panel, d_idx, d_val = tmp(qb * N * 4), tmp(nq * kk * 8), tmp(nq * kk * 4)
             for q0 in range(0, nq, qb):                     # whole rows of the panel: each block's ranking is final
                 qn = min(qb, nq - q0)
                 ctx.asmk_score_dev(qn, ent_off[q0:q0 + qn + 1], d_word.ptr, d_sig.ptr, self.bits, self.n_words, dev["word_off"].ptr,
@@ -360,9 +344,6 @@ class ASMKIndex:
                 ctx.topk_dev(d_panel.ptr, qn, N, N, kk, 0, 0, d_idx.ptr + q0 * kk * 8, d_val.ptr + q0 * kk * 4)
             idx[:, :kk] = d_idx.download((nq, kk), np.int64)
             val[:, :kk] = d_val.download((nq, kk), np.float32)
-        finally:
-            for b in bufs:
-                b.free()
         return idx, val
 
     def rank_rows(self, rows_list, k: int):
@@ -375,13 +356,9 @@ class ASMKIndex:
         off = np.zeros(len(rows_list) + 1, np.int64)
         np.cumsum([len(r) for r in rows_list], out=off[1:])
         total = int(off[-1])
-        d_rows = self.ctx.buffer(max(total, 1) * D * np.dtype(dt).itemsize)
-        try:
-            if total:
-                d_rows.upload(np.concatenate(rows_list))
+        with self.ctx.scratch() as tmp:
+            d_rows = tmp.upload(np.concatenate(rows_list) if total else np.zeros((0, D), dt))
             ent = self.query_entries(d_rows.ptr, off)
-        finally:
-            d_rows.free()
         return self.rank_entries(*ent, k)
 
     def rank_images(self, images, k: int):

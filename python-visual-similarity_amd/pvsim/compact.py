@@ -8,12 +8,20 @@ from __future__ import annotations
 
 import numpy as np
 
+from .engine import DeviceBuffer
+from .index import DeviceIndex, _PathLedger, _grow_rows, _keep_positions
 from .models import PCAModel
 
 __all__ = ["ProductQuantizer", "CompactIndex", "IVFCompactIndex", "fit_projection", "save_arrays", "load_arrays"]
 
 _MAX_PROJECTION_TRAIN = 4096
 _CHUNK_ROWS = 8192
+
+
+def _chunks(n: int):
+    """(first row, rows) of the chunks of at most _CHUNK_ROWS rows that n rows go through the device in"""
+    for r0 in range(0, n, _CHUNK_ROWS):
+        yield r0, min(_CHUNK_ROWS, n - r0)
 
 
 def _f32_rows(a, what: str) -> np.ndarray:
@@ -62,11 +70,8 @@ def fit_projection(vectors: np.ndarray, n_components: int, ctx=None) -> np.ndarr
     if not 1 <= d <= min(n, L):
         raise ValueError(f"n_components={n_components} must be between 1 and min(n_train, L)={min(n, L)}")
     ctx = ctx or default_context()
-    bufs = []
-    try:
-        d_x = ctx.buffer(x.nbytes).upload(x)
-        d_g = ctx.buffer(n * n * 4)
-        bufs += [d_x, d_g]
+    with ctx.scratch() as tmp:
+        d_x, d_g = tmp.upload(x), tmp(n * n * 4)
         ctx.cosine_dev(d_x.ptr, n, d_x.ptr, n, L, None, None, d_g.ptr, n)
         g = d_g.download((n, n), np.float32).astype(np.float64)
         g = 0.5 * (g + g.T)
@@ -77,15 +82,9 @@ def fit_projection(vectors: np.ndarray, n_components: int, ctx=None) -> np.ndarr
             raise ValueError(f"the training rows span fewer than n_components={d} dimensions")
         a = np.ascontiguousarray((vecs / np.sqrt(vals)).T, dtype=np.float32)           # Lambda^(-1/2) U^T, (d, n)
         xt = np.ascontiguousarray(x.T)                                                 # (L, n): W = a . (X^T)^T
-        d_a = ctx.buffer(a.nbytes).upload(a)
-        d_xt = ctx.buffer(xt.nbytes).upload(xt)
-        d_w = ctx.buffer(d * L * 4)
-        bufs += [d_a, d_xt, d_w]
+        d_a, d_xt, d_w = tmp.upload(a), tmp.upload(xt), tmp(d * L * 4)
         ctx.cosine_dev(d_a.ptr, d, d_xt.ptr, L, n, None, None, d_w.ptr, L)
         w = d_w.download((d, L), np.float32)
-    finally:
-        for b in bufs:
-            b.free()
     piv = np.argmax(np.abs(w), axis=1)
     sign = np.sign(w[np.arange(d), piv])
     sign[sign == 0] = 1
@@ -168,13 +167,10 @@ class ProductQuantizer:
         books = np.empty((self.m, self.ksub, dsub), np.float32)
         import warnings
         for s in range(self.m):
-            rows = DeviceRows.from_host(self.context, x[:, s * dsub:(s + 1) * dsub])
-            try:
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore", UserWarning)         # duplicate points in a sub-space: fewer distinct codewords is fine
-                    books[s] = fit_kmeans(rows, self.ksub, random_state=rng, max_iter=max_iter).cluster_centers_
-            finally:
-                rows.free()
+            with self.context.scratch() as tmp, warnings.catch_warnings():
+                warnings.simplefilter("ignore", UserWarning)             # duplicate points in a sub-space: fewer distinct codewords is fine
+                rows = DeviceRows(self.context, n, dsub, tmp.upload(x[:, s * dsub:(s + 1) * dsub]))
+                books[s] = fit_kmeans(rows, self.ksub, random_state=rng, max_iter=max_iter).cluster_centers_
         self.codebooks = books
         self._drop_table()
         return self
@@ -202,14 +198,10 @@ class ProductQuantizer:
         if n == 0:
             return np.zeros((0, self.m), np.uint8)
         ctx = self.context
-        d_x = ctx.buffer(x.nbytes).upload(x)
-        d_c = ctx.buffer(n * self.m)
-        try:
+        with ctx.scratch() as tmp:
+            d_x, d_c = tmp.upload(x), tmp(n * self.m)
             ctx.pq_encode_dev(self.table(), d_x.ptr, n, d_c.ptr)
             return d_c.download((n, self.m), np.uint8)
-        finally:
-            d_x.free()
-            d_c.free()
 
     def decode(self, codes) -> np.ndarray:
         """codes uint8 (n, m) -> the codewords they name, float32 (n, d)."""
@@ -308,7 +300,6 @@ class CompactIndex:
         """fit(); with `nlist` the rows are assigned to nlist coarse centroids (k-means on the projected training rows) and the
         quantiser is trained on, and encodes, their residuals (IVFCompactIndex)."""
         from .engine import default_context
-        from .index import DeviceIndex
         resident = source if isinstance(source, DeviceIndex) else None
         if resident is not None:
             paths, mat = list(resident.keys()), resident.matrix
@@ -334,105 +325,82 @@ class CompactIndex:
             nlist = _check_nlist(nlist, tr.shape[0], n)
         ctx = ctx or default_context()
         pq._ctx = ctx
-        from .engine import DeviceBuffer
         w = fit_projection(tr, n_components, ctx) if n_components is not None else _projection_matrix(projection, L)
-        live = []                                    # device buffers of this call: all of them are freed if anything below raises
 
-        def take(nbytes):
-            live.append(ctx.buffer(max(nbytes, 16)))
-            return live[-1]
-
-        def give(b):
-            if b in live:                            # views into the kept rows are not owned
-                live.remove(b)
-                b.free()
-
-        def project_chunks(host, dev_ptr=None, dest=None):
-            """yields (first row, rows, device buffer of the projected rows (rows, d)) over chunks of the matrix; `dest(r0, rn)`
-            names where a chunk goes (a view into the kept rows), otherwise it is a temporary the consumer gives back"""
-            for r0 in range(0, host.shape[0], _CHUNK_ROWS):
-                rn = min(_CHUNK_ROWS, host.shape[0] - r0)
-                out = dest(r0, rn) if dest is not None else take(rn * d * 4)
-                if d_w is None:                      # no projection: the rows themselves
-                    out.upload(host[r0:r0 + rn])
-                elif dev_ptr is not None:            # resident rows are read in place
-                    ctx.cosine_dev(dev_ptr + r0 * L * 4, rn, d_w.ptr, d, L, None, None, out.ptr, d)
-                else:
-                    own = take(rn * L * 4).upload(host[r0:r0 + rn])
-                    ctx.cosine_dev(own.ptr, rn, d_w.ptr, d, L, None, None, out.ptr, d)
+        def projected(chunk, host, r0, rn, dev_ptr=None, dest=None):
+            """rows [r0, r0 + rn) of the matrix, projected -> device buffer (rn, d): `dest(r0, rn)` (a view into the kept rows, not
+            owned) or a temporary of the scratch scope `chunk`"""
+            out = dest(r0, rn) if dest is not None else chunk(rn * d * 4)
+            if d_w is None:                          # no projection: the rows themselves
+                out.upload(host[r0:r0 + rn])
+            elif dev_ptr is not None:                # resident rows are read in place
+                ctx.cosine_dev(dev_ptr + r0 * L * 4, rn, d_w.ptr, d, L, None, None, out.ptr, d)
+            else:
+                with ctx.scratch() as own:
+                    ctx.cosine_dev(own.upload(host[r0:r0 + rn]).ptr, rn, d_w.ptr, d, L, None, None, out.ptr, d)
                     ctx.sync()
-                    give(own)
-                yield r0, rn, out
+            return out
 
         try:
-            d_w = take(w.nbytes).upload(w) if w is not None else None
-            db_ptr = resident._db.ptr if resident is not None else None
-            # the quantiser is trained on the projected training rows
-            ytr = np.empty((tr.shape[0], d), np.float32)
-            for r0, rn, buf in project_chunks(tr, db_ptr if train is None else None):
-                ytr[r0:r0 + rn] = buf.download((rn, d), np.float32)
-                give(buf)
-            d_cent = d_lists = d_res = None
-            if nlist is None:
-                pq.fit(ytr, random_state=random_state, max_iter=max_iter)
-            else:                                    # coarse centroids, then the quantiser on the training rows' residuals
-                from .learn import _rng
-                rng = _rng(random_state)
-                cent = _fit_coarse(ctx, ytr, nlist, rng, max_iter)
-                d_cent = take(cent.nbytes).upload(cent)
-                res = np.empty_like(ytr)
-                for r0 in range(0, ytr.shape[0], _CHUNK_ROWS):
-                    rn = min(_CHUNK_ROWS, ytr.shape[0] - r0)
-                    d_y, d_l, d_r = take(rn * d * 4).upload(ytr[r0:r0 + rn]), take(rn * 4), take(rn * d * 4)
-                    ctx.ivf_assign_dev(d_y.ptr, rn, d, d_cent.ptr, nlist, d_l.ptr, d_r.ptr)
-                    res[r0:r0 + rn] = d_r.download((rn, d), np.float32)
-                    give(d_y), give(d_l), give(d_r)
-                pq.fit(res, random_state=rng, max_iter=max_iter)
-                del res
-                d_lists, d_res = take(n * 4), take(min(n, _CHUNK_ROWS) * d * 4)
-            table = pq.table()
-            d_codes, d_inv = take(n * pq.m), take(n * 4)
-            d_proj = take(n * d * 4) if keep_projected else None
-            # kept rows are written where they stay: a chunk's buffer is then a view into d_proj
-            dest = (lambda r0, rn: DeviceBuffer.view(ctx, d_proj.ptr + r0 * d * 4, rn * d * 4)) if keep_projected else None
-            if train is None:                        # the database was the training set: its projected rows are in ytr
-                def chunks():
-                    for r0 in range(0, n, _CHUNK_ROWS):
-                        rn = min(_CHUNK_ROWS, n - r0)
-                        out = dest(r0, rn) if dest is not None else take(rn * d * 4)
-                        yield r0, rn, out.upload(ytr[r0:r0 + rn])
-                chunks = chunks()
-            else:
-                chunks = project_chunks(mat, db_ptr, dest)
-            for r0, rn, buf in chunks:
-                ctx.row_inv_norms_dev(buf.ptr, rn, d, d_inv.ptr + r0 * 4)
+            with ctx.scratch() as tmp:               # device buffers of this call; what the index keeps leaves the scope at the end
+                d_w = tmp.upload(w) if w is not None else None
+                db_ptr = resident._db.ptr if resident is not None else None
+                # the quantiser is trained on the projected training rows
+                ytr = np.empty((tr.shape[0], d), np.float32)
+                for r0, rn in _chunks(tr.shape[0]):
+                    with ctx.scratch() as chunk:
+                        ytr[r0:r0 + rn] = projected(chunk, tr, r0, rn, db_ptr if train is None else None).download((rn, d), np.float32)
+                d_cent = d_lists = d_res = None
                 if nlist is None:
-                    ctx.pq_encode_dev(table, buf.ptr, rn, d_codes.ptr + r0 * pq.m)
-                else:
-                    ctx.ivf_assign_dev(buf.ptr, rn, d, d_cent.ptr, nlist, d_lists.ptr + r0 * 4, d_res.ptr)
-                    ctx.pq_encode_dev(table, d_res.ptr, rn, d_codes.ptr + r0 * pq.m)
-                ctx.sync()
-                give(buf)
-            if d_w is not None:
-                give(d_w)
-            extra = {}
-            if nlist is not None:                    # sort into lists: by (list, original index), on the host
-                give(d_res)
-                lists = d_lists.download((n,), np.int32)
-                give(d_lists)
-                ids, list_off = _sort_into_lists(lists, nlist)
-                d_codes.upload(np.ascontiguousarray(d_codes.download((n, pq.m), np.uint8)[ids]))
-                d_inv.upload(np.ascontiguousarray(d_inv.download((n,), np.float32)[ids]))
-                extra = dict(cent=d_cent, ids=take(n * 4).upload(ids), list_off=take(list_off.nbytes).upload(list_off))
+                    pq.fit(ytr, random_state=random_state, max_iter=max_iter)
+                else:                                    # coarse centroids, then the quantiser on the training rows' residuals
+                    from .learn import _rng
+                    rng = _rng(random_state)
+                    cent = _fit_coarse(ctx, ytr, nlist, rng, max_iter)
+                    d_cent = tmp.upload(cent)
+                    res = np.empty_like(ytr)
+                    for r0, rn in _chunks(ytr.shape[0]):
+                        with ctx.scratch() as chunk:
+                            d_y, d_l, d_r = chunk.upload(ytr[r0:r0 + rn]), chunk(rn * 4), chunk(rn * d * 4)
+                            ctx.ivf_assign_dev(d_y.ptr, rn, d, d_cent.ptr, nlist, d_l.ptr, d_r.ptr)
+                            res[r0:r0 + rn] = d_r.download((rn, d), np.float32)
+                    pq.fit(res, random_state=rng, max_iter=max_iter)
+                    del res
+                    d_lists, d_res = tmp(n * 4), tmp(min(n, _CHUNK_ROWS) * d * 4)
+                table = pq.table()
+                # the arrays `add` appends to hold at least 16 bytes: _reserve_rows reads their size as the capacity
+                d_codes, d_inv = tmp(max(n * pq.m, 16)), tmp(max(n * 4, 16))
+                d_proj = tmp(max(n * d * 4, 16)) if keep_projected else None
+                # kept rows are written where they stay: a chunk's buffer is then a view into d_proj
+                dest = (lambda r0, rn: DeviceBuffer.view(ctx, d_proj.ptr + r0 * d * 4, rn * d * 4)) if keep_projected else None
+                for r0, rn in _chunks(n):
+                    with ctx.scratch() as chunk:
+                        if train is None:                # the database was the training set: its projected rows are in ytr
+                            buf = (dest(r0, rn) if dest is not None else chunk(rn * d * 4)).upload(ytr[r0:r0 + rn])
+                        else:
+                            buf = projected(chunk, mat, r0, rn, db_ptr, dest)
+                        ctx.row_inv_norms_dev(buf.ptr, rn, d, d_inv.ptr + r0 * 4)
+                        if nlist is None:
+                            ctx.pq_encode_dev(table, buf.ptr, rn, d_codes.ptr + r0 * pq.m)
+                        else:
+                            ctx.ivf_assign_dev(buf.ptr, rn, d, d_cent.ptr, nlist, d_lists.ptr + r0 * 4, d_res.ptr)
+                            ctx.pq_encode_dev(table, d_res.ptr, rn, d_codes.ptr + r0 * pq.m)
+                        ctx.sync()
+                dev = dict(codes=d_codes, inv=d_inv, projected=d_proj, w=None)
+                if nlist is not None:                    # sort into lists: by (list, original index), on the host
+                    ids, list_off = _sort_into_lists(d_lists.download((n,), np.int32), nlist)
+                    d_codes.upload(np.ascontiguousarray(d_codes.download((n, pq.m), np.uint8)[ids]))
+                    d_inv.upload(np.ascontiguousarray(d_inv.download((n,), np.float32)[ids]))
+                    dev.update(cent=d_cent, ids=tmp.upload(ids), list_off=tmp.upload(list_off))
+                for b in dev.values():                   # these are the index's from here on
+                    tmp.keep(b)
         except BaseException:
-            for b in live:
-                b.free()
-            pq.close()
+            pq.close()                               # the quantiser's device table
             raise
         self = cls.__new__(cls)
         self.quantizer, self._paths, self._ctx = pq, [str(p) for p in paths], ctx
         self._L, self._w, self._keep, self._host = L, w, bool(keep_projected), None
-        self._dev = dict(codes=d_codes, inv=d_inv, projected=d_proj, w=None, **extra)
+        self._dev = dev
         if nlist is not None:
             self._centroids, self._list_off, self._ids = cent, list_off, ids
         return self
@@ -458,8 +426,17 @@ class CompactIndex:
         return self._dev
 
     # ---- the dict-like surface the retrieval functions use
+    @property
+    def _paths(self) -> list:
+        """the paths in index order: the ledger's own list, not a copy"""
+        return self._ledger.paths
+
+    @_paths.setter
+    def _paths(self, paths):
+        self._ledger = _PathLedger(paths)
+
     def __len__(self):
-        return len(self._paths)
+        return len(self._ledger)
 
     @property
     def paths(self) -> list:
@@ -505,28 +482,14 @@ class CompactIndex:
         if self._w is None or x.shape[0] == 0:
             return x.copy() if self._w is None else np.zeros((0, self.d), np.float32)
         ctx, dev = self.context, self._device()
-        d_x = ctx.buffer(x.nbytes).upload(x)
-        d_y = ctx.buffer(x.shape[0] * self.d * 4)
-        try:
+        with ctx.scratch() as tmp:
+            d_x, d_y = tmp.upload(x), tmp(x.shape[0] * self.d * 4)
             ctx.cosine_dev(d_x.ptr, x.shape[0], dev["w"].ptr, self.d, x.shape[1], None, None, d_y.ptr, self.d)
             return d_y.download((x.shape[0], self.d), np.float32)
-        finally:
-            d_x.free()
-            d_y.free()
 
     # ---- updates
-    def _serials(self) -> dict:
-        """{path: serial number}.  A row's serial is fixed when it joins and serials rise with the original index, so the original
-        index of a row is the rank of its serial among the live ones (`self._live`, ascending): a remove deletes entries and
-        renumbers nothing, which keeps the interpreter's share of an update O(b) or O(r) beside one array copy."""
-        if getattr(self, "_serial", None) is None:
-            n = len(self._paths)
-            self._serial, self._live, self._next_serial = {p: i for i, p in enumerate(self._paths)}, np.arange(n, dtype=np.int64), n
-        return self._serial
-
     def _check_new(self, source):
         """-> (paths, float32 host rows (b, input_dim), the DeviceIndex they are resident in or None); touches no device"""
-        from .index import DeviceIndex
         resident = source if isinstance(source, DeviceIndex) else None
         paths = [str(p) for p in source.keys()]
         if resident is not None:
@@ -536,13 +499,7 @@ class CompactIndex:
         mat = _f32_rows(mat, "new vectors")
         if mat.shape[1] != self.input_dim:
             raise ValueError(f"new vectors have {mat.shape[1]} dimensions, the index takes {self.input_dim}")
-        known, seen = self._serials(), set()
-        for p in paths:
-            if p in known:
-                raise ValueError(f"{p!r} is already indexed: remove it first")
-            if p in seen:
-                raise ValueError(f"{p!r} is named twice in one add")
-            seen.add(p)
+        self._ledger.check_new(paths)
         self._check_size(len(self) + len(paths))
         return paths, mat, resident
 
@@ -551,14 +508,9 @@ class CompactIndex:
 
     def _reserve_rows(self, dev: dict, name: str, row_bytes: int, used: int, need: int) -> None:
         """room for `need` rows in dev[name], growing geometrically; the first `used` rows are copied on the device"""
-        buf = dev[name]
-        if buf.nbytes >= need * row_bytes:
-            return
-        new = self.context.buffer(max(need, 2 * (buf.nbytes // row_bytes)) * row_bytes)
-        if used:
-            self.context.copy_dev(new.ptr, buf.ptr, used * row_bytes)
-        dev[name] = new
-        buf.free()
+        have = dev[name].nbytes // row_bytes
+        if have < need:
+            dev[name] = _grow_rows(self.context, dev[name], row_bytes, used, max(need, 2 * have))
 
     def reserve(self, n: int) -> None:
         """Room for n rows in the device buffers an `add` appends to (codes and norms of a flat index, the kept projected rows)."""
@@ -571,20 +523,19 @@ class CompactIndex:
         q = self.quantizer
         return [("codes", q.m), ("inv", 4)] + ([("projected", q.d * 4)] if self._keep else [])
 
-    def _encode_new(self, mat, resident, d_codes: int, d_inv: int, d_proj, d_lists, take):
+    def _encode_new(self, mat, resident, d_codes: int, d_inv: int, d_proj, d_lists, tmp):
         """The b new rows through project -> row_inv_norms_dev -> (ivf_assign_dev + residual) -> pq_encode_dev, in chunks: codes
         to d_codes, norms to d_inv, the projected rows to d_proj (or nowhere), list numbers to d_lists (an IVF index).  Raw device
-        addresses; `take(nbytes)` hands out temporaries the caller frees."""
+        addresses; the temporaries belong to the caller's scratch scope `tmp` and live until it ends."""
         ctx, dev, pq = self.context, self._device(), self.quantizer
         d, m, L, table = pq.d, pq.m, self.input_dim, pq.table()
-        d_res = take(min(mat.shape[0], _CHUNK_ROWS) * d * 4) if d_lists is not None else None
-        for r0 in range(0, mat.shape[0], _CHUNK_ROWS):
-            rn = min(_CHUNK_ROWS, mat.shape[0] - r0)
-            src = resident._db.ptr + r0 * L * 4 if resident is not None else take(rn * L * 4).upload(mat[r0:r0 + rn]).ptr
+        d_res = tmp(min(mat.shape[0], _CHUNK_ROWS) * d * 4) if d_lists is not None else None
+        for r0, rn in _chunks(mat.shape[0]):
+            src = resident._db.ptr + r0 * L * 4 if resident is not None else tmp.upload(mat[r0:r0 + rn]).ptr
             if self._w is None and d_proj is None:
                 y = src                                            # no projection: the rows themselves, where they are
             else:
-                y = d_proj + r0 * d * 4 if d_proj is not None else take(rn * d * 4).ptr
+                y = d_proj + r0 * d * 4 if d_proj is not None else tmp(rn * d * 4).ptr
                 if self._w is None:
                     ctx.copy_dev(y, src, rn * d * 4)
                 else:
@@ -604,61 +555,39 @@ class CompactIndex:
         if not paths:
             return
         dev, n, b = self._device(), len(self), len(paths)
-        temps = []
-
-        def take(nbytes):
-            temps.append(self.context.buffer(max(nbytes, 16)))
-            return temps[-1]
-
-        try:
+        with self.context.scratch() as tmp:
             for name, row_bytes in self._appended(dev):
                 self._reserve_rows(dev, name, row_bytes, n, n + b)
-            self._append(dev, mat, resident, n, take)
-        finally:
-            for t in temps:
-                t.free()
-        serial = self._serials()
-        for i, p in enumerate(paths):
-            serial[p] = self._next_serial + i
-        self._live = np.concatenate([self._live, np.arange(self._next_serial, self._next_serial + b, dtype=np.int64)])
-        self._next_serial += b
-        self._paths.extend(paths)
+            self._append(dev, mat, resident, n, tmp)
+        self._ledger.append(paths)
         self._drop_caches(dev)
 
-    def _append(self, dev, mat, resident, n, take) -> None:
+    def _append(self, dev, mat, resident, n, tmp) -> None:
         q = self.quantizer
         self._encode_new(mat, resident, dev["codes"].ptr + n * q.m, dev["inv"].ptr + n * 4,
-                         dev["projected"].ptr + n * q.d * 4 if self._keep else None, None, take)
+                         dev["projected"].ptr + n * q.d * 4 if self._keep else None, None, tmp)
 
     def remove(self, paths) -> None:
         """The named images leave, the others keep their relative order; the original index of a survivor falls by the number of
         removed rows before it.  An unknown path is a KeyError, a path named twice a ValueError, both raised before anything changes."""
-        from .index import _compact_list, _keep_positions, _removed_indices
-        paths = [paths] if isinstance(paths, str) else [str(p) for p in paths]
-        serial = self._serials()
-        idx = np.searchsorted(self._live, _removed_indices(paths, serial))       # serials -> original indices, ascending
+        idx = self._ledger.removed_indices([paths] if isinstance(paths, str) else [str(p) for p in paths])
         if idx.size == 0:
             return
         ctx, dev, n = self.context, self._device(), len(self)
-        keep, pos = _keep_positions(ctx, idx, n)
-        try:
-            self._remove_stored(ctx, dev, n, idx, keep, pos)
+        with ctx.scratch() as tmp:
+            keep, pos = _keep_positions(tmp, idx, n)
+            self._remove_stored(tmp, dev, n, idx, keep, pos)
             if self._keep:
                 ctx.compact_rows_dev(dev["projected"].ptr, n, self.quantizer.d * 4, keep.ptr, pos.ptr, dev["projected"].ptr, first=int(idx[0]))
-        finally:
-            keep.free(), pos.free()
-        self._paths = _compact_list(self._paths, idx)
-        for p in paths:
-            del serial[p]
-        self._live = np.delete(self._live, idx)
+        self._ledger.remove(idx)
         self._drop_caches(dev)
 
     def __delitem__(self, path) -> None:
         self.remove([path])
 
-    def _remove_stored(self, ctx, dev, n, idx, keep, pos) -> None:
+    def _remove_stored(self, tmp, dev, n, idx, keep, pos) -> None:
         for name, row_bytes in (("codes", self.quantizer.m), ("inv", 4)):
-            ctx.compact_rows_dev(dev[name].ptr, n, row_bytes, keep.ptr, pos.ptr, dev[name].ptr, first=int(idx[0]))
+            tmp.ctx.compact_rows_dev(dev[name].ptr, n, row_bytes, keep.ptr, pos.ptr, dev[name].ptr, first=int(idx[0]))
 
     def _drop_caches(self, dev) -> None:
         """what was derived from the arrays an update has changed"""
@@ -669,8 +598,8 @@ class CompactIndex:
         the ADC top-R re-scored exactly against the kept projected rows and ordered by (exact score descending, index ascending)."""
         return self._rank(query_vecs, k, rerank)
 
-    def _scan(self, ctx, dev, buf, d_y, d_invq, d_lut, nq, kk, d_idx, d_val):
-        """the ADC lists of nq projected queries (rows d_y, tables d_lut) into d_idx / d_val (nq, kk); `buf` takes scratch buffers"""
+    def _scan(self, ctx, dev, tmp, d_y, d_invq, d_lut, nq, kk, d_idx, d_val):
+        """the ADC lists of nq projected queries (rows d_y, tables d_lut) into d_idx / d_val (nq, kk); `tmp`: the caller's scratch scope"""
         n, pq = len(self), self.quantizer
         ctx.pq_scan_topk_dev(d_lut.ptr, nq, pq.m, pq.ksub, dev["codes"].ptr, n, d_invq.ptr, dev["inv"].ptr, kk, 0, False,
                              d_idx.ptr, d_val.ptr)
@@ -692,33 +621,24 @@ class CompactIndex:
         if nq == 0:
             return np.zeros((0, k), np.int64), np.zeros((0, k), np.float32)
         ctx, dev = self.context, self._device()
-        bufs = []
-
-        def buf(nbytes):
-            bufs.append(ctx.buffer(max(nbytes, 16)))
-            return bufs[-1]
-
-        try:
-            d_q = buf(q.nbytes).upload(q)
+        with ctx.scratch() as tmp:
+            d_q = tmp.upload(q)
             if self._w is not None:
-                d_y = buf(nq * d * 4)
+                d_y = tmp(nq * d * 4)
                 ctx.cosine_dev(d_q.ptr, nq, dev["w"].ptr, d, q.shape[1], None, None, d_y.ptr, d)
             else:
                 d_y = d_q
-            d_invq, d_lut = buf(nq * 4), buf(nq * pq.m * pq.ksub * 4)
-            d_idx, d_val = buf(nq * kk * 8), buf(nq * kk * 4)
+            d_invq, d_lut = tmp(nq * 4), tmp(nq * pq.m * pq.ksub * 4)
+            d_idx, d_val = tmp(nq * kk * 8), tmp(nq * kk * 4)
             ctx.row_inv_norms_dev(d_y.ptr, nq, d, d_invq.ptr)
             ctx.pq_lut_dev(pq.table(), d_y.ptr, nq, d_lut.ptr)
-            self._scan(ctx, dev, buf, d_y, d_invq, d_lut, nq, kk, d_idx, d_val, **scan_args)
+            self._scan(ctx, dev, tmp, d_y, d_invq, d_lut, nq, kk, d_idx, d_val, **scan_args)
             if not rerank:
                 return d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
-            d_exact = buf(nq * kk * 4)
+            d_exact = tmp(nq * kk * 4)
             ctx.rescore_rows_dev(d_y.ptr, nq, dev["projected"].ptr, n, d, d_invq.ptr, self._rescore_norms(dev).ptr, d_idx.ptr, kk,
                                  d_exact.ptr)
             idx, val = d_idx.download((nq, kk), np.int64), d_exact.download((nq, kk), np.float32)
-        finally:
-            for b in bufs:
-                b.free()
         return order_exact(idx, val, k)
 
     # ---- persistence
@@ -773,13 +693,10 @@ def _fit_coarse(ctx, rows: np.ndarray, nlist: int, rng, max_iter: int) -> np.nda
     """coarse centroids float32 (nlist, d): learn.fit_kmeans on the projected training rows"""
     import warnings
     from .learn import DeviceRows, fit_kmeans
-    dev = DeviceRows.from_host(ctx, rows)
-    try:
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", UserWarning)             # duplicate rows: fewer distinct centroids, some lists stay empty
-            return np.ascontiguousarray(fit_kmeans(dev, nlist, random_state=rng, max_iter=max_iter).cluster_centers_, dtype=np.float32)
-    finally:
-        dev.free()
+    with ctx.scratch() as tmp, warnings.catch_warnings():
+        warnings.simplefilter("ignore", UserWarning)                 # duplicate rows: fewer distinct centroids, some lists stay empty
+        dev = DeviceRows(ctx, *rows.shape, tmp.upload(rows))
+        return np.ascontiguousarray(fit_kmeans(dev, nlist, random_state=rng, max_iter=max_iter).cluster_centers_, dtype=np.float32)
 
 
 def _sort_into_lists(lists: np.ndarray, nlist: int):
@@ -854,7 +771,7 @@ class IVFCompactIndex(CompactIndex):
         if fresh:
             ctx = self.context
             for name, a in (("cent", self._centroids), ("ids", self._ids), ("list_off", self._list_off)):
-                dev[name] = ctx.buffer(max(a.nbytes, 16)).upload(a)
+                dev[name] = ctx.buffer(a.nbytes).upload(a)
         return dev
 
     @property
@@ -884,7 +801,7 @@ class IVFCompactIndex(CompactIndex):
             stored = dev["inv"].download((len(self),), np.float32)
             orig = np.empty_like(stored)
             orig[self._ids] = stored
-            dev["inv_orig"] = self.context.buffer(max(orig.nbytes, 16)).upload(orig)
+            dev["inv_orig"] = self.context.buffer(orig.nbytes).upload(orig)
         return dev["inv_orig"]
 
     # ---- updates
@@ -902,36 +819,26 @@ class IVFCompactIndex(CompactIndex):
             dev[name] = new
         self._list_off, self._ids_host = list_off, None
 
-    def _append(self, dev, mat, resident, n, take) -> None:
+    def _append(self, dev, mat, resident, n, tmp) -> None:
         """encode the new rows, sort their list numbers on the host (b entries), merge old and new storage on the device"""
-        ctx, q, nlist, b = self.context, self.quantizer, self.nlist, mat.shape[0]
-        d_codes, d_inv, d_lists = take(b * q.m), take(b * 4), take(b * 4)
+        q, nlist, b = self.quantizer, self.nlist, mat.shape[0]
+        d_codes, d_inv, d_lists = tmp(b * q.m), tmp(b * 4), tmp(b * 4)
         self._encode_new(mat, resident, d_codes.ptr, d_inv.ptr, dev["projected"].ptr + n * q.d * 4 if self._keep else None, d_lists.ptr,
-                         take)
+                         tmp)
         perm, new_off = _sort_into_lists(d_lists.download((b,), np.int32), nlist)
-        d_perm, d_new_off = take(perm.nbytes).upload(perm), take(new_off.nbytes).upload(new_off)
-        out = [ctx.buffer(max(nbytes, 16)) for nbytes in ((n + b) * q.m, (n + b) * 4, (n + b) * 4, (nlist + 1) * 8)]
-        try:
-            ctx.ivf_insert_dev(q.m, nlist, dev["codes"].ptr, dev["inv"].ptr, dev["ids"].ptr, dev["list_off"].ptr, self._list_off,
+        d_perm, d_new_off = tmp.upload(perm), tmp.upload(new_off)
+        out = [tmp(nbytes) for nbytes in ((n + b) * q.m, (n + b) * 4, (n + b) * 4, (nlist + 1) * 8)]
+        tmp.ctx.ivf_insert_dev(q.m, nlist, dev["codes"].ptr, dev["inv"].ptr, dev["ids"].ptr, dev["list_off"].ptr, self._list_off,
                                d_codes.ptr, d_inv.ptr, d_new_off.ptr, new_off, d_perm.ptr, *(o.ptr for o in out))
-        except BaseException:
-            for o in out:
-                o.free()
-            raise
-        self._swap_stored(dev, *out, self._list_off + new_off)
+        self._swap_stored(dev, *(tmp.keep(o) for o in out), self._list_off + new_off)
 
-    def _remove_stored(self, ctx, dev, n, idx, keep, pos) -> None:
+    def _remove_stored(self, tmp, dev, n, idx, keep, pos) -> None:
         q, nlist, left = self.quantizer, self.nlist, n - idx.size
-        out = [ctx.buffer(max(nbytes, 16)) for nbytes in (left * q.m, left * 4, left * 4, (nlist + 1) * 8)]
-        try:
-            ctx.ivf_remove_dev(q.m, nlist, n, dev["codes"].ptr, dev["inv"].ptr, dev["ids"].ptr, dev["list_off"].ptr, keep.ptr, pos.ptr,
+        out = [tmp(nbytes) for nbytes in (left * q.m, left * 4, left * 4, (nlist + 1) * 8)]
+        tmp.ctx.ivf_remove_dev(q.m, nlist, n, dev["codes"].ptr, dev["inv"].ptr, dev["ids"].ptr, dev["list_off"].ptr, keep.ptr, pos.ptr,
                                *(o.ptr for o in out))
-            list_off = out[3].download((nlist + 1,), np.int64)
-        except BaseException:
-            for o in out:
-                o.free()
-            raise
-        self._swap_stored(dev, *out, list_off)
+        list_off = out[3].download((nlist + 1,), np.int64)
+        self._swap_stored(dev, *(tmp.keep(o) for o in out), list_off)
 
     def _drop_caches(self, dev) -> None:
         if dev.get("inv_orig") is not None:                # the norms in original order: remade on the next re-ranking
@@ -954,9 +861,9 @@ class IVFCompactIndex(CompactIndex):
             raise ValueError(f"an IVFCompactIndex ranks at most {MAX_IVF_K} entries per query (k and rerank), got k={k}, rerank={rerank}")
         return k, rerank
 
-    def _scan(self, ctx, dev, buf, d_y, d_invq, d_lut, nq, kk, d_idx, d_val, nprobe):
+    def _scan(self, ctx, dev, tmp, d_y, d_invq, d_lut, nq, kk, d_idx, d_val, nprobe):
         pq, nlist, nprobe = self.quantizer, self.nlist, int(nprobe)
-        d_coarse, d_pidx, d_pval = buf(nq * nlist * 4), buf(nq * nprobe * 8), buf(nq * nprobe * 4)
+        d_coarse, d_pidx, d_pval = tmp(nq * nlist * 4), tmp(nq * nprobe * 8), tmp(nq * nprobe * 4)
         ctx.ivf_coarse_dev(d_y.ptr, nq, pq.d, dev["cent"].ptr, nlist, d_coarse.ptr)
         ctx.topk_dev(d_coarse.ptr, nq, nlist, nlist, nprobe, 0, False, d_pidx.ptr, d_pval.ptr)
         ctx.ivf_scan_topk_dev(d_lut.ptr, nq, pq.m, pq.ksub, d_pidx.ptr, d_pval.ptr, nprobe, dev["list_off"].ptr, self._list_off, nlist,

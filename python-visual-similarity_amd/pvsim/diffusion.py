@@ -65,35 +65,25 @@ class Diffusion:
         from .index import DeviceIndex
         if not isinstance(index, DeviceIndex):
             raise TypeError("Diffusion.build needs a pvsim.index.DeviceIndex (a dict or a compact index keeps no resident rows to rank)")
-        N, L = index._shape
+        N, L = index.shape
         gamma = _check_int("gamma", gamma, 0, GAMMA_MAX)
         block = _check_int("block", block, 1)
         if N < 2 or L < 1:
             raise ValueError(f"a graph needs at least 2 rows of at least 1 column, the index has shape {(N, L)}")
         kg = _check_int("k", k, 1, N - 1)
-        ctx, dt = index.ctx, index._hbuf.dtype
-        bufs = [ctx.buffer(N * kg * 4)] + [ctx.buffer(N * kg * 8) for _ in range(3)] + [ctx.buffer(N * 8) for _ in range(2)]
-        d_nbr, d_a, d_w, d_s, d_deg, d_r = bufs
-        try:
+        ctx, dt = index.ctx, index.dtype
+        with ctx.scratch() as tmp:
+            d_nbr, d_a, d_w, d_s, d_deg, d_r = tmp(N * kg * 4), tmp(N * kg * 8), tmp(N * kg * 8), tmp(N * kg * 8), tmp(N * 8), tmp(N * 8)
             for b0 in range(0, N, block):
                 b = min(N, b0 + block) - b0
-                lists = index._rank_dev_buffers(index._db.ptr + b0 * L * dt.itemsize, b, kg + 1)
-                try:
-                    ctx.graph_affinity_dev(lists[1].ptr, lists[2].ptr, dt == np.float64, b, kg, b0, N, gamma, d_nbr.ptr, d_a.ptr)
-                finally:
-                    for buf in lists:
-                        buf.free()
+                with ctx.scratch() as lists:
+                    _, d_idx, d_val = index._rank_dev_buffers(lists, index._db.ptr + b0 * L * dt.itemsize, b, kg + 1)
+                    ctx.graph_affinity_dev(d_idx.ptr, d_val.ptr, dt == np.float64, b, kg, b0, N, gamma, d_nbr.ptr, d_a.ptr)
             ctx.graph_mutual_dev(d_nbr.ptr, d_a.ptr, N, kg, d_w.ptr)
             ctx.graph_degrees_dev(d_w.ptr, N, kg, d_deg.ptr, d_r.ptr)
             ctx.graph_normalise_dev(d_nbr.ptr, d_w.ptr, d_r.ptr, N, kg, d_s.ptr)
             ctx.sync()
-        except BaseException:
-            d_nbr.free(), d_s.free()
-            raise
-        finally:
-            for buf in (d_a, d_w, d_deg, d_r):
-                buf.free()
-        return cls(ctx, d_nbr, d_s, N, kg, gamma, index)
+            return cls(ctx, tmp.keep(d_nbr), tmp.keep(d_s), N, kg, gamma, index)      # the graph's from here on
 
     @classmethod
     def from_arrays(cls, nbr, s, gamma: int, index=None, ctx=None) -> "Diffusion":
@@ -112,9 +102,9 @@ class Diffusion:
             raise ValueError(f"the graph has {N} rows, the index {len(index)}")
         ctx = index.ctx if index is not None else (ctx or default_context())
         nbr32 = np.where((nbr >= 0) & (nbr < N), nbr, -1).astype(np.int32)
-        d_nbr = ctx.buffer(nbr32.nbytes).upload(nbr32)
-        d_s = ctx.buffer(s.nbytes).upload(s)
-        return cls(ctx, d_nbr, d_s, N, kg, gamma, index)
+        with ctx.scratch() as tmp:
+            d_nbr, d_s = tmp.upload(nbr32), tmp.upload(s)
+            return cls(ctx, tmp.keep(d_nbr), tmp.keep(d_s), N, kg, gamma, index)
 
     # ---- the arrays
     @property
@@ -156,14 +146,11 @@ class Diffusion:
     def _solve_dev(self, d_y, C, alpha, tol, maxiter, check_every, width, d_x, d_cols):
         """pvs_diffuse_cg_dev on C columns that are on the device; d_cols holds steps | rr | yy -> (steps, rr, yy) on the host"""
         nbytes = diffuse_workspace(self.n, C)
-        d_work = self.ctx.buffer(nbytes)
-        try:
+        with self.ctx.scratch() as tmp:
             self.ctx.diffuse_cg_dev(self._d_nbr.ptr, self._d_s.ptr, self.n, self.kg, d_y, C, alpha, tol, maxiter, check_every, width,
-                                    d_work.ptr, nbytes, d_x, d_cols.ptr, d_cols.ptr + 8 * C, d_cols.ptr + 16 * C)
+                                    tmp(nbytes).ptr, nbytes, d_x, d_cols.ptr, d_cols.ptr + 8 * C, d_cols.ptr + 16 * C)
             return (d_cols.download((C,), np.int32), d_cols.download((C,), np.float64, offset=8 * C),
                     d_cols.download((C,), np.float64, offset=16 * C))
-        finally:
-            d_work.free()
 
     def _report(self, steps, rr, yy, tol):
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -184,15 +171,11 @@ class Diffusion:
         tile = self._tile(nq, column_bytes) if nq else 0
         for c0 in range(0, nq, max(tile, 1)):
             C = min(tile, nq - c0)
-            d_y = self.ctx.buffer(self.n * C * 8).upload(np.ascontiguousarray(Y[:, c0:c0 + C]))
-            d_x = self.ctx.buffer(self.n * C * 8)
-            d_cols = self.ctx.buffer(24 * C)
-            try:
+            with self.ctx.scratch() as tmp:
+                d_y, d_x, d_cols = tmp.upload(Y[:, c0:c0 + C]), tmp(self.n * C * 8), tmp(24 * C)
                 steps[c0:c0 + C], rr[c0:c0 + C], yy[c0:c0 + C] = self._solve_dev(d_y.ptr, C, alpha, tol, maxiter, check_every, width,
                                                                                d_x.ptr, d_cols)
                 F[:, c0:c0 + C] = d_x.download((self.n, C), np.float64)
-            finally:
-                d_y.free(), d_x.free(), d_cols.free()
         self._report(steps, rr, yy, tol)
         return F, steps, rr, yy
 
@@ -212,8 +195,7 @@ class Diffusion:
         self._check_snapshot()
         _check_solver(alpha, tol, maxiter, check_every, width)
         index, N = self.index, self.n
-        L = index._shape[1]
-        dt = index._hbuf.dtype
+        L, dt = index.shape[1], index.dtype
         q = np.asarray(query_vecs)
         if q.ndim != 2 or q.shape[1] != L:
             raise ValueError("query and database dimensions differ")
@@ -232,26 +214,19 @@ class Diffusion:
             return idx, val
         ctx = self.ctx
         tile = self._tile(nq, column_bytes)
-        d_q = ctx.buffer(q.nbytes).upload(q)
-        d_y, d_x = ctx.buffer(N * tile * 8), ctx.buffer(N * tile * 8)
-        d_cols, d_oi, d_ov = ctx.buffer(24 * tile), ctx.buffer(tile * k * 8), ctx.buffer(tile * k * 8)
-        try:
+        with ctx.scratch() as tmp:
+            d_q, d_y, d_x = tmp.upload(q), tmp(N * tile * 8), tmp(N * tile * 8)
+            d_cols, d_oi, d_ov = tmp(24 * tile), tmp(tile * k * 8), tmp(tile * k * 8)
             for c0 in range(0, nq, tile):
                 C = min(tile, nq - c0)
-                lists = index._rank_dev_buffers(d_q.ptr + c0 * L * dt.itemsize, C, kq)
-                try:
-                    ctx.diffuse_rhs_dev(lists[1].ptr, lists[2].ptr, dt == np.float64, C, kq, N, self.gamma, d_y.ptr)
-                finally:
-                    for b in lists:
-                        b.free()
+                with ctx.scratch() as lists:
+                    _, d_idx, d_val = index._rank_dev_buffers(lists, d_q.ptr + c0 * L * dt.itemsize, C, kq)
+                    ctx.diffuse_rhs_dev(d_idx.ptr, d_val.ptr, dt == np.float64, C, kq, N, self.gamma, d_y.ptr)
                 steps[c0:c0 + C], rr[c0:c0 + C], yy[c0:c0 + C] = self._solve_dev(d_y.ptr, C, alpha, tol, maxiter, check_every, width,
                                                                                d_x.ptr, d_cols)
                 ctx.transpose_f64_dev(d_x.ptr, N, C, d_y.ptr)               # (N, C) -> (C, N): Y is not needed any more
                 ctx.rank_f64_dev(d_y.ptr, C, N, N, k, d_oi.ptr, d_ov.ptr)
                 idx[c0:c0 + C] = d_oi.download((C, k), np.int64)
                 val[c0:c0 + C] = d_ov.download((C, k), np.float64)
-        finally:
-            for b in (d_q, d_y, d_x, d_cols, d_oi, d_ov):
-                b.free()
         self._report(steps, rr, yy, tol)
         return idx, val

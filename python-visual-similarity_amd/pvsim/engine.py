@@ -149,6 +149,35 @@ class DeviceBuffer:
             pass
 
 
+class _Scratch:
+    """The device temporaries of one `with ctx.scratch() as tmp:` block.  `tmp(nbytes)` and `tmp.upload(array)` hand out DeviceBuffers
+    that are freed when the block ends, however it ends; `tmp.keep(buf)` takes one out of the block: it is the caller's from then on."""
+
+    def __init__(self, ctx):
+        self.ctx, self._bufs = ctx, []
+
+    def __call__(self, nbytes: int) -> DeviceBuffer:
+        self._bufs.append(self.ctx.buffer(nbytes))
+        return self._bufs[-1]
+
+    def upload(self, a) -> DeviceBuffer:
+        a = np.ascontiguousarray(a)
+        buf = self(a.nbytes)
+        return buf.upload(a) if a.nbytes else buf
+
+    def keep(self, buf):
+        self._bufs = [b for b in self._bufs if b is not buf]
+        return buf
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        bufs, self._bufs = self._bufs, []
+        for b in bufs:
+            b.free()
+
+
 class Context:
     """One device + one stream.  `stream` may be a raw hipStream_t (int), e.g.
     torch.cuda.current_stream().cuda_stream, so that work interleaves with torch in order."""
@@ -683,6 +712,10 @@ class Context:
     # ------------------------------------------------------------------ vocabulary training (one device pass each)
     def buffer(self, nbytes: int) -> "DeviceBuffer":
         return DeviceBuffer(self, nbytes)
+
+    def scratch(self) -> _Scratch:
+        """`with ctx.scratch() as tmp:` -- device temporaries that are freed when the block ends (see _Scratch)"""
+        return _Scratch(self)
 
     def materialise_dev(self, d_desc, kind, D, total_desc, d_out):
         check(_ffi.lib().pvs_materialise_dev(self.handle, ptr(d_desc), kind, D, total_desc, ptr(d_out)))

@@ -31,119 +31,110 @@ def _first_rows(encoder, queries) -> np.ndarray:
     return np.vstack(rows) if rows else np.zeros((0, 0), np.float32)
 
 
-def _vectors_and_paths(encoding_map):
-    """-> ((N, L) matrix, paths, resident index or None).  A pvsim.index.DeviceIndex already holds the matrix (and a normalised
-    copy on the GPU); a plain dict is stacked the way the reference does it (eval.py:28)."""
-    from .compact import CompactIndex
+def _first_row(encoder, image) -> np.ndarray:
+    v = encoder.encode(image)
+    return (v.reshape(1, -1) if v.ndim == 1 else v)[:1]
+
+
+def _clamped(rank, n: int, query_vecs: np.ndarray, k: int | None, dtype=np.float32, **kw):
+    """rank(query_vecs, k') with k' = min(k, N) (k=None: all N), or the empty result of scores `dtype`: once, for every kind"""
+    kk = n if k is None else max(0, min(int(k), n))
+    if query_vecs.shape[0] == 0 or kk == 0:
+        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), dtype)
+    return rank(query_vecs, kk, **kw)
+
+
+def _check_features(query_vecs: np.ndarray, L: int):
+    if query_vecs.shape[-1] <= 1 or L <= 1:
+        raise ValueError(f"Cosine similarity requires at least 2 features. Got {query_vecs.shape[-1]} features "
+                         f"for x and {L} features for y.")
+
+
+def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None):
+    """-> (indices (nq, k') int64, scores (nq, k')) with k' = min(k, N) (k=None: all N), against a host matrix."""
+    def cosine(q, kk):
+        _check_features(q, all_vectors.shape[-1])
+        c = ctx or default_context()
+        # the reference's dtype rule (pyvisim/_utils.py:312-330 -> sklearn): float32 scores iff BOTH operands are float32;
+        # anything else (Fisher encodings are float64) is scored and ranked in float64
+        if q.dtype == np.float32 and all_vectors.dtype == np.float32:
+            return c.cosine_topk(np.ascontiguousarray(q), np.ascontiguousarray(all_vectors), kk)
+        return c.cosine_topk_f64(q, all_vectors, kk)
+    return _clamped(cosine, all_vectors.shape[0], query_vecs, k)
+
+
+class _Plan:
+    """A dataset resolved once for ranking: `n` rows, `paths` in index order (the index's own list, not a copy), `matrix` (the
+    stacked host rows of a dict, None for an index), `index_of(path)` and `rank(query_vecs, k)` -> (idx (nq, k'), val (nq, k'))."""
+
+    def __init__(self, n, paths, rank, matrix=None, index_of=None):
+        self.n, self.paths, self.rank, self.matrix, self._index_of = n, paths, rank, matrix, index_of
+
+    def index_of(self, path) -> int:
+        if self._index_of is None:                                  # a dict: its positions are made when first asked for
+            self._index_of = {p: i for i, p in enumerate(self.paths)}.__getitem__
+        return self._index_of(path)
+
+
+def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None) -> _Plan:
+    """What `dataset` is (a dict, a DeviceIndex, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
+    refusal is raised here, before anything is encoded), and how it ranks.  A DeviceIndex is never asked for its host rows."""
+    from .compact import CompactIndex, IVFCompactIndex
     from .index import DeviceIndex
-    if isinstance(encoding_map, DeviceIndex):
-        return encoding_map.matrix, list(encoding_map.keys()), encoding_map
-    if isinstance(encoding_map, CompactIndex):             # codes only: there is no host matrix, N comes from len()
-        return None, encoding_map.paths, encoding_map
-    return np.array(list(encoding_map.values())), list(encoding_map.keys()), None
-
-
-def _check_nprobe(index, nprobe):
-    """nprobe= goes with an IVFCompactIndex, and only with one"""
-    from .compact import IVFCompactIndex
-    if isinstance(index, IVFCompactIndex):
+    dense, compact = isinstance(dataset, DeviceIndex), isinstance(dataset, CompactIndex)
+    if diffuse is not None:                       # the graph's own index only, and none of the other re-ranking options
+        from .diffusion import Diffusion
+        if not isinstance(diffuse, Diffusion):
+            raise TypeError("diffuse must be a pvsim.Diffusion")
+        if not dense:
+            raise TypeError("diffuse= needs the pvsim.index.DeviceIndex the graph was built on, not a dict or a compact index")
+        if diffuse.index is not dataset:
+            raise ValueError("diffuse= needs the DeviceIndex the graph was built on: this graph belongs to another index")
+        if expand is not None or rerank or nprobe is not None:
+            raise ValueError("diffuse= excludes expand=, rerank= and nprobe=")
+    if expand is not None and compact:
+        raise ValueError("query expansion needs the full-precision rows: use a dict or a DeviceIndex, not a CompactIndex")
+    if rerank and not compact:
+        raise ValueError("rerank= applies to a CompactIndex only")
+    if isinstance(dataset, IVFCompactIndex):
         if nprobe is None:
             raise ValueError("an IVFCompactIndex scans the nprobe best lists of a query: pass nprobe=")
     elif nprobe is not None:
         raise ValueError("nprobe= applies to an IVFCompactIndex only")
 
+    if compact:                                   # ADC ranking, optionally re-ranked exactly; rerank < k raises in index.rank
+        def rank(q, k):
+            if k is None:
+                raise ValueError("a CompactIndex ranks a finite list: pass k (k=None asks for the complete ranking, which needs the "
+                                 "full-precision rows -- use a dict or a DeviceIndex for that)")
+            args = () if nprobe is None else (nprobe,)
+            return _clamped(lambda q, kk: dataset.rank(q, kk, *args, rerank=rerank), n, q, k)
+    elif dense:
+        def plain(q, kk):
+            _check_features(q, dataset.shape[1])
+            return dataset.rank(q, kk)
+        if diffuse is not None:
+            rank = lambda q, k: _clamped(diffuse.rank, n, q, k, np.float64)
+        elif expand is not None:
+            rank = lambda q, k, members=None: _clamped(dataset.rank_expanded, n, q, k, qe=expand, members=members)
+        else:
+            rank = lambda q, k: _clamped(plain, n, q, k)
+    else:
+        paths, matrix = list(dataset.keys()), np.array(list(dataset.values()))        # stacked as the reference does (eval.py:28)
 
-def _rank_compact(query_vecs: np.ndarray, index, k: int | None, rerank: int = 0, nprobe=None):
-    """_rank against a pvsim.compact.CompactIndex (ADC ranking, optionally re-ranked exactly on the ADC top-`rerank`); an
-    IVFCompactIndex takes `nprobe` as well, and its lists may end in unfilled slots (index -1)."""
-    _check_nprobe(index, nprobe)
-    if k is None:
-        raise ValueError("a CompactIndex ranks a finite list: pass k (k=None asks for the complete ranking, which needs the "
-                         "full-precision rows -- use a dict or a DeviceIndex for that)")
-    kk = max(0, min(int(k), len(index)))
-    if query_vecs.shape[0] == 0 or kk == 0:
-        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float32)
-    if nprobe is not None:
-        return index.rank(query_vecs, kk, nprobe, rerank=rerank)
-    return index.rank(query_vecs, kk, rerank=rerank)             # rerank < k raises there, as it does for a direct call
-
-
-def _rank_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths, k: int, ctx, resident, expand, members=None):
-    """_rank with query expansion (pvsim.expand): on the resident index, or on a DeviceIndex that holds the dict for this call."""
-    from .index import DeviceIndex
-    if resident is not None:
-        return resident.rank_expanded(query_vecs, k, expand, members=members)
-    temp = DeviceIndex(dict(zip(paths, all_vectors)), ctx or default_context())
-    try:
-        return temp.rank_expanded(query_vecs, k, expand, members=members)
-    finally:
-        temp.close()
-
-
-def _no_compact_expansion(all_vectors, expand):
-    if expand is not None and all_vectors is None:
-        raise ValueError("query expansion needs the full-precision rows: use a dict or a DeviceIndex, not a CompactIndex")
-
-
-def _rank_diffused(query_vecs: np.ndarray, index, k: int | None, diffuse, expand=None, rerank: int = 0, nprobe=None):
-    """_rank through a pvsim.Diffusion graph: the graph's own index only, and none of the other re-ranking options"""
-    from .diffusion import Diffusion
-    from .index import DeviceIndex
-    if not isinstance(diffuse, Diffusion):
-        raise TypeError("diffuse must be a pvsim.Diffusion")
-    if not isinstance(index, DeviceIndex):
-        raise TypeError("diffuse= needs the pvsim.index.DeviceIndex the graph was built on, not a dict or a compact index")
-    if diffuse.index is not index:
-        raise ValueError("diffuse= needs the DeviceIndex the graph was built on: this graph belongs to another index")
-    if expand is not None or rerank or nprobe is not None:
-        raise ValueError("diffuse= excludes expand=, rerank= and nprobe=")
-    n = len(index)
-    kk = n if k is None else max(0, min(int(k), n))
-    if query_vecs.shape[0] == 0 or kk == 0:
-        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float64)
-    return diffuse.rank(query_vecs, kk)
-
-
-def _rank(query_vecs: np.ndarray, all_vectors: np.ndarray, k: int | None, ctx=None, resident=None, rerank: int = 0, nprobe=None):
-    """-> (indices (nq, k') int64, scores (nq, k')) with k' = min(k, N) (k=None: all N)."""
-    if all_vectors is None:                                     # a CompactIndex: no host matrix
-        return _rank_compact(query_vecs, resident, k, rerank, nprobe)
-    if rerank:
-        raise ValueError("rerank= applies to a CompactIndex only")
-    _check_nprobe(resident, nprobe)
-    n = all_vectors.shape[0]
-    kk = n if k is None else max(0, min(int(k), n))
-    if query_vecs.shape[0] == 0 or kk == 0:
-        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float32)
-    if query_vecs.shape[-1] <= 1 or all_vectors.shape[-1] <= 1:
-        raise ValueError(f"Cosine similarity requires at least 2 features. Got {query_vecs.shape[-1]} features "
-                         f"for x and {all_vectors.shape[-1]} features for y.")
-    if resident is not None:
-        return resident.rank(query_vecs, kk)
-    ctx = ctx or default_context()
-    # the reference's dtype rule (pyvisim/_utils.py:312-330 -> sklearn): float32 scores iff BOTH operands are float32;
-    # anything else (Fisher encodings are float64) is scored and ranked in float64
-    if query_vecs.dtype == np.float32 and all_vectors.dtype == np.float32:
-        return ctx.cosine_topk(np.ascontiguousarray(query_vecs), np.ascontiguousarray(all_vectors), kk)
-    return ctx.cosine_topk_f64(query_vecs, all_vectors, kk)
-
-
-def _rank_maybe_expanded(query_vecs: np.ndarray, all_vectors: np.ndarray, paths, k: int | None, ctx, resident, expand, rerank: int = 0,
-                         nprobe=None):
-    """_rank, or with `expand` (a pvsim.expand.QueryExpansion) the ranking of the expanded queries: same k' and same empty results"""
-    if expand is None:
-        if not rerank and nprobe is None:
-            return _rank(query_vecs, all_vectors, k, ctx, resident)
-        return _rank(query_vecs, all_vectors, k, ctx, resident, rerank, nprobe)
-    if rerank:
-        raise ValueError("rerank= applies to a CompactIndex only")
-    _check_nprobe(resident, nprobe)
-    _no_compact_expansion(all_vectors, expand)
-    n = all_vectors.shape[0]
-    kk = n if k is None else max(0, min(int(k), n))
-    if query_vecs.shape[0] == 0 or kk == 0:
-        return np.zeros((query_vecs.shape[0], 0), np.int64), np.zeros((query_vecs.shape[0], 0), np.float32)
-    return _rank_expanded(query_vecs, all_vectors, paths, kk, ctx, resident, expand)
+        def expanded(q, kk, members=None):                          # on a DeviceIndex that holds the dict for this call
+            temp = DeviceIndex(dict(zip(paths, matrix)), ctx or default_context())
+            try:
+                return temp.rank_expanded(q, kk, expand, members=members)
+            finally:
+                temp.close()
+        if expand is not None:
+            rank = lambda q, k, members=None: _clamped(expanded, matrix.shape[0], q, k, members=members)
+        else:
+            rank = lambda q, k: _rank(q, matrix, k, ctx)            # the module's _rank at the time of the call: tests replace it
+        return _Plan(matrix.shape[0], paths, rank, matrix)
+    n = len(dataset)
+    return _Plan(n, dataset._ledger.paths, rank, index_of=dataset._ledger.index_of)
 
 
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
@@ -154,23 +145,9 @@ def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.nda
     only, and required there): the inverted lists scanned; the list is shorter than k when they hold fewer rows.  `diffuse`: a
     pvsim.Diffusion graph built on `dataset` (a DeviceIndex); the list is then the diffusion ranking and its float64 scores, and
     `rerank`, `expand` and `nprobe` are excluded."""
-    if diffuse is not None:
-        _rank_diffused(np.zeros((0, 0)), dataset, 0, diffuse, expand, rerank, nprobe)          # refuse before anything is encoded
-    all_vectors, all_paths, resident = _vectors_and_paths(dataset)
-    _no_compact_expansion(all_vectors, expand)
-    query_vector = encoder.encode(uploaded_image)
-    if query_vector.ndim == 1:
-        query_vector = query_vector.reshape(1, -1)
-    if diffuse is not None:
-        idx, val = _rank_diffused(query_vector[:1], dataset, k, diffuse)
-    elif all_vectors is None:                                     # a CompactIndex: the only index that can re-rank
-        idx, val = _rank_compact(query_vector[:1], resident, k, rerank, nprobe)
-    else:
-        if rerank:
-            raise ValueError("rerank= applies to a CompactIndex only")
-        _check_nprobe(resident, nprobe)
-        idx, val = _rank_maybe_expanded(query_vector[:1], all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand)
-    return [(all_paths[i], s) for i, s in zip(idx[0], val[0]) if i >= 0]      # unfilled slots of an IVF list are dropped
+    plan = _plan(dataset, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None))
+    idx, val = plan.rank(_first_row(encoder, uploaded_image), k)
+    return [(plan.paths[i], s) for i, s in zip(idx[0], val[0]) if i >= 0]     # unfilled slots of an IVF list are dropped
 
 
 def expand_verified(uploaded_image: np.ndarray, ranked, index, encoder, k: int = 5, qe=None,
@@ -188,21 +165,15 @@ def expand_verified(uploaded_image: np.ndarray, ranked, index, encoder, k: int =
         raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers!r}")
     if isinstance(k, bool) or int(k) != k or k < 0:
         raise ValueError(f"k must be a non-negative integer, got {k!r}")
-    all_vectors, all_paths, resident = _vectors_and_paths(index)
-    _no_compact_expansion(all_vectors, qe)
+    plan = _plan(index, expand=qe, ctx=getattr(encoder, "context", None))
     ranked = list(ranked)
     verified = [path for path, _, inliers in ranked if inliers >= min_inliers][:qe.n]
-    kk = min(int(k), len(all_paths))
-    if not verified or kk == 0:
+    if not verified or min(int(k), plan.n) == 0:
         return [(path, sim) for path, sim, _ in ranked[:k]]
-    pos = resident._pos if resident is not None else {p: i for i, p in enumerate(all_paths)}
-    members = np.full((1, min(qe.n, len(all_paths))), -1, np.int64)
-    members[0, :len(verified)] = [pos[p] for p in verified]
-    query_vector = encoder.encode(uploaded_image)
-    if query_vector.ndim == 1:
-        query_vector = query_vector.reshape(1, -1)
-    idx, val = _rank_expanded(query_vector[:1], all_vectors, all_paths, kk, getattr(encoder, "context", None), resident, qe, members)
-    return [(all_paths[i], s) for i, s in zip(idx[0], val[0])]
+    members = np.full((1, min(qe.n, plan.n)), -1, np.int64)
+    members[0, :len(verified)] = [plan.index_of(p) for p in verified]
+    idx, val = plan.rank(_first_row(encoder, uploaded_image), k, members=members)
+    return [(plan.paths[i], s) for i, s in zip(idx[0], val[0])]
 
 
 def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: int | None = None,
@@ -226,22 +197,20 @@ def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: i
     return (front + back)[:k]
 
 
+def _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse):
+    """-> (ranked indices (nq, k'), -1 in the unfilled slots at the end of an IVF list; the label of every database entry)"""
+    plan = _plan(encoding_map, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None))
+    idx, _ = plan.rank(_first_rows(encoder, images), k)
+    return idx, [path_labels_dict[p] for p in plan.paths]
+
+
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
               path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None, diffuse=None) -> float:
     """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
     there) and `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) as in retrieve_top_k_similar."""
-    if diffuse is not None:
-        _rank_diffused(np.zeros((0, 0)), encoding_map, 0, diffuse, expand, rerank, nprobe)     # refuse before anything is encoded
-    all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
-    _no_compact_expansion(all_vectors, expand)
     labels = list(image_labels)
-    q = _first_rows(encoder, images)
-    if diffuse is not None:
-        idx, _ = _rank_diffused(q, encoding_map, k, diffuse)
-    else:
-        idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
-    db_labels = [path_labels_dict[p] for p in all_paths]
+    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse)
     aps = []
     for row, true_label in zip(idx, labels):
         relevant_count, precision_sum = 0, 0.0
@@ -258,17 +227,8 @@ def top_k_accuracy(images: Iterable[np.ndarray], image_labels: Iterable[int], en
     """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
     there) and `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) as in retrieve_top_k_similar."""
-    if diffuse is not None:
-        _rank_diffused(np.zeros((0, 0)), encoding_map, 0, diffuse, expand, rerank, nprobe)     # refuse before anything is encoded
-    all_vectors, all_paths, resident = _vectors_and_paths(encoding_map)
-    _no_compact_expansion(all_vectors, expand)
     images = list(images)
     labels = list(image_labels)
-    q = _first_rows(encoder, images)
-    if diffuse is not None:
-        idx, _ = _rank_diffused(q, encoding_map, k, diffuse)
-    else:
-        idx, _ = _rank_maybe_expanded(q, all_vectors, all_paths, k, getattr(encoder, "context", None), resident, expand, rerank, nprobe)
-    db_labels = [path_labels_dict[p] for p in all_paths]
+    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse)
     correct = sum(1 for row, true_label in zip(idx, labels) if any(i >= 0 and db_labels[i] == true_label for i in row))
     return float(correct / len(images))

@@ -58,19 +58,22 @@ def _removed_indices(paths, pos: dict) -> np.ndarray:
     return np.sort(np.array([pos[p] for p in paths], dtype=np.int64))
 
 
-def _keep_positions(ctx, idx: np.ndarray, n: int):
-    """ascending removed indices -> (keep mask uint8 (n,), positions int64 (n + 1,)) as device buffers: idx.size indices go up"""
-    d_idx = ctx.buffer(idx.nbytes).upload(idx)
-    keep, pos = ctx.buffer(max(n, 16)), ctx.buffer((n + 1) * 8)
-    try:
-        ctx.keep_mask_dev(d_idx.ptr, idx.size, n, keep.ptr)
-        ctx.keep_positions_dev(keep.ptr, n, pos.ptr)
-    except BaseException:
-        keep.free(), pos.free()
-        raise
-    finally:
-        d_idx.free()
+def _keep_positions(tmp, idx: np.ndarray, n: int):
+    """ascending removed indices -> (keep mask uint8 (n,), positions int64 (n + 1,)) as device buffers of the scratch scope `tmp`
+    (Context.scratch): idx.size indices go up"""
+    d_idx, keep, pos = tmp.upload(idx), tmp(n), tmp((n + 1) * 8)
+    tmp.ctx.keep_mask_dev(d_idx.ptr, idx.size, n, keep.ptr)
+    tmp.ctx.keep_positions_dev(keep.ptr, n, pos.ptr)
     return keep, pos
+
+
+def _grow_rows(ctx, buf, row_bytes: int, used: int, need: int):
+    """-> a device buffer of `need` rows that holds the first `used` rows of `buf` (copied on the device); `buf` is freed"""
+    new = ctx.buffer(need * row_bytes)
+    if used * row_bytes:
+        ctx.copy_dev(new.ptr, buf.ptr, used * row_bytes)
+    buf.free()
+    return new
 
 
 def _compact_host_rows(buf: np.ndarray, n: int, idx: np.ndarray) -> None:
@@ -94,6 +97,57 @@ def _compact_list(items: list, idx: np.ndarray) -> list:
     return out
 
 
+class _PathLedger:
+    """Which path stands at which position of a mutable index, across adds and removes.
+
+    A path gets a serial number when it joins; serials rise with the position, so the position of a path is the rank of its serial
+    among the live ones (`_live`, ascending int64).  A remove deletes entries and renumbers nothing: the interpreter's share of an
+    update is O(b) for an add and O(r) for a remove, beside one array copy and the list slices.  `paths` is the list in index order."""
+
+    def __init__(self, paths=()):
+        self.paths = list(paths)
+        self._next = len(self.paths)
+        self._serial = {p: i for i, p in enumerate(self.paths)}
+        self._live = np.arange(self._next, dtype=np.int64)
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __contains__(self, path):
+        return path in self._serial
+
+    def index_of(self, path) -> int:
+        return int(np.searchsorted(self._live, self._serial[path]))
+
+    def check_new(self, paths) -> None:
+        """ValueError for a path that is already indexed or named twice in `paths`; nothing changes"""
+        seen = set()
+        for p in paths:
+            if p in self._serial:
+                raise ValueError(f"{p!r} is already indexed: remove it first")
+            if p in seen:
+                raise ValueError(f"{p!r} is named twice in one add")
+            seen.add(p)
+
+    def removed_indices(self, paths) -> np.ndarray:
+        """paths to remove -> their positions, ascending int64 (KeyError / ValueError as _removed_indices); nothing changes"""
+        return np.searchsorted(self._live, _removed_indices(paths, self._serial))
+
+    def append(self, paths) -> None:
+        for i, p in enumerate(paths, self._next):
+            self._serial[p] = i
+        self._live = np.concatenate([self._live, np.arange(self._next, self._next + len(paths), dtype=np.int64)])
+        self._next += len(paths)
+        self.paths.extend(paths)
+
+    def remove(self, idx: np.ndarray) -> None:
+        """the entries at positions idx (ascending, as removed_indices gives them) leave"""
+        for i in idx.tolist():
+            del self._serial[self.paths[i]]
+        self.paths = _compact_list(self.paths, idx)
+        self._live = np.delete(self._live, idx)
+
+
 class DeviceIndex(Mapping):
     """An encoding map {image_path: vector} whose vectors ALSO live on the GPU, uploaded and normalised once.
 
@@ -114,13 +168,13 @@ class DeviceIndex(Mapping):
     def __init__(self, encoding_map, ctx=None):
         from .engine import default_context
         self.ctx = ctx or default_context()
-        self._paths = list(encoding_map.keys())
+        self._paths = encoding_map.keys()
         mat = np.array(list(encoding_map.values()))                      # as the reference builds it (eval.py:28)
         if mat.ndim != 2:
             raise ValueError("DeviceIndex needs one vector of the same length per entry")
         self._hbuf = np.ascontiguousarray(mat, dtype=np.float32 if mat.dtype == np.float32 else np.float64)
         n, L = self._hbuf.shape
-        self._db = self.ctx.buffer(max(self._hbuf.nbytes, 16))
+        self._db = self.ctx.buffer(self._hbuf.nbytes)
         if n and L:
             self._db.upload(self._hbuf)
         self._finish()
@@ -130,15 +184,29 @@ class DeviceIndex(Mapping):
         """An index over rows that are already on the device (`d_rows`, a DeviceBuffer the index takes over): downloads the host copy
         the Mapping serves and computes the norms with the kernel every index uses."""
         self = cls.__new__(cls)
-        self.ctx, self._paths, self._db = ctx, list(paths), d_rows
+        self.ctx, self._paths, self._db = ctx, paths, d_rows
         self._hbuf = d_rows.download((n, L), dtype) if n and L else np.zeros((n, L), dtype)
         self._finish()
         return self
 
     @property
-    def _shape(self):
-        """(N, L) without touching the host mirror"""
-        return len(self._paths), self._hbuf.shape[1]
+    def _paths(self) -> list:
+        """the paths in index order: the ledger's own list, not a copy"""
+        return self._ledger.paths
+
+    @_paths.setter
+    def _paths(self, paths):
+        self._ledger = _PathLedger(paths)
+
+    @property
+    def shape(self):
+        """(N, L), read without touching the host mirror"""
+        return len(self._ledger), self._hbuf.shape[1]
+
+    @property
+    def dtype(self):
+        """float32 or float64: the dtype of the rows, of the norms and of a ranking's scores"""
+        return self._hbuf.dtype
 
     @property
     def _host(self) -> np.ndarray:
@@ -165,27 +233,27 @@ class DeviceIndex(Mapping):
             self._hbuf = grown
 
     def _finish(self):
-        n, L = self._shape
+        n, L = self.shape
         self._pending, self._mirror_rows, self._cap = [], n, n      # host-mirror notes, rows the mirror holds, rows the device buffers hold
-        self._pos = {p: i for i, p in enumerate(self._paths)}
         self.modifications = 0                                      # adds and removes since construction
-        self._inv = self.ctx.buffer(max(n, 1) * self._hbuf.itemsize)
+        self._inv = self.ctx.buffer(n * self._hbuf.itemsize)
         self._inv_host = None
         if n and L:
-            if self._hbuf.dtype == np.float32:
-                self.ctx.row_inv_norms_dev(self._db.ptr, n, L, self._inv.ptr)
-            else:
-                self.ctx.row_inv_norms_f64_dev(self._db.ptr, n, L, self._inv.ptr)
+            self._row_inv_norms(self._db.ptr, n, self._inv.ptr)
+
+    def _row_inv_norms(self, d_rows: int, rows: int, d_inv: int) -> None:
+        """1 / ||row|| of device rows of the index's dtype and length, by the kernel every ranking uses"""
+        (self.ctx.row_inv_norms_dev if self.dtype == np.float32 else self.ctx.row_inv_norms_f64_dev)(d_rows, rows, self.shape[1], d_inv)
 
     # ---- Mapping: the dict's view of the same rows
     def __getitem__(self, path):
-        return self._host[self._pos[path]]
+        return self._host[self._ledger.index_of(path)]
 
     def __iter__(self):
         return iter(self._paths)
 
     def __len__(self):
-        return len(self._paths)
+        return len(self._ledger)
 
     @property
     def matrix(self) -> np.ndarray:
@@ -196,7 +264,7 @@ class DeviceIndex(Mapping):
     def inv_norms(self) -> np.ndarray:
         """(N,) host copy of the device's 1 / ||row||, in the index's dtype (downloaded once)."""
         if self._inv_host is None:
-            n, L = self._shape
+            n, L = self.shape
             self._inv_host = self._inv.download((n,), self._hbuf.dtype) if n and L else np.zeros(n, self._hbuf.dtype)
         return self._inv_host
 
@@ -209,17 +277,12 @@ class DeviceIndex(Mapping):
     def reserve(self, n: int) -> None:
         """Room for n rows in the device row buffer and the norms, and in the host mirror (no-op when they already hold that many)."""
         n = int(n)
-        used, L = self._shape
+        used, L = self.shape
         if n <= self._cap:
             return
         isz = self._hbuf.dtype.itemsize
-        for name, row_bytes in (("_db", L * isz), ("_inv", isz)):
-            old = getattr(self, name)
-            new = self.ctx.buffer(max(n * row_bytes, 16))
-            if used and row_bytes:
-                self.ctx.copy_dev(new.ptr, old.ptr, used * row_bytes)
-            setattr(self, name, new)
-            old.free()
+        self._db = _grow_rows(self.ctx, self._db, L * isz, used, n)
+        self._inv = _grow_rows(self.ctx, self._inv, isz, used, n)
         self._cap = n
         if not self._pending:
             self._grow_mirror(used, n)
@@ -231,10 +294,8 @@ class DeviceIndex(Mapping):
         paths = list(encoding_map.keys())
         if not paths:
             return
-        clash = [p for p in paths if p in self._pos]
-        if clash:
-            raise ValueError(f"{clash[0]!r} is already indexed ({len(clash)} such path(s)): remove it first")
-        n, L = self._shape
+        self._ledger.check_new(paths)
+        n, L = self.shape
         dt = self._hbuf.dtype
         new = np.array(list(encoding_map.values()))
         if new.ndim != 2 or new.shape[1] != L:
@@ -254,99 +315,71 @@ class DeviceIndex(Mapping):
         if L:
             isz = dt.itemsize
             self._db.upload(new, offset=n * L * isz)
-            (self.ctx.row_inv_norms_dev if dt == np.float32 else self.ctx.row_inv_norms_f64_dev)(
-                self._db.ptr + n * L * isz, b, L, self._inv.ptr + n * isz)
-        for i, p in enumerate(paths):
-            self._pos[p] = n + i
-        self._paths.extend(paths)
+            self._row_inv_norms(self._db.ptr + n * L * isz, b, self._inv.ptr + n * isz)
+        self._ledger.append(paths)
         self._inv_host = None
         self.modifications += 1
 
     def remove(self, paths) -> None:
         """The named entries leave; the others keep their order, as `del d[k]` on the dict does.  An unknown path is a KeyError, a
         path named twice a ValueError, both raised before anything changes.  Rows and norms are compacted in place on the device."""
-        idx = _removed_indices(paths, self._pos)
+        idx = self._ledger.removed_indices(paths)
         if idx.size == 0:
             return
-        n, L = self._shape
+        n, L = self.shape
         isz = self._hbuf.dtype.itemsize
         if L:
-            keep, pos = _keep_positions(self.ctx, idx, n)
-            try:
+            with self.ctx.scratch() as tmp:
+                keep, pos = _keep_positions(tmp, idx, n)
                 self.ctx.compact_rows_dev(self._db.ptr, n, L * isz, keep.ptr, pos.ptr, self._db.ptr, first=int(idx[0]))
                 self.ctx.compact_rows_dev(self._inv.ptr, n, isz, keep.ptr, pos.ptr, self._inv.ptr, first=int(idx[0]))
-            finally:
-                keep.free(), pos.free()
         self._pending.append(("remove", idx))
-        self._paths = _compact_list(self._paths, idx)
-        self._pos = {p: i for i, p in enumerate(self._paths)}
+        self._ledger.remove(idx)
         self._inv_host = None
         self.modifications += 1
 
     def __delitem__(self, path) -> None:
         self.remove([path])
 
-    def _rank_dev_buffers(self, d_q: int, nq: int, k: int):
+    def _rank_dev_buffers(self, tmp, d_q: int, nq: int, k: int):
         """the ranking behind `_rank_dev` with the lists left on the device -> (1 / ||q|| (nq,), idx int64 (nq, k), val (nq, k)), three
-        DeviceBuffers the caller frees"""
-        n, L = self._shape
-        dt = self._hbuf.dtype
-        isz = dt.itemsize
-        d_invq = self.ctx.buffer(max(nq, 1) * isz)
-        d_idx = self.ctx.buffer(nq * k * 8)
-        d_val = self.ctx.buffer(nq * k * isz)
-        try:
-            if dt == np.float32:
-                self.ctx.row_inv_norms_dev(d_q, nq, L, d_invq.ptr)
-                if nq >= 512:     # as the host entry point: the filtered retrieval gives the same lists faster, and declines what does not qualify
-                    self.ctx.cosine_topk_filtered_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
-                else:
-                    self.ctx.cosine_topk_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), 0, False, d_idx.ptr, d_val.ptr)
-            else:
-                self.ctx.row_inv_norms_f64_dev(d_q, nq, L, d_invq.ptr)
-                self.ctx.cosine_topk_f64_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
-        except BaseException:
-            for b in (d_invq, d_idx, d_val):
-                b.free()
-            raise
+        DeviceBuffers of the caller's scratch scope `tmp`"""
+        n, L = self.shape
+        isz = self.dtype.itemsize
+        d_invq, d_idx, d_val = tmp(nq * isz), tmp(nq * k * 8), tmp(nq * k * isz)
+        self._row_inv_norms(d_q, nq, d_invq.ptr)
+        if self.dtype != np.float32:
+            self.ctx.cosine_topk_f64_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
+        elif nq >= 512:           # as the host entry point: the filtered retrieval gives the same lists faster, and declines what does not qualify
+            self.ctx.cosine_topk_filtered_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), d_idx.ptr, d_val.ptr)
+        else:
+            self.ctx.cosine_topk_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), 0, False, d_idx.ptr, d_val.ptr)
         return d_invq, d_idx, d_val
 
     def _rank_dev(self, d_q: int, nq: int, k: int, want_inv: bool = False):
         """`rank` of nq rows of the index's dtype that are on the device (raw pointer) -> (idx, val[, 1 / ||q|| (nq,)])."""
-        dt = self._hbuf.dtype
-        d_invq, d_idx, d_val = self._rank_dev_buffers(d_q, nq, k)
-        try:
+        dt = self.dtype
+        with self.ctx.scratch() as tmp:
+            d_invq, d_idx, d_val = self._rank_dev_buffers(tmp, d_q, nq, k)
             out = d_idx.download((nq, k), np.int64), d_val.download((nq, k), dt)
             return out + (d_invq.download((nq,), dt),) if want_inv else out
-        finally:
-            for b in (d_invq, d_idx, d_val):
-                b.free()
 
     def _inv_norms_dev(self, d_q: int, nq: int) -> np.ndarray:
         """1 / ||row|| of nq device rows of the index's dtype, by the kernel the rankings use -> host (nq,)"""
-        dt = self._hbuf.dtype
-        d_inv = self.ctx.buffer(max(nq, 1) * dt.itemsize)
-        try:
-            (self.ctx.row_inv_norms_dev if dt == np.float32 else self.ctx.row_inv_norms_f64_dev)(d_q, nq, self._shape[1], d_inv.ptr)
-            return d_inv.download((nq,), dt)
-        finally:
-            d_inv.free()
+        with self.ctx.scratch() as tmp:
+            d_inv = tmp(nq * self.dtype.itemsize)
+            self._row_inv_norms(d_q, nq, d_inv.ptr)
+            return d_inv.download((nq,), self.dtype)
 
     def rank(self, query_vecs: np.ndarray, k: int):
         """-> (idx (nq, k) int64, val (nq, k)) of the queries against the resident database; 1 <= k <= N."""
         q = np.asarray(query_vecs)
-        n, L = self._shape
-        if q.ndim != 2 or q.shape[1] != L:
+        if q.ndim != 2 or q.shape[1] != self.shape[1]:
             raise ValueError("query and database dimensions differ")
-        f32 = self._hbuf.dtype == np.float32 and q.dtype == np.float32
-        if not f32 and self._hbuf.dtype == np.float32:                   # mixed dtypes: float64 scores from the host copies
+        if self.dtype == np.float32 and q.dtype != np.float32:           # mixed dtypes: float64 scores from the host copies
             return self.ctx.cosine_topk_f64(q, self._host, int(k))
-        q = np.ascontiguousarray(q, dtype=self._hbuf.dtype)
-        d_q = self.ctx.buffer(max(q.nbytes, 16)).upload(q)
-        try:
-            return self._rank_dev(d_q.ptr, q.shape[0], int(k))
-        finally:
-            d_q.free()
+        with self.ctx.scratch() as tmp:
+            return self._rank_dev(tmp.upload(np.ascontiguousarray(q, dtype=self.dtype)).ptr, q.shape[0], int(k))
 
     # ---- query expansion and database-side augmentation (pvsim/expand.py, DESIGN.md section 13)
     def _list_weights(self, idx, val, scheme, alpha):
@@ -360,17 +393,11 @@ class DeviceIndex(Mapping):
     def _combine(self, d_self, w_self, idx, w, d_out):
         """pvs_combine_rows_dev of the resident rows: lists and weights go up, the rows stay where they are"""
         n, r = idx.shape
-        N, L = self._shape
-        bufs = [self.ctx.buffer(max(a.nbytes, 16)) for a in (w_self, idx, w)]
-        try:
-            for b, a in zip(bufs, (w_self, idx, w)):
-                if a.size:
-                    b.upload(a)
-            self.ctx.combine_rows_dev(self._db.ptr, N, L, self._hbuf.dtype == np.float64, d_self, bufs[0].ptr,
-                                      bufs[1].ptr if r else None, bufs[2].ptr if r else None, n, r, d_out)
-        finally:
-            for b in bufs:
-                b.free()
+        N, L = self.shape
+        with self.ctx.scratch() as tmp:
+            d_w_self, d_idx, d_w = tmp.upload(w_self), tmp.upload(idx), tmp.upload(w)
+            self.ctx.combine_rows_dev(self._db.ptr, N, L, self.dtype == np.float64, d_self, d_w_self.ptr,
+                                      d_idx.ptr if r else None, d_w.ptr if r else None, n, r, d_out)
 
     def rank_expanded(self, query_vecs: np.ndarray, k: int, qe, members=None, return_queries: bool = False):
         """`rank` after query expansion `qe` (pvsim.expand.QueryExpansion): the queries are ranked, each is replaced by
@@ -385,8 +412,8 @@ class DeviceIndex(Mapping):
         if not isinstance(qe, QueryExpansion):
             raise TypeError("qe must be a pvsim.expand.QueryExpansion")
         q = np.asarray(query_vecs)
-        N, L = self._shape
-        dt = self._hbuf.dtype
+        N, L = self.shape
+        dt = self.dtype
         if q.ndim != 2 or q.shape[1] != L:
             raise ValueError("query and database dimensions differ")
         if dt == np.float32 and q.dtype != np.float32:
@@ -405,9 +432,8 @@ class DeviceIndex(Mapping):
             out = (np.zeros((0, int(k)), np.int64), np.zeros((0, int(k)), dt))
             return out + (q,) if return_queries else out
         n1 = min(qe.n, N)
-        d_q = self.ctx.buffer(q.nbytes).upload(q)
-        d_e = self.ctx.buffer(q.nbytes)
-        try:
+        with self.ctx.scratch() as tmp:
+            d_q, d_e = tmp.upload(q), tmp(q.nbytes)
             if members is None:
                 idx, val, inv_q = self._rank_dev(d_q.ptr, nq, n1, want_inv=True)
             elif qe.scheme == "alpha":                                   # the members' scores: from the complete ranking
@@ -425,8 +451,6 @@ class DeviceIndex(Mapping):
                     idx, val = self._rank_dev(d_e.ptr, nq, n1)
             out = self._rank_dev(d_e.ptr, nq, int(k))
             return out + (d_e.download((nq, L), dt),) if return_queries else out
-        finally:
-            d_q.free(), d_e.free()
 
     def augmented(self, r: int = 10, scheme: str = "linear", alpha: int = 3, block: int = 4096) -> "DeviceIndex":
         """Database-side augmentation: a new DeviceIndex with the same paths in the same order, whose row i is
@@ -438,9 +462,9 @@ class DeviceIndex(Mapping):
         _check_count("r", r)
         _check_count("block", block)
         _check_scheme(scheme, alpha)
-        N, L = self._shape
-        dt = self._hbuf.dtype
-        d_new = self.ctx.buffer(max(N * L * dt.itemsize, 16))
+        N, L = self.shape
+        dt = self.dtype
+        d_new = self.ctx.buffer(N * L * dt.itemsize)
         if N and L:
             kk = min(int(r), N - 1) + 1
             inv = self.inv_norms

@@ -480,3 +480,56 @@ def test_device_index_after_updates_equals_a_rebuild(gpu_ctx, dtype):
     alive = list(range(30))
     check()
     index.close(), old.close()
+
+
+def _small_updated_index(ctx, dtype):
+    """a DeviceIndex of 40 x 16 rows after a remove of 3 scattered paths and an add of 5 -> (index, dict of the survivors in order,
+    rows); its host mirror is behind by those two updates"""
+    from pvsim.index import DeviceIndex
+    x, paths = _corpus(7500, 16, n=45)
+    x = x.astype(dtype)
+    index = DeviceIndex({paths[i]: x[i] for i in range(40)}, ctx)
+    index.remove([paths[i] for i in (31, 2, 17)])
+    index.add({paths[i]: x[i] for i in range(40, 45)})
+    alive = [i for i in range(45) if i not in (2, 17, 31)]
+    assert len(index._pending) == 2 and list(index) == [paths[i] for i in alive]
+    return index, {paths[i]: x[i] for i in alive}, x
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_eval_leaves_the_host_mirror_of_an_updated_index_alone(gpu_ctx, dtype):
+    """the retrieval functions rank a resident index on the device and read its paths: the rows an update left behind in the host
+    mirror are not compacted for them, and the results are those of the dict of the survivors"""
+    from pvsim import eval as ev
+    index, survivors, x = _small_updated_index(gpu_ctx, dtype)
+    labels = {p: i % 4 for i, p in enumerate(survivors)}
+    queries, q_labels = [x[5], x[2], x[41], x[30]], [1, 0, 3, 2]
+    for target in (index, survivors):
+        got = [ev.retrieve_top_k_similar(queries[0], target, _Identity(), k=7),
+               ev.retrieve_top_k_similar(queries[1], target, _Identity(), k=100),
+               ev.top_k_map(queries, q_labels, target, labels, _Identity(), k=9),
+               ev.top_k_map(queries, q_labels, target, labels, _Identity()),
+               ev.top_k_accuracy(queries, q_labels, target, labels, _Identity(), k=3)]
+        if target is index:
+            assert len(index._pending) == 2                         # nobody asked for host rows
+            resident = got
+    assert len(resident[1]) == 42
+    for a, b in zip(resident[:2], got[:2]):
+        assert [p for p, _ in a] == [p for p, _ in b] and _same(np.array([s for _, s in a]), np.array([s for _, s in b]))
+    assert resident[2:] == got[2:]
+    index.close()
+
+
+def test_expand_verified_after_an_update(gpu_ctx):
+    """the members' positions come from the index's own path ledger: the list equals the one the dict of the survivors gives"""
+    from pvsim import QueryExpansion
+    from pvsim import eval as ev
+    index, survivors, x = _small_updated_index(gpu_ctx, np.float32)
+    names = list(survivors)
+    ranked = [(names[1], 0.9, 12), (names[20], 0.8, 2), (names[-1], 0.7, 9), (names[5], 0.6, 0)]     # two verified: one old, one added
+    got = ev.expand_verified(x[5], ranked, index, _Identity(), k=6, qe=QueryExpansion(n=3))
+    want = ev.expand_verified(x[5], ranked, survivors, _Identity(), k=6, qe=QueryExpansion(n=3))
+    assert len(got) == 6 and [p for p, _ in got] == [p for p, _ in want]
+    assert _same(np.array([s for _, s in got]), np.array([s for _, s in want]))
+    assert len(index._pending) == 2
+    index.close()

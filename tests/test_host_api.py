@@ -248,3 +248,60 @@ def test_one_hip_runtime_is_mapped_in_either_import_order(order):
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("RUNTIMES")][-1].split()
     assert line[1] == "1", r.stdout
+
+
+def test_scratch_scope_frees_its_buffers_however_it_ends():
+    """Context.scratch() over a context that only records: what a block allocated is freed when it ends, normally, by an exception in
+    the body or by a failing allocation; a kept buffer is the caller's; an empty array is given a buffer and no copy"""
+    from pvsim.engine import Context
+
+    class Buf:
+        def __init__(self, log, nbytes):
+            self.log, self.nbytes, self.uploads = log, nbytes, 0
+
+        def upload(self, a):
+            self.uploads += 1
+            return self
+
+        def free(self):
+            self.log["freed"].append(self)
+
+    class Recorder:
+        def __init__(self, fail_at=None):
+            self.made, self.freed, self.fail_at = [], [], fail_at
+
+        def buffer(self, nbytes):
+            if len(self.made) == self.fail_at:
+                raise MemoryError("out of device memory")
+            self.made.append(Buf({"freed": self.freed}, nbytes))
+            return self.made[-1]
+
+    def same(a, b):
+        return len(a) == len(b) and all(x is y for x, y in zip(a, b))
+
+    ctx = Recorder()
+    with Context.scratch(ctx) as tmp:
+        a, b = tmp(8), tmp.upload(np.arange(3, dtype=np.int64))
+        assert tmp.ctx is ctx and (a.nbytes, b.nbytes, a.uploads, b.uploads) == (8, 24, 0, 1) and ctx.freed == []
+    assert same(ctx.made, [a, b]) and same(ctx.freed, [a, b])
+    ctx = Recorder()
+    with pytest.raises(KeyError):
+        with Context.scratch(ctx) as tmp:
+            tmp(1), tmp(2)
+            raise KeyError("the body fails")
+    assert len(ctx.made) == 2 and same(ctx.freed, ctx.made)
+    ctx = Recorder(fail_at=2)
+    with pytest.raises(MemoryError):
+        with Context.scratch(ctx) as tmp:
+            bufs = [tmp(n) for n in (1, 2, 3, 4)]                   # the third allocation fails: the first two are still freed
+    assert len(ctx.made) == 2 and same(ctx.freed, ctx.made)
+    ctx = Recorder()
+    with Context.scratch(ctx) as tmp:
+        a, b, c = tmp(1), tmp(2), tmp(3)
+        assert tmp.keep(b) is b and tmp.keep(None) is None
+    assert same(ctx.freed, [a, c])
+    ctx = Recorder()
+    with Context.scratch(ctx) as tmp:
+        e = tmp.upload(np.zeros((0, 4), np.float32))
+        assert e.nbytes == 0 and e.uploads == 0
+    assert same(ctx.freed, [e])

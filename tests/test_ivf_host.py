@@ -326,8 +326,8 @@ def test_eval_refusals_with_nprobe():
     index, a = _stub(rng)
     flat = CompactIndex(a["paths"], a["codes"], a["inv"], ProductQuantizer.from_codebooks(a["cb"]))
     labels = {p: 0 for p in a["paths"]}
-    vecs, paths, res = ev._vectors_and_paths(index)
-    assert vecs is None and paths == a["paths"] and res is index
+    plan = ev._plan(index, nprobe=2)
+    assert plan.matrix is None and plan.paths == a["paths"] and plan.paths is index._paths and plan.n == len(index)
 
     class Identity:
         def encode(self, v):

@@ -229,10 +229,10 @@ def test_eval_rejects_full_ranking_of_a_compact_index():
     cb = rng.standard_normal((2, 4, 2)).astype(np.float32)
     ci = CompactIndex(["a", "b", "c"], rng.integers(0, 4, (3, 2)).astype(np.uint8), np.ones(3, np.float32),
                       ProductQuantizer.from_codebooks(cb))
-    vecs, paths, res = ev._vectors_and_paths(ci)
-    assert vecs is None and paths == ["a", "b", "c"] and res is ci
+    plan = ev._plan(ci)
+    assert plan.matrix is None and plan.paths == ["a", "b", "c"] and plan.paths is ci._paths and plan.n == 3
     with pytest.raises(ValueError, match="pass k"):
-        ev._rank(np.zeros((1, 4), np.float32), vecs, None, None, res)
+        plan.rank(np.zeros((1, 4), np.float32), None)
 
     class Identity:
         def encode(self, v):

@@ -78,6 +78,66 @@ def test_removal_follows_dict_deletion():
     assert np.array_equal(buf[:36], want)
 
 
+def test_path_ledger_follows_a_dict():
+    """pvsim.index._PathLedger (paths <-> positions of every mutable index) against a plain dict given the same adds and removes"""
+    from pvsim.index import _PathLedger
+    rng = np.random.default_rng(1512)
+    names = [f"img/{i}.jpg" for i in range(200)]
+    d = dict.fromkeys(names[:60])
+    ledger = _PathLedger(names[:60])
+
+    def same():
+        live = list(d)
+        assert ledger.paths == live and len(ledger) == len(live)
+        assert [ledger.index_of(p) for p in live] == list(range(len(live)))
+        for p in names:
+            assert (p in ledger) == (p in d)
+            if p not in d:
+                with pytest.raises(KeyError):
+                    ledger.index_of(p)
+
+    def add(paths):
+        ledger.check_new(paths)
+        ledger.append(paths)
+        d.update(dict.fromkeys(paths))
+        same()
+
+    def remove(paths):
+        idx = ledger.removed_indices(paths)
+        assert idx.dtype == np.int64 and idx.tolist() == sorted(list(d).index(p) for p in paths)
+        ledger.remove(idx)
+        for p in paths:
+            del d[p]
+        same()
+
+    same()
+    remove([names[0]])                                              # the first path, then the last
+    remove([names[59]])
+    add([])
+    remove([])
+    add(names[60:93])                                               # 33 paths
+    remove(names[90:93])                                            # right behind the add that brought them
+    add([names[0]])                                                 # a removed path comes back, in the last place
+    assert ledger.paths[-1] == names[0] and ledger.index_of(names[0]) == len(d) - 1
+    for step in range(45):                                          # mixed: 0, 1, 33 new paths; 0, 1 or scattered removed ones
+        absent = [p for p in names if p not in d]
+        b = min((0, 1, 33)[step % 3], len(absent))
+        add([absent[i] for i in rng.permutation(len(absent))[:b]])
+        live = list(d)
+        r = min((1, 0, int(rng.integers(2, 20)))[step % 3], len(live))
+        remove([live[i] for i in rng.permutation(len(live))[:r]])
+    # the four refusals leave everything as it was
+    live, absent = list(d), [p for p in names if p not in d]
+    for bad, exc, match in ((lambda: ledger.check_new([absent[0], live[3]]), ValueError, "is already indexed"),
+                            (lambda: ledger.check_new([absent[0], absent[1], absent[0]]), ValueError, "named twice in one add"),
+                            (lambda: ledger.removed_indices([live[0], absent[0]]), KeyError, None),
+                            (lambda: ledger.removed_indices([live[0], live[1], live[0]]), ValueError, "named twice in one remove")):
+        with pytest.raises(exc, match=match):
+            bad()
+        same()
+    assert ledger.removed_indices(live[5]).tolist() == [5]          # one path as a string
+
+
 # ------------------------------------------------------------------------------------------------ inverted lists
 def _stored(rng, lists, nlist, m):
     """an index's storage from the list number of every row, by the product's own host sort"""
@@ -189,10 +249,9 @@ def test_compact_index_update_validation_touches_no_device():
 
 
 def test_device_index_update_validation_touches_no_device():
-    from pvsim.index import DeviceIndex
+    from pvsim.index import DeviceIndex, _PathLedger
     index = DeviceIndex.__new__(DeviceIndex)                        # the surface without a context: paths and the host mirror only
-    index._paths = ["a", "b", "c"]
-    index._pos = {p: i for i, p in enumerate(index._paths)}
+    index._ledger = _PathLedger(["a", "b", "c"])
     index._hbuf = np.arange(12, dtype=np.float32).reshape(3, 4)
     index._pending, index._mirror_rows, index._cap = [], 3, 3
     row = np.zeros(4, np.float32)
@@ -215,7 +274,7 @@ def test_device_index_update_validation_touches_no_device():
     rows = {p: np.full(4, i, np.float32) for i, p in enumerate("defgh")}
     index._pending = [("remove", np.array([0, 2])), ("add", np.stack([rows["d"], rows["e"]])), ("remove", np.array([1])),
                       ("add", np.stack([rows["f"]]))]
-    index._paths, index._cap = ["b", "e", "f"], 8
+    index._ledger, index._cap = _PathLedger(["b", "e", "f"]), 8
     assert np.array_equal(index.matrix, np.stack([np.arange(4, 8, dtype=np.float32), rows["e"], rows["f"]]))
     assert index._pending == [] and index._mirror_rows == 3 and index._hbuf.shape[0] == 3
 

@@ -16,7 +16,7 @@ rows behind the first removed one only), and for the class level `rebuild_ms`: t
 replaces (IVF: download, argsort into lists, upload, as IVFCompactIndex.fit does it; flat and dense: the upload by the constructor).
 An add is undone by an untimed remove of the same rows, a remove by an untimed add (which appends: every timed remove therefore names
 the rows that stand at the same scattered POSITIONS at that moment).  The class level at N = 10^6 includes what Python costs on the
-path list and the position dict (O(N) per remove).  Nothing here is a pass / fail threshold."""
+path list (one slice per run of kept paths).  Nothing here is a pass / fail threshold."""
 import argparse
 import json
 import os
@@ -136,9 +136,9 @@ def main():
         outs = [ctx.buffer(s) for s in ((n - r) * m, (n - r) * 4, (n - r) * 4, (nlist + 1) * 8)]
 
         def remove():
-            keep, pos = _keep_positions(ctx, idx, n)
-            ctx.ivf_remove_dev(m, nlist, n, d_codes.ptr, d_inv.ptr, d_ids.ptr, d_off.ptr, keep.ptr, pos.ptr, *(o.ptr for o in outs))
-            keep.free(), pos.free()
+            with ctx.scratch() as tmp:
+                keep, pos = _keep_positions(tmp, idx, n)
+                ctx.ivf_remove_dev(m, nlist, n, d_codes.ptr, d_inv.ptr, d_ids.ptr, d_off.ptr, keep.ptr, pos.ptr, *(o.ptr for o in outs))
 
         emit({"level": "entry", "index": "ivf", "op": "mask + positions + pvs_ivf_remove_dev", "rows": r, **shape,
               "ms": _timed(ctx, remove, args.steps, args.warmup), "copy_ms": c_stored, "moved_bytes": stored_bytes})
@@ -147,7 +147,8 @@ def main():
     c_codes = copy_ms(n * m)
     d_out = ctx.buffer(n * m)
     for r, idx in scattered.items():
-        keep, pos = _keep_positions(ctx, idx, n)
+        with ctx.scratch() as tmp:                                # kept past the block: freed below
+            keep, pos = (tmp.keep(b) for b in _keep_positions(tmp, idx, n))
         ms = _timed(ctx, lambda: ctx.compact_rows_dev(d_codes.ptr, n, m, keep.ptr, pos.ptr, d_out.ptr), args.steps, args.warmup)
         emit({"level": "entry", "index": "codes", "op": "pvs_compact_rows_dev out of place", "rows": r, **shape, "ms": ms,
               "copy_ms": c_codes, "moved_bytes": n * m})
@@ -222,7 +223,8 @@ def main():
               "ms": _timed(ctx, index.remove, args.steps, args.warmup, prepare=lambda: [index._paths[i] for i in idx],
                            undo=lambda gone: index.add({p: mat[int(p[5:])] for p in gone}))})
         # the device's part alone: the in-place compaction of the resident rows, restored by an untimed copy
-        keep, pos = _keep_positions(ctx, idx.astype(np.int64), N)
+        with ctx.scratch() as tmp:
+            keep, pos = (tmp.keep(b) for b in _keep_positions(tmp, idx.astype(np.int64), N))
         d_save = ctx.buffer(N * L * 4)
         ctx.copy_dev(d_save.ptr, index._db.ptr, N * L * 4)
         emit({"level": "entry", "index": "dense", "op": "pvs_compact_rows_dev in place", "rows": r, "first": int(idx[0]), **dshape,
