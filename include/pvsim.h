@@ -676,6 +676,36 @@ int pvs_rank_f64_dev(pvs_ctx* ctx, const double* d_scores, int64_t nq, int64_t n
 int pvs_asmk_aggregate_dev(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, int desc_kind, const int64_t* d_offsets,
                            const int64_t* h_offsets, int64_t n_images, int64_t total_desc, const int32_t* d_labels,
                            const float* d_proj, int bits, int32_t* d_ent_word, uint32_t* d_ent_sig, int32_t* d_ent_count);
+
+/* MULTIPLE ASSIGNMENT of a query's rows (the paper assigns every query row to its 5 nearest words; the database stays single
+ * assignment).
+ *
+ * TOP-M LIST of a row.  For a row x (the value the encoders use; for the RootSIFT kinds, what pvs_materialise_dev gives) and
+ * centroid j < K:
+ *   dot_j  the float32 fma chain of the exact assignment kernel: it starts at +0 and runs over the dims in the order
+ *          (8t + e, 8t + 4 + e), e = 0..3, t ascending.
+ *   v_j    = fmaf(-2, dot_j, |c_j|^2), with |c_j|^2 the sequential float32 sum the codebook stores.  |x|^2 is not added.  A v_j that
+ *          is NaN or +inf counts as +inf.
+ *   list   the first m centroids in the order (v ascending, j ascending), 1 <= m <= min(K, 8).  The order is total, so the list does
+ *          not depend on how the vocabulary or the rows are cut.  Column 0 is the label of pvs_kmeans_predict_dev for every input
+ *          that entry point accepts, an all-NaN row included (label 0).  Padded rows of the table (index >= K) never appear.
+ * The same descriptor kinds, D range and alignment rules (vector and scalar load path) as pvs_kmeans_predict_dev.  d_labels int32
+ * [total_desc][m]; d_val float32 [total_desc][m] (the v of every label) or NULL.  A workgroup takes 256 rows and a contiguous
+ * range of the table's 256-centroid blocks: splits = 0 leaves the number of ranges to the host (about two workgroups per compute
+ * unit over the launch, at least one block per range, so a large batch gets 1), any other value is clamped to 1..(K_pad / 256),
+ * K_pad = K rounded up to 256 (1 range where K <= 128) -- every value gives the same bits.  No global atomics.  m outside
+ * 1..min(K, 8) is PVS_ERR_INVALID; total_desc == 0 is a no-op.  Enqueues on the context's stream and never waits.  Timed on slot 0. */
+int pvs_kmeans_topm_dev(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, int desc_kind, int64_t total_desc, int m, int splits,
+                        int32_t* d_labels, float* d_val);
+/* ENTRIES with m labels per row: d_labels int32 [total_desc][m], the m labels of a row distinct and in [0, K) (preconditions;
+ * pvs_kmeans_topm_dev gives such lists).  The entries of an image are the distinct labels over all its rows and slots, ascending.
+ * V of word w adds (x_j - c_w) for j ascending over the rows that hold w in any slot; z, bits and storage as above.  Image i
+ * writes to the slots m offsets[i] .. of d_ent_word int32 [m total_desc] and d_ent_sig uint32 [m total_desc][bits / 32].  Limits:
+ * at most 8192 rows and rows * m <= 16384 keys per image (a 2000-row query fits at m = 8), 1 <= m <= min(K, 8); more is
+ * PVS_ERR_UNSUPPORTED.  At m = 1 the outputs are those of pvs_asmk_aggregate_dev.  Timed on slot 1. */
+int pvs_asmk_aggregate_ma_dev(pvs_ctx* ctx, const pvs_codebook* cb, const void* d_desc, int desc_kind, const int64_t* d_offsets,
+                              const int64_t* h_offsets, int64_t n_images, int64_t total_desc, const int32_t* d_labels, int m,
+                              const float* d_proj, int bits, int32_t* d_ent_word, uint32_t* d_ent_sig, int32_t* d_ent_count);
 /* Query q holds the entries h_q_off[q] .. h_q_off[q + 1] - 1 of d_q_word int32 / d_q_sig uint32 [.][bits / 32] (h_q_off: HOST int64
  * [nq + 1], non-decreasing); a query word outside [0, K) is skipped.  d_word_off, d_ent_img, d_ent_sig, d_gamma_db: the storage
  * above for N < 2^31 images; d_wt int32 [K], d_sel int32 [bits + 1], d_gamma_q float32 [nq].  Signature arrays are 16-byte aligned

@@ -126,6 +126,13 @@ static void update_sites(size_t n, size_t tile) {
   CHECK(update_stage_bytes(n, 3) == al(n * 3), "staging block of %zu rows", n);
 }
 
+// the partial lists of the top-m assignment (assign_topm.hip): indices, then values, [row][split][m] each
+static void topm_site(size_t total, size_t splits, size_t m) {
+  const TopmPartialLayout t = topm_partial_layout(total, splits, m);
+  const size_t piece = al(total * splits * m * 4);
+  CHECK(t.idx.off == 0 && t.val.off == piece && t.bytes == 2 * piece, "top-m partial lists total=%zu splits=%zu m=%zu", total, splits, m);
+}
+
 int main() {
   generic_align<256>();
   generic_align<16>();
@@ -152,6 +159,10 @@ int main() {
   for (size_t N : rows) update_sites(N, 64);
   for (size_t nc : rows) sift_site(nc);
   for (size_t nc : Ns) sift_site(nc);
+  const size_t splits[] = {2, 3, 64, 256}, ms[] = {1, 5, 8};
+  for (size_t total : Ns)
+    for (size_t sp : splits)
+      for (size_t m : ms) topm_site(total, sp, m);
 
   if (g_fail) {
     fprintf(stderr, "ws_layout_check: %d checks failed\n", g_fail);

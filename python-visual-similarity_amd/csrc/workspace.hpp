@@ -29,7 +29,7 @@ namespace pvs {
 //                     learn.hip: launch_label_sums (squared rows), launch_gram (tile accumulator)
 //   WS_FP16_ROWS      filter.hip: launch_cosine_topk_filtered
 //   WS_LISTS          filter.hip: launch_cosine_topk_filtered; api.hip: pvs_cosine_topk_f64; vlad.hip: launch_assign;
-//                     neighbors.hip: knn_f64_rows, pvs_l2_knn_dev
+//                     neighbors.hip: knn_f64_rows, pvs_l2_knn_dev; assign_topm.hip: pvs_kmeans_topm_dev (partial lists, splits > 1)
 //   WS_NB_NORMS       neighbors.hip: pvs_l2_knn_dev, radius_impl
 //   WS_NB_F64_ROWS    neighbors.hip: to_f64_copies
 //   WS_DSIFT_TABLE    dsift.hip: pvs_dsift_dev
@@ -177,6 +177,17 @@ struct IvfRemoveLayout {
 inline IvfRemoveLayout ivf_remove_layout(size_t n, size_t ntiles, size_t tile) {
   WsLayout<> l;
   return {l.add<uint8_t>(n), l.add<int64_t>(n + 1), l.add<int64_t>(ntiles), l.add<int64_t>(tile), l.add<int64_t>(1), l.bytes()};
+}
+
+// pvs_kmeans_topm_dev with splits > 1, WS_LISTS: the partial lists [row][split][m], indices then values
+struct TopmPartialLayout {
+  WsPiece<int32_t> idx;
+  WsPiece<float> val;
+  size_t bytes;
+};
+inline TopmPartialLayout topm_partial_layout(size_t total, size_t splits, size_t m) {
+  WsLayout<> l;
+  return {l.add<int32_t>(total * splits * m), l.add<float>(total * splits * m), l.bytes()};
 }
 
 }  // namespace pvs

@@ -79,6 +79,7 @@ SIGNATURES = {
     "pvs_vlad_encode": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _np, _vp, _vp],
     "pvs_vlad_encode_dev": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _np, _vp, _vp, _vp],
     "pvs_kmeans_predict_dev": [_vp, _vp, _vp, _int, _i64, _vp],
+    "pvs_kmeans_topm_dev": [_vp, _vp, _vp, _int, _i64, _int, _int, _vp, _vp],
     "pvs_fisher_encode": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _np, _vp],
     "pvs_fisher_encode_dev": [_vp, _vp, _vp, _vp, _int, _vp, _i64, _i64, _np, _vp, _int],
     "pvs_gmm_predict_proba_dev": [_vp, _vp, _vp, _int, _i64, _vp],
@@ -147,6 +148,7 @@ SIGNATURES = {
     "pvs_diffuse_cg_dev": [_vp, _vp, _vp, _i64, _int, _vp, _i64, C.c_double, C.c_double, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp],
     "pvs_rank_f64_dev": [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp],
     "pvs_asmk_aggregate_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp],
+    "pvs_asmk_aggregate_ma_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp],
     "pvs_asmk_score_dev": [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _i64],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],

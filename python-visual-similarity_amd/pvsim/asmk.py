@@ -8,7 +8,7 @@ the words two images share.  It searches a database by the local descriptors the
 
     local = LocalFeatureIndex.from_images(paths)
     index = ASMKIndex.fit(local, n_words=65536)                  # or ASMKIndex.build(local, vocabulary)
-    hits = index.retrieve(query_image, k=100)                    # [(path, score)]
+    hits = index.retrieve(query_image, k=100)                    # [(path, score)]; ma=5 assigns every query row to its 5 nearest words
     ranked = eval.rerank_spatial(query_image, hits, local, SpatialVerifier())
 
 Two device kernels (csrc/asmk.hip) do the work: the aggregation of a batch of images into entries, and the scan of the inverted file
@@ -27,6 +27,8 @@ __all__ = ["ASMKIndex", "selectivity", "word_weights", "gammas", "random_project
 SCALE = 1023                       # sel[0], and the factor of gamma
 IDF_SCALE = 64                     # wt = rint(64 ln(N / df))
 MAX_ROWS = 8192                    # rows of one image (pvs_asmk_aggregate_dev)
+MAX_MA = 8                         # words per query row (pvs_kmeans_topm_dev)
+MAX_KEYS = 16384                   # rows x words of one query image (pvs_asmk_aggregate_ma_dev)
 PANEL_BYTES = 64 << 20             # score panel of one query block
 _KIND = "asmk_index"
 
@@ -101,24 +103,47 @@ def _row_dtype(kind):
 
 
 # ------------------------------------------------------------------------------------------------ device steps
-def device_entries(ctx, cb, d_rows, offsets, kind, d_proj, bits):
+def check_ma(ma, n_words: int, offsets=None) -> int:
+    """`ma`, the words a query row is assigned to: an integer in 1..min(8, n_words).  With `offsets`, also the keys of the largest
+    image: rows * ma <= 16384 (pvs_asmk_aggregate_ma_dev).  Raises before any device work."""
+    if isinstance(ma, bool) or not isinstance(ma, (int, np.integer)) or not (1 <= ma <= min(MAX_MA, int(n_words))):
+        raise ValueError(f"ma must be an integer in 1..{min(MAX_MA, int(n_words))}, got {ma!r}")
+    ma = int(ma)
+    if ma > 1 and offsets is not None:
+        rows = int(np.diff(np.asarray(offsets, np.int64)).max(initial=0))
+        if rows * ma > MAX_KEYS:
+            raise NotImplementedError(f"a query of {rows} rows at ma = {ma} holds {rows * ma} keys, more than {MAX_KEYS}")
+    return ma
+
+
+def device_entries(ctx, cb, d_rows, offsets, kind, d_proj, bits, ma=1):
     """assign + aggregate + download + compact for the images whose rows lie at `d_rows` (device pointer) with host CSR `offsets`.
-    -> (ent_off int64 (n + 1,), words int32 (E,), sigs uint32 (E, bits / 32)), image-major, words ascending inside an image."""
+    -> (ent_off int64 (n + 1,), words int32 (E,), sigs uint32 (E, bits / 32)), image-major, words ascending inside an image.
+    ma = 1: every row goes to its nearest word (pvs_kmeans_predict_dev + pvs_asmk_aggregate_dev); ma >= 2: to its ma nearest words
+    (pvs_kmeans_topm_dev + pvs_asmk_aggregate_ma_dev), the multiple assignment of a QUERY's rows."""
     offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    ma = check_ma(ma, cb.K, offsets)
     n, total, W = len(offsets) - 1, int(offsets[-1]), bits // 32
     if n == 0 or total == 0:
         return np.zeros(n + 1, np.int64), np.zeros(0, np.int32), np.zeros((0, W), np.uint32)
+    slots = total * ma
     with ctx.scratch() as tmp:
-        d_lab, d_word, d_sig, d_cnt, d_off = tmp(total * 4), tmp(total * 4), tmp(total * 4 * W), tmp(n * 4), tmp.upload(offsets)
-        ctx.kmeans_predict_dev(cb, d_rows, kind, total, d_lab.ptr)
-        ctx.asmk_aggregate_dev(cb, d_rows, kind, d_off.ptr, offsets, n, total, d_lab.ptr, d_proj, bits, d_word.ptr, d_sig.ptr, d_cnt.ptr)
+        d_lab, d_word, d_sig, d_cnt, d_off = tmp(slots * 4), tmp(slots * 4), tmp(slots * 4 * W), tmp(n * 4), tmp.upload(offsets)
+        if ma == 1:
+            ctx.kmeans_predict_dev(cb, d_rows, kind, total, d_lab.ptr)
+            ctx.asmk_aggregate_dev(cb, d_rows, kind, d_off.ptr, offsets, n, total, d_lab.ptr, d_proj, bits, d_word.ptr, d_sig.ptr, d_cnt.ptr)
+        else:
+            ctx.kmeans_topm_dev(cb, d_rows, kind, total, ma, d_lab.ptr)
+            ctx.asmk_aggregate_ma_dev(cb, d_rows, kind, d_off.ptr, offsets, n, total, d_lab.ptr, ma, d_proj, bits, d_word.ptr, d_sig.ptr,
+                                      d_cnt.ptr)
         counts = d_cnt.download((n,), np.int32).astype(np.int64)
-        words = d_word.download((total,), np.int32)
-        sigs = d_sig.download((total, W), np.uint32)
+        words = d_word.download((slots,), np.int32)
+        sigs = d_sig.download((slots, W), np.uint32)
     ent_off = np.zeros(n + 1, np.int64)
     np.cumsum(counts, out=ent_off[1:])
-    slot = np.arange(total, dtype=np.int64) - np.repeat(offsets[:-1], np.diff(offsets))     # position of a slot inside its image
-    keep = slot < np.repeat(counts, np.diff(offsets))
+    per = np.diff(offsets) * ma                                                              # slots of an image
+    slot = np.arange(slots, dtype=np.int64) - np.repeat(offsets[:-1] * ma, per)             # position of a slot inside its image
+    keep = slot < np.repeat(counts, per)
     return ent_off, np.ascontiguousarray(words[keep]), np.ascontiguousarray(sigs[keep])
 
 
@@ -305,11 +330,12 @@ class ASMKIndex:
                 f"alpha={self.alpha}, tau={self.tau}, idf={self.idf})")
 
     # -------------------------------------------------------------------------------------------------- queries
-    def query_entries(self, d_rows, offsets):
-        """entries of query images whose rows are on the device -> (ent_off, words, sigs)"""
+    def query_entries(self, d_rows, offsets, ma=1):
+        """entries of query images whose rows are on the device -> (ent_off, words, sigs); `ma`: words per row (1..min(8, n_words))"""
+        ma = check_ma(ma, self.n_words, offsets)
         dev = self._resident()
         return device_entries(self.ctx, dev["cb"], d_rows, offsets, self.desc_kind,
-                              dev["projection"].ptr if dev["projection"] is not None else None, self.bits)
+                              dev["projection"].ptr if dev["projection"] is not None else None, self.bits, ma)
 
     def rank_entries(self, ent_off, words, sigs, k: int, slice_images: int = 0):
         """Rank the database for queries given as entries -> (idx int64 (nq, k), val float32 (nq, k)); slots that cannot be filled
@@ -346,8 +372,10 @@ class ASMKIndex:
             val[:, :kk] = d_val.download((nq, kk), np.float32)
         return idx, val
 
-    def rank_rows(self, rows_list, k: int):
-        """Rank the database for queries given as host descriptor rows (one (n, D) array per query, uint8 for DESC_U8_ROOTSIFT)."""
+    def rank_rows(self, rows_list, k: int, ma=1):
+        """Rank the database for queries given as host descriptor rows (one (n, D) array per query, uint8 for DESC_U8_ROOTSIFT).
+        `ma`: the nearest words every query row is assigned to (the paper uses 5); the database stays single assignment."""
+        ma = check_ma(ma, self.n_words)
         D = self.centroids.shape[1]
         dt = _row_dtype(self.desc_kind)
         rows_list = [np.ascontiguousarray(r, dtype=dt).reshape(-1, D) for r in rows_list]
@@ -356,28 +384,30 @@ class ASMKIndex:
         off = np.zeros(len(rows_list) + 1, np.int64)
         np.cumsum([len(r) for r in rows_list], out=off[1:])
         total = int(off[-1])
+        check_ma(ma, self.n_words, off)
         with self.ctx.scratch() as tmp:
             d_rows = tmp.upload(np.concatenate(rows_list) if total else np.zeros((0, D), dt))
-            ent = self.query_entries(d_rows.ptr, off)
+            ent = self.query_entries(d_rows.ptr, off, ma)
         return self.rank_entries(*ent, k)
 
-    def rank_images(self, images, k: int):
-        """Rank the database for query images (arrays or paths), extracted with the index's extractor."""
+    def rank_images(self, images, k: int, ma=1):
+        """Rank the database for query images (arrays or paths), extracted with the index's extractor; `ma` as in rank_rows."""
         from .verify import LocalFeatureIndex
+        ma = check_ma(ma, self.n_words)
         if self.desc_kind != DESC_U8_ROOTSIFT:
             raise ValueError("images are extracted as uint8 rows: the index must read DESC_U8_ROOTSIFT")
         q = LocalFeatureIndex.from_images(list(images), self.extractor, ctx=self.ctx)
         try:
             if int(np.diff(q.offsets).max(initial=0)) > MAX_ROWS:
                 raise NotImplementedError(f"a query of more than {MAX_ROWS} rows is not supported")
-            ent = self.query_entries(q.rows.ptr, q.offsets)
+            ent = self.query_entries(q.rows.ptr, q.offsets, ma)
         finally:
             q.close()
         return self.rank_entries(*ent, k)
 
-    def retrieve(self, query_image, k: int = 100) -> list:
-        """-> [(path, score)] best first: the `hits` that eval.rerank_spatial takes."""
-        idx, val = self.rank_images([query_image], k)
+    def retrieve(self, query_image, k: int = 100, ma=1) -> list:
+        """-> [(path, score)] best first: the `hits` that eval.rerank_spatial takes.  `ma`: words per query row (rank_rows)."""
+        idx, val = self.rank_images([query_image], k, ma)
         return [(self._paths[int(i)], float(v)) for i, v in zip(idx[0], val[0]) if i >= 0]
 
     # -------------------------------------------------------------------------------------------------- persistence

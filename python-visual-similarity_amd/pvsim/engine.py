@@ -429,6 +429,12 @@ class Context:
     def kmeans_predict_dev(self, cb, d_desc, kind, total_desc, d_labels):
         check(_ffi.lib().pvs_kmeans_predict_dev(self.handle, cb.handle, ptr(d_desc), kind, total_desc, ptr(d_labels)))
 
+    def kmeans_topm_dev(self, cb, d_desc, kind, total_desc, m, d_labels, d_val=None, splits=0):
+        """pvs_kmeans_topm_dev: the m nearest centroids of every row by (v ascending, index ascending) -> d_labels int32 (total, m)
+        and, when given, their v in d_val float32 (total, m).  splits = 0 leaves the cut of the vocabulary to the host."""
+        check(_ffi.lib().pvs_kmeans_topm_dev(self.handle, cb.handle, ptr(d_desc), int(kind), int(total_desc), int(m), int(splits),
+                                             ptr(d_labels), ptr(d_val)))
+
     def gmm_predict_proba_dev(self, g, d_desc, kind, total_desc, d_resp):
         check(_ffi.lib().pvs_gmm_predict_proba_dev(self.handle, g.handle, ptr(d_desc), kind, total_desc, ptr(d_resp)))
 
@@ -546,6 +552,17 @@ class Context:
         check(_ffi.lib().pvs_asmk_aggregate_dev(self.handle, cb.handle, ptr(d_desc), int(kind), ptr(d_offsets), ptr(h), int(n_images),
                                                 int(total_desc), ptr(d_labels), ptr(d_proj), int(bits), ptr(d_ent_word), ptr(d_ent_sig),
                                                 ptr(d_ent_count)))
+
+    def asmk_aggregate_ma_dev(self, cb, d_desc, kind, d_offsets, h_offsets, n_images, total_desc, d_labels, m, d_proj, bits, d_ent_word,
+                              d_ent_sig, d_ent_count):
+        """pvs_asmk_aggregate_ma_dev: rows + m distinct labels per row (d_labels int32 (total, m)) -> per image its entries in the
+        slots m * offsets[i] .. of arrays sized m * total_desc, and their count"""
+        h = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        if h.shape != (int(n_images) + 1,):
+            raise ValueError(f"h_offsets must have n_images + 1 = {int(n_images) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_aggregate_ma_dev(self.handle, cb.handle, ptr(d_desc), int(kind), ptr(d_offsets), ptr(h), int(n_images),
+                                                   int(total_desc), ptr(d_labels), int(m), ptr(d_proj), int(bits), ptr(d_ent_word),
+                                                   ptr(d_ent_sig), ptr(d_ent_count)))
 
     def asmk_score_dev(self, nq, h_q_off, d_q_word, d_q_sig, bits, K, d_word_off, d_ent_img, d_ent_sig, N, d_wt, d_sel, d_gamma_q,
                        d_gamma_db, d_scores, ld, slice_images=0):
