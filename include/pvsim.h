@@ -719,6 +719,53 @@ int pvs_asmk_score_dev(pvs_ctx* ctx, int64_t nq, const int64_t* h_q_off, const i
                        const int32_t* d_wt, const int32_t* d_sel, const float* d_gamma_q, const float* d_gamma_db, int slice_images,
                        float* d_scores, int64_t ld);
 
+/* ---------------------------------------------------------------- ASMK maintenance: inversion on the device, list insert and remove
+ * With weights that belong to the vocabulary and not to the indexed set (a FROZEN index), gamma(X) depends on X's own entries alone,
+ * and adding or removing images is what section 15 calls an update: data movement, with the arrays of a from-scratch build of the
+ * surviving images as the result, byte for byte.  The entry points below are integer counting and data movement: no floating
+ * point; integer atomics only on counters in LDS whose result does not depend on the order of arrival, never to decide a position;
+ * no kernel waits for another workgroup; every output element is written exactly once.  They enqueue on the context's stream and
+ * never wait for the device: all sizing comes from the host copies of the offsets.  They serve fewer than 2^31 entries (slots for
+ * the inversion); more is PVS_ERR_UNSUPPORTED, found on the host.  1 <= K <= 65536, bits in {32, 64, 96, 128}, W = bits / 32.
+ * Signature arrays are 16-byte aligned at W = 4, 8-byte at W = 2, 4-byte otherwise, and move as one load of that width per entry.
+ * Timed on slot 6. */
+/* IMAGE-MAJOR ENTRIES -> INVERTED FILE.  The inputs are what pvs_asmk_aggregate_dev leaves behind: d_offsets int64 [n_images + 1]
+ * with its HOST copy h_offsets (total = h_offsets[n_images]), d_ent_count int32 [n_images], d_ent_word int32 [total], d_ent_sig
+ * uint32 [total][W].  The entries of image i are the slots offsets[i] .. offsets[i] + count[i] - 1 (count clamped to the image's
+ * slots); slots beyond are unwritten memory and are never read as entries.  An entry whose word lies outside [0, K) is dropped.
+ * Outputs, all sized by total: d_word_off int64 [K + 1], d_out_img int32 [total], d_out_sig uint32 [total][W].  word_off[K] = E is
+ * the number of defined output entries; the entry (image i, word w) stands at word_off[w] + #{i' < i holding w} and carries the id
+ * img_base + i (img_base + n_images <= 2^31 - 1).  Elements at and beyond E are not written.  A stable least-significant-digit
+ * radix sort on the word, 8-bit digits (one pass for K <= 256, otherwise two); a slot that is no entry carries a digit behind
+ * every word.  Each pass: digit counts per tile, one exclusive scan over [digit][tile], a scatter in which a lane's rank inside its
+ * tile comes from wave ballots and per-wave counts in LDS.  tile_entries = 0 leaves the tile to the host; other values are a
+ * multiple of 256 in 256..65536 (clamped, and raised where total needs more than 65536 tiles) -- every value gives the same bytes.
+ * total == 0 writes zero offsets.  Uses the workspace (16 bytes per slot and the counts). */
+int pvs_asmk_invert_dev(pvs_ctx* ctx, int K, int bits, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n_images,
+                        const int32_t* d_ent_count, const int32_t* d_ent_word, const uint32_t* d_ent_sig, int64_t img_base,
+                        int tile_entries, int64_t* d_word_off, int32_t* d_out_img, uint32_t* d_out_sig);
+/* d_sums int64 [n_images]: sums[i] = the sum over image i's entries (same slot layout) of 1023 wt[w], d_wt int32 [K]; a word outside
+ * [0, K) adds 0.  One wave per image.  gamma is float32(1 / sqrt(float64(sums[i]))) on the host, 0 where the sum is 0. */
+int pvs_asmk_weight_sums_dev(pvs_ctx* ctx, int K, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n_images,
+                             const int32_t* d_ent_count, const int32_t* d_ent_word, const int32_t* d_wt, int64_t* d_sums);
+/* LIST INSERT.  A stored file (d_word_off with its HOST copy h_word_off, d_ent_img, d_ent_sig; E = h_word_off[K] entries) and a
+ * batch inverted by pvs_asmk_invert_dev (d_new_off / h_new_off, d_new_img, d_new_sig; b = h_new_off[K]) are merged into the
+ * d_out_* arrays of E + b entries: out_word_off[w] = word_off[w] + new_off[w], and list w is its old entries followed by its new
+ * ones.  Precondition: every new id exceeds every stored id, so the result is sorted by (word, image).  One lane per merged entry
+ * finds its word by a binary search of the summed offsets.  E + b < 2^31.  Any overlap of an output with an input is
+ * PVS_ERR_INVALID.  E + b == 0 writes the offsets only. */
+int pvs_asmk_insert_dev(pvs_ctx* ctx, int K, int bits, const int64_t* d_word_off, const int64_t* h_word_off, const int32_t* d_ent_img,
+                        const uint32_t* d_ent_sig, const int64_t* d_new_off, const int64_t* h_new_off, const int32_t* d_new_img,
+                        const uint32_t* d_new_sig, int64_t* d_out_word_off, int32_t* d_out_img, uint32_t* d_out_sig);
+/* LIST REMOVE.  d_keep uint8 [N] and d_pos int64 [N + 1] by image id (pvs_keep_mask_dev / pvs_keep_positions_dev).  A stored entry e
+ * survives iff keep[ent_img[e]] != 0 (an id outside [0, N) breaks a precondition: the entry is dropped), its new id is
+ * pos[ent_img[e]], and the survivors keep their stored order.  out_word_off[w] = the number of survivors before word_off[w].
+ * h_word_off is the HOST copy of d_word_off (E = h_word_off[K] < 2^31).  Outputs, sized by E, are disjoint from the inputs
+ * (PVS_ERR_INVALID).  E == 0 writes zero offsets.  Uses the workspace (4 bytes per entry). */
+int pvs_asmk_remove_dev(pvs_ctx* ctx, int K, int bits, int64_t N, const int64_t* d_word_off, const int64_t* h_word_off,
+                        const int32_t* d_ent_img, const uint32_t* d_ent_sig, const uint8_t* d_keep, const int64_t* d_pos,
+                        int64_t* d_out_word_off, int32_t* d_out_img, uint32_t* d_out_sig);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

@@ -1,6 +1,6 @@
 // Host-only check of workspace.hpp (tests/test_workspace_host.py builds it with -fsanitize=address,undefined and runs it):
 // the generic properties of WsLayout, then four call sites held offset for offset against the closed-form byte arithmetic those sites
-// carried inline before they were written with the layout, and the blocks of update.hip against theirs.  Exit status 0 = every check held.
+// carried inline before they were written with the layout, and the blocks of update.hip and asmk_update.hip against theirs.  Exit status 0 = every check held.
 #include <cstdio>
 #include <memory>
 
@@ -133,6 +133,18 @@ static void topm_site(size_t total, size_t splits, size_t m) {
   CHECK(t.idx.off == 0 && t.val.off == piece && t.bytes == 2 * piece, "top-m partial lists total=%zu splits=%zu m=%zu", total, splits, m);
 }
 
+// the ASMK maintenance blocks (asmk_update.hip): the sort's two item arrays, digit counts and scan partials; the survivor flags
+static void asmk_update_sites(size_t total, size_t ntiles) {
+  const size_t ncounts = 257 * ntiles, nscan = (ncounts + 2047) / 2048;
+  const AsmkInvertLayout a = asmk_invert_layout(total, ncounts, nscan);
+  CHECK(a.items_a.off == 0 && a.items_b.off == al(total * 8) && a.counts.off == 2 * al(total * 8) &&
+            a.partials.off == 2 * al(total * 8) + al(ncounts * 4) && a.bytes == 2 * al(total * 8) + al(ncounts * 4) + al(nscan * 4),
+        "ASMK inversion block total=%zu ntiles=%zu", total, ntiles);
+  const AsmkRemoveLayout r = asmk_remove_layout(total, (total + 1 + 2047) / 2048);
+  CHECK(r.spos.off == 0 && r.partials.off == al((total + 1) * 4) && r.bytes == al((total + 1) * 4) + al((total + 1 + 2047) / 2048 * 4),
+        "ASMK remove block entries=%zu", total);
+}
+
 int main() {
   generic_align<256>();
   generic_align<16>();
@@ -157,6 +169,8 @@ int main() {
           }
   for (size_t N : Ns) update_sites(N, 2048);
   for (size_t N : rows) update_sites(N, 64);
+  for (size_t N : Ns) asmk_update_sites(N, (N + 255) / 256);
+  for (size_t N : rows) asmk_update_sites(N, (N + 4095) / 4096);
   for (size_t nc : rows) sift_site(nc);
   for (size_t nc : Ns) sift_site(nc);
   const size_t splits[] = {2, 3, 64, 256}, ms[] = {1, 5, 8};

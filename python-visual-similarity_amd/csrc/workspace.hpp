@@ -38,7 +38,9 @@ namespace pvs {
 //   WS_VERIFY_POINTS, WS_VERIFY_SMALL    match.hip: pvs_verify_dev
 //   WS_IVF_CANDIDATES ivf.hip: pvs_ivf_scan_topk_dev (candidate scores | candidate ids of one query block)
 //   WS_UPDATE         update.hip: pvs_keep_positions_dev (scan partials), pvs_compact_rows_dev in place (staging rows of one window),
-//                     pvs_ivf_insert_dev (source of every merged row), pvs_ivf_remove_dev (stored keep mask | positions | scan partials)
+//                     pvs_ivf_insert_dev (source of every merged row), pvs_ivf_remove_dev (stored keep mask | positions | scan partials);
+//                     asmk_update.hip: pvs_asmk_invert_dev (two item arrays | digit counts | scan partials), pvs_asmk_remove_dev
+//                     (survivor flags, scanned in place | scan partials)
 enum WsSlot : int {
   WS_STAGE_IN = 0, WS_SCRATCH = 1, WS_PANEL_OUT = 2, WS_PROJECTED = 3, WS_AUX_ROWS = 4, WS_FP16_ROWS = 5, WS_LISTS = 6, WS_NB_NORMS = 7,
   WS_NB_F64_ROWS = 8, WS_DSIFT_TABLE = 9, WS_SIFT_PYRAMID = 10, WS_SIFT_TABLES = 11, WS_SIFT_KEYPOINTS = 12, WS_MATCH_TABLE = 13,
@@ -177,6 +179,28 @@ struct IvfRemoveLayout {
 inline IvfRemoveLayout ivf_remove_layout(size_t n, size_t ntiles, size_t tile) {
   WsLayout<> l;
   return {l.add<uint8_t>(n), l.add<int64_t>(n + 1), l.add<int64_t>(ntiles), l.add<int64_t>(tile), l.add<int64_t>(1), l.bytes()};
+}
+
+// pvs_asmk_invert_dev, WS_UPDATE: the (key, source slot) items of the radix sort in two arrays that the passes swap, the digit counts
+// [257][ntiles] that one scan turns into positions, and that scan's partials (one per scan block of the counts)
+struct AsmkInvertLayout {
+  WsPiece<uint64_t> items_a, items_b;
+  WsPiece<int32_t> counts, partials;
+  size_t bytes;
+};
+inline AsmkInvertLayout asmk_invert_layout(size_t total, size_t ncounts, size_t nscanblocks) {
+  WsLayout<> l;
+  return {l.add<uint64_t>(total), l.add<uint64_t>(total), l.add<int32_t>(ncounts), l.add<int32_t>(nscanblocks), l.bytes()};
+}
+
+// pvs_asmk_remove_dev, WS_UPDATE: one survivor flag per stored entry and one more slot for the total, scanned in place, and the scan's partials
+struct AsmkRemoveLayout {
+  WsPiece<int32_t> spos, partials;
+  size_t bytes;
+};
+inline AsmkRemoveLayout asmk_remove_layout(size_t entries, size_t nscanblocks) {
+  WsLayout<> l;
+  return {l.add<int32_t>(entries + 1), l.add<int32_t>(nscanblocks), l.bytes()};
 }
 
 // pvs_kmeans_topm_dev with splits > 1, WS_LISTS: the partial lists [row][split][m], indices then values

@@ -12,8 +12,16 @@ the words two images share.  It searches a database by the local descriptors the
     ranked = eval.rerank_spatial(query_image, hits, local, SpatialVerifier())
 
 Two device kernels (csrc/asmk.hip) do the work: the aggregation of a batch of images into entries, and the scan of the inverted file
-into a score panel that `pvs_topk_dev` ranks.  The inversion (a stable sort on words) and the integer weights are made on the host,
-at build time only, in float64 as include/pvsim.h defines them; tests/asmk_numpy.py restates every value."""
+into a score panel that `pvs_topk_dev` ranks.  The inversion (a stable sort on words) is made on the host by default and on the
+device with `build(..., on_device=True)` (csrc/asmk_update.hip); the integer weights are made on the host, in float64 as
+include/pvsim.h defines them; tests/asmk_numpy.py restates every value.
+
+An index whose weights belong to the vocabulary and not to the indexed set is FROZEN (`build(..., weights=wt)` or `freeze()`), and
+a frozen index takes new images and gives up old ones without a rebuild:
+
+    index.freeze()
+    local.add(new); index.add(new)                               # `new`: a LocalFeatureIndex of the new images
+    local.remove(paths); index.remove(paths)"""
 from __future__ import annotations
 
 import math
@@ -69,13 +77,26 @@ def _weight_sums(ent_off, words, wt) -> np.ndarray:
     return s
 
 
-def gammas(ent_off, words, wt) -> np.ndarray:
-    """float32 (n,): 1 / sqrt(sum of 1023 wt[w] over the image's entries), 0 for an image without (weighted) entries."""
-    s = _weight_sums(ent_off, words, wt)
+def _gammas_of_sums(s) -> np.ndarray:
     g = np.zeros(len(s), np.float32)
     nz = s > 0
     g[nz] = (1.0 / np.sqrt(s[nz].astype(np.float64))).astype(np.float32)
     return g
+
+
+def gammas(ent_off, words, wt) -> np.ndarray:
+    """float32 (n,): 1 / sqrt(sum of 1023 wt[w] over the image's entries), 0 for an image without (weighted) entries."""
+    return _gammas_of_sums(_weight_sums(ent_off, words, wt))
+
+
+def check_weights(weights, K: int) -> np.ndarray:
+    """`weights=` of build: an integer array (K,) with every value in 0..1023 -> int32 (K,); anything else is a ValueError"""
+    w = np.asarray(weights)
+    if w.dtype.kind not in "iu" or w.shape != (int(K),):
+        raise ValueError(f"weights must be an integer array of shape ({int(K)},), got {w.dtype} {w.shape}")
+    if w.size and (int(w.min()) < 0 or int(w.max()) > SCALE):
+        raise ValueError(f"every weight must lie in 0..{SCALE}, got {int(w.min())}..{int(w.max())}")
+    return np.ascontiguousarray(w, dtype=np.int32)
 
 
 def random_projection(bits: int, dim: int, random_state=0) -> np.ndarray:
@@ -157,17 +178,49 @@ def invert(ent_off, words, sigs, K):
     return word_off, np.ascontiguousarray(img[order]), np.ascontiguousarray(sigs[order])
 
 
+def device_invert(ctx, tmp, cb, d_rows, offsets, kind, d_proj, bits, img_base=0, tile_entries=0) -> dict:
+    """assign + aggregate + pvs_asmk_invert_dev for a batch whose rows lie at `d_rows`: nothing but K + 1 offsets comes back.
+    -> dict(n, total, word_off (host int64 (K + 1,)), d_word_off, d_img, d_sig (arrays of `total` slots, word_off[K] of them
+    defined), sums(d_wt) -> host int64 (n,) weight sums).  Every buffer belongs to the scratch block `tmp`; tmp.keep() takes one."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    n, total, W, K = len(offsets) - 1, int(offsets[-1]), bits // 32, cb.K
+    d_lab, d_word, d_sig, d_cnt, d_off = tmp(total * 4), tmp(total * 4), tmp(total * 4 * W), tmp(n * 4), tmp.upload(offsets)
+    d_woff, d_img, d_osig = tmp((K + 1) * 8), tmp(total * 4), tmp(total * 4 * W)
+    if total:
+        ctx.kmeans_predict_dev(cb, d_rows, kind, total, d_lab.ptr)
+        ctx.asmk_aggregate_dev(cb, d_rows, kind, d_off.ptr, offsets, n, total, d_lab.ptr, d_proj, bits, d_word.ptr, d_sig.ptr, d_cnt.ptr)
+    ctx.asmk_invert_dev(K, bits, d_off.ptr, offsets, n, d_cnt.ptr, d_word.ptr, d_sig.ptr, img_base, d_woff.ptr, d_img.ptr, d_osig.ptr,
+                        tile_entries)
+
+    def sums(d_wt):
+        if n == 0:
+            return np.zeros(0, np.int64)
+        d_sums = tmp(n * 8)
+        ctx.asmk_weight_sums_dev(K, d_off.ptr, offsets, n, d_cnt.ptr, d_word.ptr, d_wt, d_sums.ptr)
+        return d_sums.download((n,), np.int64)
+
+    return dict(n=n, total=total, word_off=d_woff.download((K + 1,), np.int64), d_word_off=d_woff, d_img=d_img, d_sig=d_osig, sums=sums)
+
+
+_NOT_FROZEN = ("an ASMKIndex whose weights come from the indexed set is immutable: document frequencies, weights and gammas depend on "
+               "the whole set of images -- rebuild it with ASMKIndex.build(local, vocabulary), or hold the weights fixed with "
+               "freeze() or build(..., weights=) and update it in place")
+
+
 # ------------------------------------------------------------------------------------------------ index
 class ASMKIndex:
     """Paths + an inverted file of (image, signature) entries over visual words, resident on the device, searched by
     pvs_asmk_score_dev + pvs_topk_dev.
 
     Build one with `ASMKIndex.build` (a vocabulary you have) or `ASMKIndex.fit` (trains one).  The arrays are uploaded on first use.
-    The index is immutable: `add` and `remove` name a rebuild, because document frequencies, and with them every weight and gamma,
-    change with the set of images."""
+    An index whose weights derive from its own images is immutable: `add` and `remove` name a rebuild, because document
+    frequencies, and with them every weight and gamma, change with the set of images.  A FROZEN index (`freeze()`, or
+    `build(..., weights=wt)`) holds its weights fixed; `add`, `remove` and `del index[path]` then move data on the device, and the
+    result equals `build(<the surviving images in surviving order>, vocabulary, weights=index.wt, ...)` array for array.  After an
+    update or a device build `ent_img`, `ent_sig` and `gamma_db` are downloaded when first read; `word_off` is always on the host."""
 
     def __init__(self, paths, centroids, word_off, ent_img, ent_sig, gamma_db, wt, sel, bits, alpha=3.0, tau=0.0, idf=True,
-                 projection=None, desc_kind=DESC_U8_ROOTSIFT, ctx=None, extractor=None):
+                 projection=None, desc_kind=DESC_U8_ROOTSIFT, ctx=None, extractor=None, frozen=False):
         self._paths = list(paths)
         self.centroids = _centroids(centroids)
         K, D = self.centroids.shape
@@ -176,36 +229,85 @@ class ASMKIndex:
             raise ValueError(f"bits must be 32, 64, 96 or 128, got {bits!r}")
         W = self.bits // 32
         self.word_off = np.ascontiguousarray(word_off, dtype=np.int64)
-        self.ent_img = np.ascontiguousarray(ent_img, dtype=np.int32)
-        self.ent_sig = np.ascontiguousarray(ent_sig, dtype=np.uint32).reshape(-1, W)
+        on_device = ent_img is None and ent_sig is None       # _build_on_device: the two arrays are resident, and come from the kernels
+        self.ent_img = None if on_device else np.ascontiguousarray(ent_img, dtype=np.int32)
+        self.ent_sig = None if on_device else np.ascontiguousarray(ent_sig, dtype=np.uint32).reshape(-1, W)
         self.gamma_db = np.ascontiguousarray(gamma_db, dtype=np.float32)
         self.wt = np.ascontiguousarray(wt, dtype=np.int32)
         self.sel = np.ascontiguousarray(sel, dtype=np.int32)
         self.projection = None if projection is None else np.ascontiguousarray(projection, dtype=np.float32)
         _row_dtype(desc_kind)
         self.alpha, self.tau, self.idf, self.desc_kind = float(alpha), float(tau), bool(idf), int(desc_kind)
-        N, E = len(self._paths), len(self.ent_img)
+        N = len(self._paths)
+        E = len(self.ent_img) if not on_device else int(self.word_off[-1]) if self.word_off.size else 0
         if self.word_off.shape != (K + 1,) or self.word_off[0] != 0 or self.word_off[-1] != E or (np.diff(self.word_off) < 0).any():
             raise ValueError("word_off must be K + 1 non-decreasing offsets from 0 to the number of entries")
-        if self.ent_sig.shape[0] != E or self.gamma_db.shape != (N,) or self.wt.shape != (K,) or self.sel.shape != (self.bits + 1,):
+        if (not on_device and self.ent_sig.shape[0] != E) or self.gamma_db.shape != (N,) or self.wt.shape != (K,) or self.sel.shape != (self.bits + 1,):
             raise ValueError("the arrays of the index do not fit together")
-        if E and (self.ent_img.min() < 0 or self.ent_img.max() >= N):
+        if E and not on_device and (self.ent_img.min() < 0 or self.ent_img.max() >= N):
             raise ValueError("an entry names an image outside the index")
         if self.projection is None and self.bits != D:
             raise ValueError(f"without a projection bits must equal D = {D}, got {self.bits}")
         if self.projection is not None and self.projection.shape != (self.bits, D):
             raise ValueError(f"the projection must be (bits, D) = {(self.bits, D)}, got {self.projection.shape}")
         self._ctx, self._extractor, self._dev = ctx, extractor, None
+        self._frozen, self._spare, self._cap_e, self._cap_n = bool(frozen), None, 0, 0
+
+    # the three arrays that an update leaves on the device: host copies made when first read
+    def _host(self, name, shape, dtype):
+        a = self.__dict__.get("_h_" + name)
+        if a is None:
+            buf = self._dev[name]
+            a = buf.download(shape, dtype) if int(np.prod(shape)) else np.zeros(shape, dtype)
+            self.__dict__["_h_" + name] = a
+        return a
+
+    @property
+    def ent_img(self) -> np.ndarray:
+        return self._host("ent_img", (int(self.word_off[-1]),), np.int32)
+
+    @ent_img.setter
+    def ent_img(self, a):
+        self.__dict__["_h_ent_img"] = a
+
+    @property
+    def ent_sig(self) -> np.ndarray:
+        return self._host("ent_sig", (int(self.word_off[-1]), self.bits // 32), np.uint32)
+
+    @ent_sig.setter
+    def ent_sig(self, a):
+        self.__dict__["_h_ent_sig"] = a
+
+    @property
+    def gamma_db(self) -> np.ndarray:
+        return self._host("gamma_db", (len(self._paths),), np.float32)
+
+    @gamma_db.setter
+    def gamma_db(self, a):
+        self.__dict__["_h_gamma_db"] = a
+
+    def _stale(self):
+        """the device holds the truth: forget the host copies"""
+        self.ent_img = self.ent_sig = self.gamma_db = None
 
     # -------------------------------------------------------------------------------------------------- construction
     @classmethod
     def build(cls, local, vocabulary, bits: int = 128, alpha: float = 3.0, tau: float = 0.0, idf: bool = True, projection=None,
-              random_state=0, desc_kind=DESC_U8_ROOTSIFT, extractor=None) -> "ASMKIndex":
+              random_state=0, desc_kind=DESC_U8_ROOTSIFT, extractor=None, weights=None, on_device: bool = False) -> "ASMKIndex":
         """Index the images of a `LocalFeatureIndex` against `vocabulary` ((K, D) centroids or a KMeansModel): assign, aggregate,
         download the counts, compact, invert on the host, make the weights, gamma and sel.  `projection`: None (needs bits == D),
-        "random" (a seeded orthonormal matrix) or a (bits, D) array."""
+        "random" (a seeded orthonormal matrix) or a (bits, D) array.
+
+        `weights`: int32 (K,) with every value in 0..1023, e.g. the `wt` of an index over a training corpus.  The index uses them as
+        they are (`idf` is recorded but derives nothing) and is frozen: it can be updated in place.
+        `on_device=True` inverts on the device as well: only the K + 1 offsets and one weight sum per image come back, and the
+        inverted file never leaves the device.  Both routes give the same arrays byte for byte."""
         cent = _centroids(vocabulary)
         K, D = cent.shape
+        if weights is not None:
+            weights = check_weights(weights, K)
+        if not isinstance(on_device, (bool, np.bool_)):
+            raise ValueError(f"on_device must be a bool, got {on_device!r}")
         if desc_kind != DESC_U8_ROOTSIFT:
             raise ValueError("the rows of a LocalFeatureIndex are uint8: only DESC_U8_ROOTSIFT reads them")
         if D != 128:
@@ -224,6 +326,8 @@ class ASMKIndex:
         if int(np.diff(local.offsets).max(initial=0)) > MAX_ROWS:
             raise NotImplementedError(f"an image of more than {MAX_ROWS} rows cannot be indexed")
         ctx = local.ctx
+        if on_device:
+            return cls._build_on_device(local, cent, sel, bits, alpha, tau, idf, projection, desc_kind, ctx, extractor, weights)
         cb = ctx.codebook(cent)
         try:
             with ctx.scratch() as tmp:
@@ -233,9 +337,37 @@ class ASMKIndex:
             cb.close()
         N = len(local)
         word_off, ent_img, ent_sig = invert(ent_off, words, sigs, K)
-        wt = word_weights(np.diff(word_off), N, idf)          # an image holds a word at most once: df = the length of the list
+        # an image holds a word at most once: df = the length of the list
+        wt = word_weights(np.diff(word_off), N, idf) if weights is None else weights
         return cls(local.paths, cent, word_off, ent_img, ent_sig, gammas(ent_off, words, wt), wt, sel, bits, alpha, tau, idf,
-                   projection, desc_kind, ctx, extractor)
+                   projection, desc_kind, ctx, extractor, weights is not None)
+
+    @classmethod
+    def _build_on_device(cls, local, cent, sel, bits, alpha, tau, idf, projection, desc_kind, ctx, extractor, weights):
+        N = len(local)
+        cb = ctx.codebook(cent)
+        dev = {"cb": cb}
+        try:
+            with ctx.scratch() as tmp:
+                d_proj = tmp.upload(projection).ptr if projection is not None else None
+                got = device_invert(ctx, tmp, cb, local.rows.ptr, local.offsets, desc_kind, d_proj, bits)
+                word_off = got["word_off"]
+                wt = word_weights(np.diff(word_off), N, idf) if weights is None else weights
+                dev["wt"] = ctx.buffer(wt.nbytes).upload(wt)
+                gamma = _gammas_of_sums(got["sums"](dev["wt"].ptr))
+                dev["word_off"], dev["ent_img"], dev["ent_sig"] = tmp.keep(got["d_word_off"]), tmp.keep(got["d_img"]), tmp.keep(got["d_sig"])
+            dev["gamma_db"] = ctx.buffer(gamma.nbytes).upload(gamma) if N else ctx.buffer(0)
+            dev["sel"] = ctx.buffer(sel.nbytes).upload(sel)
+            dev["projection"] = None if projection is None else ctx.buffer(projection.nbytes).upload(projection)
+        except Exception:
+            for b in dev.values():
+                if b is not None:
+                    (b.close if b is cb else b.free)()
+            raise
+        self = cls(local.paths, cent, word_off, None, None, gamma, wt, sel, bits, alpha, tau, idf, projection, desc_kind, ctx, extractor,
+                   weights is not None)
+        self._dev, self._cap_e, self._cap_n = dev, got["total"], N
+        return self
 
     @classmethod
     def fit(cls, local, n_words: int, train_rows: int | None = None, random_state=0, max_iter: int = 20, **build_kwargs) -> "ASMKIndex":
@@ -293,13 +425,189 @@ class ASMKIndex:
             self._extractor = KeypointRootSIFT(nfeatures=2000, ctx=self._ctx)
         return self._extractor
 
-    def add(self, *args, **kwargs):
-        raise NotImplementedError("an ASMKIndex is immutable: document frequencies, weights and gammas depend on the whole set of "
-                                  "images -- rebuild it with ASMKIndex.build(local, vocabulary)")
+    # -------------------------------------------------------------------------------------------------- frozen weights and updates
+    @property
+    def frozen(self) -> bool:
+        """True when `wt` is a property of the vocabulary, not of the indexed set: the index can be updated in place."""
+        return self._frozen
 
-    def remove(self, *args, **kwargs):
-        raise NotImplementedError("an ASMKIndex is immutable: document frequencies, weights and gammas depend on the whole set of "
-                                  "images -- rebuild it with ASMKIndex.build(local, vocabulary)")
+    def freeze(self, unseen_weight: int = 0) -> "ASMKIndex":
+        """Declare the weights fixed from now on, so that `add` and `remove` work; returns self.
+
+        `unseen_weight`, an integer in 0..1023, is given to the words whose weight is 0 at this moment: the words no image held.
+        The default 0 changes no bit of any score or ranking.  A non-zero value changes gamma(Q) of the queries that hold such
+        words (their scores against every image scale down), and lets images added later match on them; with 0 such words stay
+        silent in later adds: their entries are stored, but weigh nothing."""
+        if isinstance(unseen_weight, (bool, np.bool_)) or not isinstance(unseen_weight, (int, np.integer)) or not (0 <= unseen_weight <= SCALE):
+            raise ValueError(f"unseen_weight must be an integer in 0..{SCALE}, got {unseen_weight!r}")
+        if unseen_weight and (self.wt == 0).any():
+            self.wt = np.where(self.wt == 0, np.int32(unseen_weight), self.wt).astype(np.int32)
+            if self._dev is not None:
+                self._dev["wt"].upload(self.wt)
+        self._frozen = True
+        return self
+
+    def _new_batch(self, source, rows_list):
+        """the arguments of add -> (paths, offsets, LocalFeatureIndex or None, host rows or None), checked, before any device work"""
+        if hasattr(source, "offsets") and hasattr(source, "rows") and rows_list is None:
+            if self.desc_kind != DESC_U8_ROOTSIFT:
+                raise ValueError("the rows of a LocalFeatureIndex are uint8: only DESC_U8_ROOTSIFT reads them")
+            paths, off, rows = list(source.paths), np.ascontiguousarray(source.offsets, dtype=np.int64), None
+        else:
+            if rows_list is None:
+                raise ValueError("add takes a LocalFeatureIndex, or paths and one array of rows per path")
+            paths, source = list(source), None
+            D, dt = self.centroids.shape[1], _row_dtype(self.desc_kind)
+            rows_list = [np.ascontiguousarray(r, dtype=dt).reshape(-1, D) for r in rows_list]
+            if len(rows_list) != len(paths):
+                raise ValueError(f"{len(paths)} paths but {len(rows_list)} arrays of rows")
+            off = np.zeros(len(paths) + 1, np.int64)
+            np.cumsum([len(r) for r in rows_list], out=off[1:])
+            rows = np.concatenate(rows_list) if int(off[-1]) else np.zeros((0, D), dt)
+        have = set(self._paths)
+        for p in paths:
+            if p in have:
+                raise ValueError(f"{p!r} is already in the index (or named twice)")
+            have.add(p)
+        if int(np.diff(off).max(initial=0)) > MAX_ROWS:
+            raise NotImplementedError(f"an image of more than {MAX_ROWS} rows cannot be indexed")
+        return paths, off, source, rows
+
+    def _file_buffers(self, cap):
+        ctx, W = self.ctx, self.bits // 32
+        return {"word_off": ctx.buffer((self.n_words + 1) * 8), "ent_img": ctx.buffer(cap * 4), "ent_sig": ctx.buffer(cap * 4 * W), "cap": cap}
+
+    def _other(self, need):
+        """the buffers an out-of-place update writes: the spare set, replaced by a larger one when `need` entries do not fit"""
+        sp, self._spare = self._spare, None
+        if sp is None or sp["cap"] < need:
+            if sp is not None:
+                for name in ("word_off", "ent_img", "ent_sig"):
+                    sp[name].free()
+            sp = self._file_buffers(max(need, 2 * self._cap_e if need > self._cap_e else self._cap_e, 1))
+        return sp
+
+    def _swap(self, out):
+        """`out` becomes the file, the file becomes the spare"""
+        dev = self._dev
+        self._spare = {"word_off": dev["word_off"], "ent_img": dev["ent_img"], "ent_sig": dev["ent_sig"], "cap": self._cap_e}
+        dev["word_off"], dev["ent_img"], dev["ent_sig"], self._cap_e = out["word_off"], out["ent_img"], out["ent_sig"], out["cap"]
+
+    def _ensure_capacity(self):
+        """after the first upload the buffers hold exactly what the host arrays held"""
+        if self._cap_e == 0 and self._cap_n == 0:
+            self._cap_e, self._cap_n = int(self.word_off[-1]), len(self._paths)
+
+    def reserve(self, entries: int) -> "ASMKIndex":
+        """Make room for `entries` entries in the inverted file, so that adds up to that size allocate nothing; returns self."""
+        if isinstance(entries, (bool, np.bool_)) or not isinstance(entries, (int, np.integer)) or entries < 0:
+            raise ValueError(f"entries must be a non-negative integer, got {entries!r}")
+        if entries >= 1 << 31:
+            raise NotImplementedError("list maintenance serves fewer than 2^31 entries")
+        dev = self._resident()
+        E = int(self.word_off[-1])
+        if entries > self._cap_e:
+            ctx, W = self.ctx, self.bits // 32
+            out = self._file_buffers(int(entries))
+            ctx.copy_dev(out["word_off"].ptr, dev["word_off"].ptr, (self.n_words + 1) * 8)
+            ctx.copy_dev(out["ent_img"].ptr, dev["ent_img"].ptr, E * 4)
+            ctx.copy_dev(out["ent_sig"].ptr, dev["ent_sig"].ptr, E * 4 * W)
+            self._swap(out)
+            sp, self._spare = self._spare, None
+            for name in ("word_off", "ent_img", "ent_sig"):
+                sp[name].free()
+        return self
+
+    def add(self, source=None, rows_list=None, *args, **kwargs):
+        """Append images: `add(local)` with a LocalFeatureIndex reads its resident rows in place and takes its paths;
+        `add(paths, rows_list)` takes one host array of rows per path (uint8 for DESC_U8_ROOTSIFT).  The new images get the ids
+        N, N + 1, ...; a path the index already holds is a ValueError before anything changes; an empty batch is a no-op.
+        NotImplementedError on an index that is not frozen (see `freeze`)."""
+        if not self._frozen:
+            raise NotImplementedError(_NOT_FROZEN)
+        if args or kwargs:
+            raise TypeError("add takes a LocalFeatureIndex, or paths and rows_list")
+        paths, off, local, rows = self._new_batch(source, rows_list)
+        n = len(paths)
+        if n == 0:
+            return self
+        ctx, dev = self.ctx, self._resident()
+        K, N, E = self.n_words, len(self._paths), int(self.word_off[-1])
+        with ctx.scratch() as tmp:
+            d_rows = local.rows.ptr if local is not None else tmp.upload(rows).ptr
+            d_proj = dev["projection"].ptr if dev["projection"] is not None else None
+            got = device_invert(ctx, tmp, dev["cb"], d_rows, off, self.desc_kind, d_proj, self.bits, img_base=N)
+            new_off = got["word_off"]
+            b = int(new_off[-1])
+            if E + b >= 1 << 31:
+                raise NotImplementedError("list maintenance serves fewer than 2^31 entries")
+            gamma_new = _gammas_of_sums(got["sums"](dev["wt"].ptr))
+            out = self._other(E + b)
+            try:
+                ctx.asmk_insert_dev(K, self.bits, dev["word_off"].ptr, self.word_off, dev["ent_img"].ptr, dev["ent_sig"].ptr,
+                                    got["d_word_off"].ptr, new_off, got["d_img"].ptr, got["d_sig"].ptr, out["word_off"].ptr,
+                                    out["ent_img"].ptr, out["ent_sig"].ptr)
+            except Exception:
+                self._spare = out
+                raise
+            if N + n > self._cap_n:
+                cap = max(N + n, 2 * self._cap_n)
+                g = ctx.buffer(cap * 4)
+                ctx.copy_dev(g.ptr, dev["gamma_db"].ptr, N * 4)
+                dev["gamma_db"].free()
+                dev["gamma_db"], self._cap_n = g, cap
+            dev["gamma_db"].upload(gamma_new, N * 4)
+            ctx.sync()                                        # the batch's buffers go back to the pool with the block
+        self._swap(out)
+        self.word_off = self.word_off + new_off
+        self._paths = self._paths + paths
+        self._stale()
+        return self
+
+    def remove(self, paths=None, *args, **kwargs):
+        """Drop the named images; the survivors keep their order and are renumbered 0 .. N' - 1.  An unknown path is a KeyError, a
+        path named twice a ValueError, both before anything changes; an empty list is a no-op.  NotImplementedError on an index
+        that is not frozen (see `freeze`)."""
+        if not self._frozen:
+            raise NotImplementedError(_NOT_FROZEN)
+        if args or kwargs:
+            raise TypeError("remove takes a list of paths")
+        paths = list(paths if paths is not None else [])
+        where = {p: i for i, p in enumerate(self._paths)}
+        gone = []
+        for p in paths:
+            if p not in where:
+                raise KeyError(p)
+            gone.append(where[p])
+        if len(set(gone)) != len(gone):
+            raise ValueError("a path is named twice")
+        if not gone:
+            return self
+        ctx, dev = self.ctx, self._resident()
+        K, N, E = self.n_words, len(self._paths), int(self.word_off[-1])
+        removed = np.sort(np.array(gone, np.int64))
+        out = self._other(E)
+        with ctx.scratch() as tmp:
+            d_removed, d_keep, d_pos = tmp.upload(removed), tmp(N), tmp((N + 1) * 8)
+            ctx.keep_mask_dev(d_removed.ptr, len(removed), N, d_keep.ptr)
+            ctx.keep_positions_dev(d_keep.ptr, N, d_pos.ptr)
+            try:
+                ctx.asmk_remove_dev(K, self.bits, N, dev["word_off"].ptr, self.word_off, dev["ent_img"].ptr, dev["ent_sig"].ptr, d_keep.ptr,
+                                    d_pos.ptr, out["word_off"].ptr, out["ent_img"].ptr, out["ent_sig"].ptr)
+            except Exception:
+                self._spare = out
+                raise
+            ctx.compact_rows_dev(dev["gamma_db"].ptr, N, 4, d_keep.ptr, d_pos.ptr, dev["gamma_db"].ptr, first=int(removed[0]))
+            word_off = out["word_off"].download((K + 1,), np.int64)
+        self._swap(out)
+        self.word_off = word_off
+        dead = set(gone)
+        self._paths = [p for i, p in enumerate(self._paths) if i not in dead]
+        self._stale()
+        return self
+
+    def __delitem__(self, path):
+        self.remove([path])
 
     def _resident(self) -> dict:
         if self._dev is None:
@@ -309,15 +617,22 @@ class ASMKIndex:
                 a = getattr(self, name)
                 dev[name] = None if a is None else ctx.buffer(a.nbytes).upload(a) if a.nbytes else ctx.buffer(0)
             self._dev = dev
+        self._ensure_capacity()
         return self._dev
 
     def close(self):
         if self._dev is not None:
+            _ = self.ent_img, self.ent_sig, self.gamma_db    # what only the device holds comes to the host first
             self._dev.pop("cb").close()
             for b in self._dev.values():
                 if b is not None:
                     b.free()
             self._dev = None
+            self._cap_e = self._cap_n = 0
+        if self._spare is not None:
+            for name in ("word_off", "ent_img", "ent_sig"):
+                self._spare[name].free()
+            self._spare = None
 
     def __enter__(self):
         return self
@@ -326,7 +641,7 @@ class ASMKIndex:
         self.close()
 
     def __repr__(self):
-        return (f"ASMKIndex(images={len(self)}, words={self.n_words}, bits={self.bits}, entries={len(self.ent_img)}, "
+        return (f"ASMKIndex(images={len(self)}, words={self.n_words}, bits={self.bits}, entries={int(self.word_off[-1])}, "
                 f"alpha={self.alpha}, tau={self.tau}, idf={self.idf})")
 
     # -------------------------------------------------------------------------------------------------- queries
@@ -416,7 +731,8 @@ class ASMKIndex:
         ints = all(isinstance(p, (int, np.integer)) and not isinstance(p, bool) for p in self._paths)
         arrays = dict(kind=_KIND, paths=np.array(self._paths, dtype=np.int64 if ints else np.str_), centroids=self.centroids,
                       word_off=self.word_off, ent_img=self.ent_img, ent_sig=self.ent_sig, gamma_db=self.gamma_db, wt=self.wt, sel=self.sel,
-                      params=np.array([self.bits, self.alpha, self.tau, float(self.idf), self.desc_kind], np.float64))
+                      params=np.array([self.bits, self.alpha, self.tau, float(self.idf), self.desc_kind], np.float64),
+                      frozen=np.array(self._frozen))
         if self.projection is not None:
             arrays["projection"] = self.projection
         np.savez(path, **arrays)
@@ -430,4 +746,4 @@ class ASMKIndex:
             paths = [int(v) for v in z["paths"]] if z["paths"].dtype.kind in "iu" else [str(v) for v in z["paths"]]
             return cls(paths, z["centroids"], z["word_off"], z["ent_img"], z["ent_sig"], z["gamma_db"], z["wt"], z["sel"], int(p[0]),
                        float(p[1]), float(p[2]), bool(p[3]), z["projection"] if "projection" in z.files else None, int(p[4]), ctx,
-                       extractor)
+                       extractor, bool(z["frozen"]) if "frozen" in z.files else False)

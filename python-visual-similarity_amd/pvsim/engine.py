@@ -575,6 +575,47 @@ class Context:
                                             ptr(d_ent_img), ptr(d_ent_sig), int(N), ptr(d_wt), ptr(d_sel), ptr(d_gamma_q),
                                             ptr(d_gamma_db), int(slice_images), ptr(d_scores), int(ld)))
 
+    # ASMK maintenance
+    def asmk_invert_dev(self, K, bits, d_offsets, h_offsets, n_images, d_ent_count, d_ent_word, d_ent_sig, img_base, d_word_off,
+                        d_out_img, d_out_sig, tile_entries=0):
+        """pvs_asmk_invert_dev: the slots pvs_asmk_aggregate_dev filled -> word_off int64 (K + 1,), and ent_img / ent_sig sorted by
+        (word, image) in arrays sized by the slots; image i carries img_base + i.  h_offsets: host int64 (n_images + 1,)"""
+        h = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        if h.shape != (int(n_images) + 1,):
+            raise ValueError(f"h_offsets must have n_images + 1 = {int(n_images) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_invert_dev(self.handle, int(K), int(bits), ptr(d_offsets), ptr(h), int(n_images), ptr(d_ent_count),
+                                             ptr(d_ent_word), ptr(d_ent_sig), int(img_base), int(tile_entries), ptr(d_word_off),
+                                             ptr(d_out_img), ptr(d_out_sig)))
+
+    def asmk_weight_sums_dev(self, K, d_offsets, h_offsets, n_images, d_ent_count, d_ent_word, d_wt, d_sums):
+        """pvs_asmk_weight_sums_dev: sums int64 (n_images,), the sum of 1023 wt[w] over each image's entries in the same slots"""
+        h = np.ascontiguousarray(h_offsets, dtype=np.int64)
+        if h.shape != (int(n_images) + 1,):
+            raise ValueError(f"h_offsets must have n_images + 1 = {int(n_images) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_weight_sums_dev(self.handle, int(K), ptr(d_offsets), ptr(h), int(n_images), ptr(d_ent_count),
+                                                  ptr(d_ent_word), ptr(d_wt), ptr(d_sums)))
+
+    def asmk_insert_dev(self, K, bits, d_word_off, h_word_off, d_ent_img, d_ent_sig, d_new_off, h_new_off, d_new_img, d_new_sig,
+                        d_out_word_off, d_out_img, d_out_sig):
+        """pvs_asmk_insert_dev: a stored file + an inverted batch of larger ids -> the merged file in distinct buffers.  h_word_off,
+        h_new_off: the host copies of the two offset arrays, int64 (K + 1,)"""
+        h, hn = np.ascontiguousarray(h_word_off, dtype=np.int64), np.ascontiguousarray(h_new_off, dtype=np.int64)
+        if h.shape != (int(K) + 1,) or hn.shape != (int(K) + 1,):
+            raise ValueError(f"h_word_off and h_new_off must have K + 1 = {int(K) + 1} entries, got shapes {h.shape}, {hn.shape}")
+        check(_ffi.lib().pvs_asmk_insert_dev(self.handle, int(K), int(bits), ptr(d_word_off), ptr(h), ptr(d_ent_img), ptr(d_ent_sig),
+                                             ptr(d_new_off), ptr(hn), ptr(d_new_img), ptr(d_new_sig), ptr(d_out_word_off), ptr(d_out_img),
+                                             ptr(d_out_sig)))
+
+    def asmk_remove_dev(self, K, bits, N, d_word_off, h_word_off, d_ent_img, d_ent_sig, d_keep, d_pos, d_out_word_off, d_out_img,
+                        d_out_sig):
+        """pvs_asmk_remove_dev: keep uint8 (N,) and pos int64 (N + 1,) by image id -> the surviving entries, renumbered, in distinct
+        buffers.  h_word_off: the host copy of the offsets, int64 (K + 1,)"""
+        h = np.ascontiguousarray(h_word_off, dtype=np.int64)
+        if h.shape != (int(K) + 1,):
+            raise ValueError(f"h_word_off must have K + 1 = {int(K) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_remove_dev(self.handle, int(K), int(bits), int(N), ptr(d_word_off), ptr(h), ptr(d_ent_img),
+                                             ptr(d_ent_sig), ptr(d_keep), ptr(d_pos), ptr(d_out_word_off), ptr(d_out_img), ptr(d_out_sig)))
+
     # index maintenance (DESIGN.md section 15)
     SCAN_TILE = _ffi.SCAN_TILE
 

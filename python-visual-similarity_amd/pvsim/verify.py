@@ -180,6 +180,88 @@ class LocalFeatureIndex:
         i = self._pos[path]
         return self.host_frames()[int(self.offsets[i]):int(self.offsets[i + 1])]
 
+    # -------------------------------------------------------------------------------------------------- updates
+    def add(self, other, rows_list=None, frames_list=None) -> "LocalFeatureIndex":
+        """Append images: `add(other)` with a LocalFeatureIndex copies its rows and frames on the device and takes its paths;
+        `add(paths, rows_list, frames_list)` takes host arrays as `from_arrays` does.  A path the index already holds is a
+        ValueError before anything changes; an empty batch is a no-op.  Together with an ASMKIndex: `local.add(new); asmk.add(new)`."""
+        if isinstance(other, LocalFeatureIndex):
+            if rows_list is not None or frames_list is not None:
+                raise ValueError("add takes a LocalFeatureIndex alone, or paths with rows_list and frames_list")
+            paths, off, host = list(other.paths), other.offsets, None
+        else:
+            if rows_list is None or frames_list is None:
+                raise ValueError("add takes a LocalFeatureIndex alone, or paths with rows_list and frames_list")
+            paths = list(other)
+            rows_list = [_u8_rows("rows", r) for r in rows_list]
+            frames_list = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, 6) for f in frames_list]
+            if len(rows_list) != len(frames_list) or any(len(r) != len(f) for r, f in zip(rows_list, frames_list)):
+                raise ValueError("rows and frames must pair up image by image and row by row")
+            if len(rows_list) != len(paths):
+                raise ValueError(f"{len(paths)} paths but {len(rows_list)} arrays of rows")
+            off = np.zeros(len(paths) + 1, np.int64)
+            np.cumsum([len(r) for r in rows_list], out=off[1:])
+            host = (rows_list, frames_list)
+        have = set(self.paths)
+        for p in paths:
+            if p in have:
+                raise ValueError(f"{p!r} is already in the index (or named twice)")
+            have.add(p)
+        if not paths:
+            return self
+        ctx, total, more = self.ctx, self.total_rows, int(off[-1])
+        if more:
+            rows, frames = ctx.buffer((total + more) * 128), ctx.buffer((total + more) * 24)
+            ctx.copy_dev(rows.ptr, self.rows.ptr, total * 128)
+            ctx.copy_dev(frames.ptr, self.frames.ptr, total * 24)
+            if host is None:
+                ctx.copy_dev(rows.ptr + total * 128, other.rows.ptr, more * 128)
+                ctx.copy_dev(frames.ptr + total * 24, other.frames.ptr, more * 24)
+            else:
+                rows.upload(np.concatenate(host[0]), total * 128)
+                frames.upload(np.concatenate(host[1]), total * 24)
+            ctx.sync()
+            self.rows.free()
+            self.frames.free()
+            self.rows, self.frames = rows, frames
+        self.offsets = np.concatenate([self.offsets, total + np.asarray(off[1:], np.int64)])
+        self.paths = self.paths + paths
+        self._pos = {p: i for i, p in enumerate(self.paths)}
+        self._host_frames = None
+        return self
+
+    def remove(self, paths) -> "LocalFeatureIndex":
+        """Drop the named images; the survivors keep their order.  Rows and frames are compacted in place on the device.  An unknown
+        path is a KeyError, a path named twice a ValueError, both before anything changes; an empty list is a no-op."""
+        gone = []
+        for p in list(paths):
+            if p not in self._pos:
+                raise KeyError(p)
+            gone.append(self._pos[p])
+        if len(set(gone)) != len(gone):
+            raise ValueError("a path is named twice")
+        if not gone:
+            return self
+        gone = sorted(gone)
+        ctx, total, off = self.ctx, self.total_rows, self.offsets
+        removed = np.concatenate([np.arange(off[i], off[i + 1], dtype=np.int64) for i in gone])
+        if len(removed):
+            with ctx.scratch() as tmp:
+                d_removed, d_keep, d_pos = tmp.upload(removed), tmp(total), tmp((total + 1) * 8)
+                ctx.keep_mask_dev(d_removed.ptr, len(removed), total, d_keep.ptr)
+                ctx.keep_positions_dev(d_keep.ptr, total, d_pos.ptr)
+                ctx.compact_rows_dev(self.rows.ptr, total, 128, d_keep.ptr, d_pos.ptr, self.rows.ptr, first=int(removed[0]))
+                ctx.compact_rows_dev(self.frames.ptr, total, 24, d_keep.ptr, d_pos.ptr, self.frames.ptr, first=int(removed[0]))
+                ctx.sync()
+        dead = set(gone)
+        counts = [int(off[i + 1] - off[i]) for i in range(len(self.paths)) if i not in dead]
+        self.paths = [p for i, p in enumerate(self.paths) if i not in dead]
+        self.offsets = np.zeros(len(self.paths) + 1, np.int64)
+        np.cumsum(counts, out=self.offsets[1:])
+        self._pos = {p: i for i, p in enumerate(self.paths)}
+        self._host_frames = None
+        return self
+
     def close(self):
         for b in (self.rows, self.frames):
             if b is not None:
