@@ -766,6 +766,61 @@ int pvs_asmk_remove_dev(pvs_ctx* ctx, int K, int bits, int64_t N, const int64_t*
                         const int32_t* d_ent_img, const uint32_t* d_ent_sig, const uint8_t* d_keep, const int64_t* d_pos,
                         int64_t* d_out_word_off, int32_t* d_out_img, uint32_t* d_out_sig);
 
+/* ---------------------------------------------------------------- ASMK query expansion: majority-vote signatures and new words
+ * Query expansion on the entries themselves (Tolias, Jegou, "Visual query expansion with or without geometry: refining local
+ * descriptors by feature aggregation", Pattern Recognition 2014): the signatures of the query's words are refined by the signatures
+ * that reliable results, the MEMBERS, store for the same words, and words that enough members agree on are added.  The members'
+ * entries are read out of the word-major file: every list is sorted by image, so "does member i hold word w, and with which
+ * signature" is one binary search.  All arithmetic is integer; nothing depends on any order of summation.
+ *
+ * INPUTS per query q: its entries as pvs_asmk_score_dev takes them (words strictly ascending, signatures q_w);
+ *   members[q][0 .. R)  int32 image ids in [0, N), strictly ascending, then -1 padding up to R (0 <= R <= 32): the members are the
+ *                       ids before the first negative value;
+ *   votes[q][0 .. R)    int32 in 1..1023, votes[q][r] belongs to members[q][r];
+ * and, shared by the call, query_vote in 0..65535, h_max in 0..B, min_support in 0..33.
+ *
+ * DEFINITION.  For each word w in [0, K), ascending: M(w) is the set of members r whose id stands in list w, s_r the signature
+ * stored there.
+ *   w is a query word with signature q_w:
+ *     the voters are the members r in M(w) with popcount(s_r xor q_w) <= h_max: the gate always uses the ORIGINAL query signature;
+ *     for each bit t: tally[t] = query_vote (2 q_w[t] - 1) + sum over the voters of votes[r] (2 s_r[t] - 1), in int32
+ *     (|tally| <= 65535 + 32 * 1023);
+ *     the new bit is 1 if tally > 0, 0 if tally < 0 and q_w[t] if tally = 0;
+ *     w is always an output entry.
+ *   w is not a query word:
+ *     w is an output entry iff min_support >= 1 and |M(w)| >= min_support;
+ *     the tally runs over all of M(w), with no gate and no query term;
+ *     the bit is 1 iff tally >= 0: the z >= 0 rule of the signatures.
+ * Query words outside [0, K) are dropped from the output (the score skips them anyway).
+ *
+ * OUTPUT per query: the entries ascending by word; count, the true number of entries; sum, the int64 sum of 1023 wt[w] over the
+ * output entries (what gamma(Q) and the caller's 2^32 check need).  With R = 0 the output equals the query's in-range entries;
+ * with min_support = 0 no word is added. */
+/* Query block as for the score: nq, HOST h_q_off int64 [nq + 1], d_q_word, d_q_sig, bits.  File: K, d_word_off, d_ent_img,
+ * d_ent_sig, N < 2^31.  d_members and d_votes int32 [nq][R] (may be NULL at R = 0).  d_wt int32 [K].
+ * Outputs: d_out_word int32 [nq][cap], d_out_sig uint32 [nq][cap][bits / 32], d_out_count int32 [nq], d_out_sum int64 [nq].
+ * CAPACITY: count and sum are always the true values; output entry j of query q goes to position j of its row iff j < cap; nothing
+ * at or beyond min(count, cap) of a row is touched.  cap = min(K, |Q| + R * 8192) always suffices (an image holds at most 8192
+ * entries); cap = 0 gives counts and sums alone (the two output arrays may then be NULL).
+ * DETERMINISM: a wave owns 64 consecutive words of one query, a workgroup a tile of tile_words words.  tile_words = 0 leaves the cut
+ * to the host (about eight workgroups per compute unit over the query block); other values are a multiple of 64 in 64..4096 --
+ * every value gives the same bytes, since the position of an entry comes from a count per 64 words and one scan per query.  No
+ * output position is decided by an atomic (the kernels hold none), no workgroup waits for another, every written element is
+ * written once.
+ * CHECKS on the host, PVS_ERR_INVALID: bits, K, N, R, query_vote, h_max, min_support, tile_words, cap < 0, decreasing offsets,
+ * NULL arrays, and the alignment of pvs_asmk_score_dev (signature arrays, d_out_sig included: 16 bytes at bits = 128, 8 at 64, 4
+ * otherwise).  BROKEN PRECONDITIONS on the device side: a member id >= N stands in no list, so it is never in M(w) and changes
+ * nothing; a member list that does not ascend strictly (before its padding) gives unspecified members of M(w), but count, sum and
+ * positions stay consistent with each other and no read or write leaves its array; votes outside 1..1023 are used as they are.
+ * The query offsets travel as kernel arguments, 128 queries per launch: more queries mean more launches (three per 128 queries:
+ * mark, scan, emit), all enqueued by the one call.  Uses the workspace (256 + 8 bytes per 64 words and query of a block, 34 MB at
+ * K = 65536 and 128 queries).  Enqueues on the context's stream and never waits for it.  Timed on slot 6. */
+int pvs_asmk_expand_dev(pvs_ctx* ctx, int64_t nq, const int64_t* h_q_off, const int32_t* d_q_word, const uint32_t* d_q_sig, int bits,
+                        int K, const int64_t* d_word_off, const int32_t* d_ent_img, const uint32_t* d_ent_sig, int64_t N, int R,
+                        const int32_t* d_members, const int32_t* d_votes, int query_vote, int h_max, int min_support,
+                        const int32_t* d_wt, int tile_words, int cap, int32_t* d_out_word, uint32_t* d_out_sig,
+                        int32_t* d_out_count, int64_t* d_out_sum);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

@@ -145,6 +145,14 @@ static void asmk_update_sites(size_t total, size_t ntiles) {
         "ASMK remove block entries=%zu", total);
 }
 
+// the block of the ASMK query expansion (asmk_expand.hip): hit masks of every word, then chunk counts and chunk weight sums
+static void asmk_expand_site(size_t queries, size_t nchunks) {
+  const AsmkExpandLayout e = asmk_expand_layout(queries, nchunks);
+  const size_t mask_b = al(queries * nchunks * 64 * 4), small_b = al(queries * nchunks * 4);
+  CHECK(e.mask.off == 0 && e.cnt.off == mask_b && e.wsum.off == mask_b + small_b && e.bytes == mask_b + 2 * small_b,
+        "ASMK expansion block queries=%zu chunks=%zu", queries, nchunks);
+}
+
 int main() {
   generic_align<256>();
   generic_align<16>();
@@ -171,6 +179,8 @@ int main() {
   for (size_t N : rows) update_sites(N, 64);
   for (size_t N : Ns) asmk_update_sites(N, (N + 255) / 256);
   for (size_t N : rows) asmk_update_sites(N, (N + 4095) / 4096);
+  for (size_t nq : {(size_t)1, (size_t)3, (size_t)128})
+    for (size_t nchunks : {(size_t)1, (size_t)5, (size_t)1024}) asmk_expand_site(nq, nchunks);
   for (size_t nc : rows) sift_site(nc);
   for (size_t nc : Ns) sift_site(nc);
   const size_t splits[] = {2, 3, 64, 256}, ms[] = {1, 5, 8};

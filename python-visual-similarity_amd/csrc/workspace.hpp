@@ -40,7 +40,8 @@ namespace pvs {
 //   WS_UPDATE         update.hip: pvs_keep_positions_dev (scan partials), pvs_compact_rows_dev in place (staging rows of one window),
 //                     pvs_ivf_insert_dev (source of every merged row), pvs_ivf_remove_dev (stored keep mask | positions | scan partials);
 //                     asmk_update.hip: pvs_asmk_invert_dev (two item arrays | digit counts | scan partials), pvs_asmk_remove_dev
-//                     (survivor flags, scanned in place | scan partials)
+//                     (survivor flags, scanned in place | scan partials); asmk_expand.hip: pvs_asmk_expand_dev (hit masks | chunk counts |
+//                     chunk weight sums of one query block)
 enum WsSlot : int {
   WS_STAGE_IN = 0, WS_SCRATCH = 1, WS_PANEL_OUT = 2, WS_PROJECTED = 3, WS_AUX_ROWS = 4, WS_FP16_ROWS = 5, WS_LISTS = 6, WS_NB_NORMS = 7,
   WS_NB_F64_ROWS = 8, WS_DSIFT_TABLE = 9, WS_SIFT_PYRAMID = 10, WS_SIFT_TABLES = 11, WS_SIFT_KEYPOINTS = 12, WS_MATCH_TABLE = 13,
@@ -201,6 +202,18 @@ struct AsmkRemoveLayout {
 inline AsmkRemoveLayout asmk_remove_layout(size_t entries, size_t nscanblocks) {
   WsLayout<> l;
   return {l.add<int32_t>(entries + 1), l.add<int32_t>(nscanblocks), l.bytes()};
+}
+
+// pvs_asmk_expand_dev, WS_UPDATE: for one block of `queries` queries the member hit mask of every word (chunks of 64 words), and per
+// chunk the number of output entries (scanned in place into positions) and their weight sum
+struct AsmkExpandLayout {
+  WsPiece<uint32_t> mask;
+  WsPiece<int32_t> cnt, wsum;
+  size_t bytes;
+};
+inline AsmkExpandLayout asmk_expand_layout(size_t queries, size_t nchunks) {
+  WsLayout<> l;
+  return {l.add<uint32_t>(queries * nchunks * 64), l.add<int32_t>(queries * nchunks), l.add<int32_t>(queries * nchunks), l.bytes()};
 }
 
 // pvs_kmeans_topm_dev with splits > 1, WS_LISTS: the partial lists [row][split][m], indices then values

@@ -9,6 +9,7 @@
     from pvsim import QueryExpansion                   # query expansion / database-side augmentation on a DeviceIndex
     from pvsim import Diffusion                        # diffusion re-ranking on the kNN graph of a DeviceIndex
     from pvsim import ASMKIndex                        # local-descriptor retrieval: ASMK* with binary signatures, an inverted file
+    from pvsim import ASMKExpansion                    # its query expansion: majority-vote signatures and words the results agree on
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -20,8 +21,8 @@ from ._errors import CapacityError
 from .compact import CompactIndex, IVFCompactIndex, ProductQuantizer
 from .expand import QueryExpansion
 from .diffusion import Diffusion
-from .asmk import ASMKIndex
+from .asmk import ASMKExpansion, ASMKIndex
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion", "ASMKIndex"]
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion", "ASMKIndex", "ASMKExpansion"]

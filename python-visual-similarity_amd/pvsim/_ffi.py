@@ -154,6 +154,8 @@ SIGNATURES = {
     "pvs_asmk_weight_sums_dev": [_vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp],
     "pvs_asmk_insert_dev": [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pvs_asmk_remove_dev": [_vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "pvs_asmk_expand_dev": [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _int, _int, _int, _vp, _int, _int,
+                            _vp, _vp, _vp, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

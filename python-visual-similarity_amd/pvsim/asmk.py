@@ -21,7 +21,12 @@ a frozen index takes new images and gives up old ones without a rebuild (DESIGN.
 
     index.freeze()
     local.add(new); index.add(new)                               # `new`: a LocalFeatureIndex of the new images
-    local.remove(paths); index.remove(paths)"""
+    local.remove(paths); index.remove(paths)
+
+Query expansion on the entries (`ASMKExpansion`, csrc/asmk_expand.hip; tests/asmk_expand_numpy.py restates it):
+the best results of a first ranking refine the signatures of the query's words and add the words they agree on, on the device:
+
+    hits = index.retrieve(query_image, k=100, expand=ASMKExpansion(n=10, min_support=2))"""
 from __future__ import annotations
 
 import math
@@ -30,7 +35,7 @@ import numpy as np
 
 from ._ffi import DESC_F32, DESC_F32_ROOTSIFT, DESC_U8_ROOTSIFT
 
-__all__ = ["ASMKIndex", "selectivity", "word_weights", "gammas", "random_projection"]
+__all__ = ["ASMKIndex", "ASMKExpansion", "selectivity", "word_weights", "gammas", "random_projection"]
 
 SCALE = 1023                       # sel[0], and the factor of gamma
 IDF_SCALE = 64                     # wt = rint(64 ln(N / df))
@@ -38,6 +43,10 @@ MAX_ROWS = 8192                    # rows of one image (pvs_asmk_aggregate_dev)
 MAX_MA = 8                         # words per query row (pvs_kmeans_topm_dev)
 MAX_KEYS = 16384                   # rows x words of one query image (pvs_asmk_aggregate_ma_dev)
 PANEL_BYTES = 64 << 20             # score panel of one query block
+MAX_MEMBERS = 32                   # members of one query (pvs_asmk_expand_dev)
+MAX_QUERY_VOTE = 65535
+EXPAND_BYTES = 256 << 20           # expanded entries of one query block
+PAD_BYTE = 0x7F                    # fills the unwritten tail of a row of expanded words: 0x7F7F7F7F is no word, the score skips it
 _KIND = "asmk_index"
 
 
@@ -200,6 +209,95 @@ def device_invert(ctx, tmp, cb, d_rows, offsets, kind, d_proj, bits, img_base=0,
         return d_sums.download((n,), np.int64)
 
     return dict(n=n, total=total, word_off=d_woff.download((K + 1,), np.int64), d_word_off=d_woff, d_img=d_img, d_sig=d_osig, sums=sums)
+
+
+# ------------------------------------------------------------------------------------------------ query expansion
+def _check_int(name, v, lo, hi):
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not (lo <= v <= hi):
+        raise ValueError(f"{name} must be an integer in {lo}..{hi}, got {v!r}")
+    return int(v)
+
+
+class ASMKExpansion:
+    """How `ASMKIndex.rank_*`, `retrieve` and `expand_verified` re-query (Tolias and Jegou, Pattern Recognition
+    2014): the first `n` results of the previous ranking are the members; the signature of every query word becomes the majority
+    vote of the query's own signature (`query_vote` votes) and the signatures the members store for that word within Hamming
+    distance `h_max` of the query's (default bits // 4); a word the query lacks is added when at least `min_support` members hold it
+    (0: no word is added).  `scheme` "flat" gives every member the vote 1 (`query_vote` defaults to 2), "linear" gives the member at
+    rank j the vote n - j (`query_vote` defaults to n).  `passes` > 1 repeats this from the lists of the expanded query; every pass
+    expands the original entries."""
+
+    def __init__(self, n: int = 10, h_max=None, min_support: int = 2, query_vote=None, scheme: str = "flat", passes: int = 1):
+        self.n = _check_int("n", n, 1, MAX_MEMBERS)
+        self.h_max = None if h_max is None else _check_int("h_max", h_max, 0, 128)
+        self.min_support = _check_int("min_support", min_support, 0, MAX_MEMBERS + 1)
+        if scheme not in ("flat", "linear"):
+            raise ValueError(f"scheme must be 'flat' or 'linear', got {scheme!r}")
+        self.scheme = scheme
+        default = 2 if scheme == "flat" else self.n
+        self.query_vote = default if query_vote is None else _check_int("query_vote", query_vote, 0, MAX_QUERY_VOTE)
+        if isinstance(passes, (bool, np.bool_)) or not isinstance(passes, (int, np.integer)) or passes < 1:
+            raise ValueError(f"passes must be an integer >= 1, got {passes!r}")
+        self.passes = int(passes)
+
+    def resolve_h_max(self, bits: int) -> int:
+        """h_max for signatures of `bits` bits: the default is bits // 4; a value above bits is a ValueError"""
+        if self.h_max is None:
+            return int(bits) // 4
+        if self.h_max > bits:
+            raise ValueError(f"h_max = {self.h_max} exceeds the {bits} bits of a signature")
+        return self.h_max
+
+    def members_of(self, idx):
+        """ranked lists idx (nq, >= 0 slots; -1 where a slot is not filled) -> (members int32 (nq, n), votes int32 (nq, n)): the
+        filled slots among the first n, ids ascending with -1 behind them, every vote beside its member"""
+        idx = np.asarray(idx, np.int64)
+        if idx.ndim != 2:
+            raise ValueError("the ranked lists must be a 2-d array")
+        nq, n = idx.shape[0], self.n
+        lists = np.full((nq, n), -1, np.int64)
+        lists[:, :min(n, idx.shape[1])] = idx[:, :n]
+        rank_vote = np.ones(n, np.int64) if self.scheme == "flat" else n - np.arange(n, dtype=np.int64)
+        votes = np.broadcast_to(rank_vote, (nq, n)).copy()
+        for q in range(nq):
+            ids = lists[q][lists[q] >= 0]
+            if len(np.unique(ids)) != len(ids):
+                raise ValueError(f"query {q} names a member twice")
+        key = np.where(lists >= 0, lists, np.iinfo(np.int64).max)
+        order = np.argsort(key, axis=1, kind="stable")
+        members = np.take_along_axis(lists, order, axis=1)
+        votes = np.where(members >= 0, np.take_along_axis(votes, order, axis=1), 0)
+        return np.ascontiguousarray(members, dtype=np.int32), np.ascontiguousarray(votes, dtype=np.int32)
+
+    def __repr__(self):
+        return (f"ASMKExpansion(n={self.n}, h_max={self.h_max}, min_support={self.min_support}, query_vote={self.query_vote}, "
+                f"scheme={self.scheme!r}, passes={self.passes})")
+
+
+def check_expanded_sums(sums, expansion) -> None:
+    """the weight sums of expanded queries (int64, from the device): ValueError where one reaches 2^32"""
+    sums = np.asarray(sums, np.int64)
+    if sums.size and int(sums.max()) >= 1 << 32:
+        raise ValueError(f"the expanded query {int(sums.argmax())} holds entries whose weights sum to 2^32 or more: the integer score "
+                         f"could overflow -- raise min_support (now {expansion.min_support}) or lower n (now {expansion.n}), so that "
+                         "fewer words are added")
+
+
+def _check_members(members, votes, nq, N):
+    """members / votes as the device takes them: int32 (nq, R), ids strictly ascending in [0, N) then -1, votes in 1..1023"""
+    members, votes = np.ascontiguousarray(members, dtype=np.int32), np.ascontiguousarray(votes, dtype=np.int32)
+    if members.ndim != 2 or members.shape != votes.shape or members.shape[0] != nq or members.shape[1] > MAX_MEMBERS:
+        raise ValueError(f"members and votes must both be (nq, R) = ({nq}, R <= {MAX_MEMBERS}), got {members.shape} and {votes.shape}")
+    live = members >= 0
+    if (live[:, 1:] & ~live[:, :-1]).any() or (members < -1).any():
+        raise ValueError("the members of a query come first, -1 padding behind them")
+    if (members >= N).any():
+        raise ValueError(f"a member id is not below the {N} images of the index")
+    if (live[:, 1:] & (members[:, 1:] <= members[:, :-1])).any():
+        raise ValueError("the members of a query must ascend strictly")
+    if ((votes[live] < 1) | (votes[live] > SCALE)).any():
+        raise ValueError(f"every vote must lie in 1..{SCALE}")
+    return members, votes
 
 
 _NOT_FROZEN = ("an ASMKIndex whose weights come from the indexed set is immutable: document frequencies, weights and gammas depend on "
@@ -652,44 +750,179 @@ class ASMKIndex:
         return device_entries(self.ctx, dev["cb"], d_rows, offsets, self.desc_kind,
                               dev["projection"].ptr if dev["projection"] is not None else None, self.bits, ma)
 
-    def rank_entries(self, ent_off, words, sigs, k: int, slice_images: int = 0):
-        """Rank the database for queries given as entries -> (idx int64 (nq, k), val float32 (nq, k)); slots that cannot be filled
-        are idx = -1, val = -inf.  ValueError for a query whose weights could overflow the integer score."""
+    def _query_arrays(self, ent_off, words, sigs):
         ent_off = np.ascontiguousarray(ent_off, dtype=np.int64)
         words = np.ascontiguousarray(words, dtype=np.int32)
-        W = self.bits // 32
-        sigs = np.ascontiguousarray(sigs, dtype=np.uint32).reshape(-1, W)
+        sigs = np.ascontiguousarray(sigs, dtype=np.uint32).reshape(-1, self.bits // 32)
+        return ent_off, words, sigs
+
+    def _rank_dev(self, tmp, d_word, d_sig, h_off, gq, k, slice_images=0):
+        """score + top-k for queries whose entries lie on the device (host offsets `h_off`, host gammas `gq`) -> (idx (nq, k), val
+        (nq, k)) on the host, slots that cannot be filled idx = -1, val = -inf.  N > 0 and nq > 0."""
+        ctx, dev, nq, N = self.ctx, self._resident(), len(h_off) - 1, len(self)
+        idx, val = np.full((nq, k), -1, np.int64), np.full((nq, k), -np.inf, np.float32)
+        kk = min(k, N)
+        qb = int(max(1, min(nq, PANEL_BYTES // (4 * N))))
+        d_gq = tmp.upload(gq)
+        d_panel, d_idx, d_val = tmp(qb * N * 4), tmp(nq * kk * 8), tmp(nq * kk * 4)
+        for q0 in range(0, nq, qb):                     # whole rows of the panel: each block's ranking is final
+            qn = min(qb, nq - q0)
+            ctx.asmk_score_dev(qn, h_off[q0:q0 + qn + 1], d_word.ptr, d_sig.ptr, self.bits, self.n_words, dev["word_off"].ptr,
+                               dev["ent_img"].ptr, dev["ent_sig"].ptr, N, dev["wt"].ptr, dev["sel"].ptr, d_gq.ptr + q0 * 4,
+                               dev["gamma_db"].ptr, d_panel.ptr, N, slice_images)
+            ctx.topk_dev(d_panel.ptr, qn, N, N, kk, 0, 0, d_idx.ptr + q0 * kk * 8, d_val.ptr + q0 * kk * 4)
+        idx[:, :kk] = d_idx.download((nq, kk), np.int64)
+        val[:, :kk] = d_val.download((nq, kk), np.float32)
+        return idx, val
+
+    def _query_sums(self, ent_off, words):
+        sums = _weight_sums(ent_off, words, self.wt)
+        if len(sums) and int(sums.max()) >= 1 << 32:
+            raise ValueError(f"query {int(sums.argmax())} holds entries whose weights sum to 2^32 or more: the integer score could "
+                             "overflow (4104 entries are always safe)")
+        return sums
+
+    def rank_entries(self, ent_off, words, sigs, k: int, slice_images: int = 0, expand=None):
+        """Rank the database for queries given as entries -> (idx int64 (nq, k), val float32 (nq, k)); slots that cannot be filled
+        are idx = -1, val = -inf.  ValueError for a query whose weights could overflow the integer score.
+
+        `expand`: None, or an `ASMKExpansion`: rank to depth n, take the filled slots of each list as members (ids ascending for
+        the device, every vote beside its member), expand the entries (pvs_asmk_expand_dev), rank the expanded queries to depth k.
+        The expanded entries stay on the device between the expansion and the score; only counts, weight sums and ranked lists
+        come to the host.  One host synchronisation per pass is inherent: the score takes its entry offsets and gamma(Q) from the
+        host, and gamma(Q), like the 2^32 guard, needs the weight sum the expansion found."""
+        ent_off, words, sigs = self._query_arrays(ent_off, words, sigs)
         nq, N = len(ent_off) - 1, len(self)
         if isinstance(k, bool) or int(k) != k or k < 1:
             raise ValueError(f"k must be a positive integer, got {k!r}")
         k = int(k)
-        sums = _weight_sums(ent_off, words, self.wt)
-        if nq and int(sums.max()) >= 1 << 32:
-            raise ValueError(f"query {int(sums.argmax())} holds entries whose weights sum to 2^32 or more: the integer score could "
-                             "overflow (4104 entries are always safe)")
-        idx, val = np.full((nq, k), -1, np.int64), np.full((nq, k), -np.inf, np.float32)
+        if expand is not None:
+            return self._rank_expanded(ent_off, words, sigs, k, expand, slice_images)
+        sums = self._query_sums(ent_off, words)
         if nq == 0 or N == 0:
-            return idx, val
-        kk = min(k, N)
-        gq = gammas(ent_off, words, self.wt)
-        ctx, dev = self.ctx, self._resident()
-        qb = int(max(1, min(nq, PANEL_BYTES // (4 * N))))
-        with ctx.scratch() as tmp:
-            d_word, d_sig, d_gq = tmp.upload(words), tmp.upload(sigs), tmp.upload(gq)
-            d_panel, d_idx, d_val = tmp(qb * N * 4), tmp(nq * kk * 8), tmp(nq * kk * 4)
-            for q0 in range(0, nq, qb):                     # whole rows of the panel: each block's ranking is final
-                qn = min(qb, nq - q0)
-                ctx.asmk_score_dev(qn, ent_off[q0:q0 + qn + 1], d_word.ptr, d_sig.ptr, self.bits, self.n_words, dev["word_off"].ptr,
-                                   dev["ent_img"].ptr, dev["ent_sig"].ptr, N, dev["wt"].ptr, dev["sel"].ptr, d_gq.ptr + q0 * 4,
-                                   dev["gamma_db"].ptr, d_panel.ptr, N, slice_images)
-                ctx.topk_dev(d_panel.ptr, qn, N, N, kk, 0, 0, d_idx.ptr + q0 * kk * 8, d_val.ptr + q0 * kk * 4)
-            idx[:, :kk] = d_idx.download((nq, kk), np.int64)
-            val[:, :kk] = d_val.download((nq, kk), np.float32)
+            return np.full((nq, k), -1, np.int64), np.full((nq, k), -np.inf, np.float32)
+        with self.ctx.scratch() as tmp:
+            d_word, d_sig = tmp.upload(words), tmp.upload(sigs)
+            return self._rank_dev(tmp, d_word, d_sig, ent_off, _gammas_of_sums(sums), k, slice_images)
+
+    # -------------------------------------------------------------------------------------------------- query expansion
+    def _expand_cap(self, ent_off, R):
+        """entries one expanded query can hold: its own and at most 8192 per member, never more than the words there are"""
+        longest = int(np.diff(ent_off).max(initial=0))
+        return max(1, min(self.n_words, longest + int(R) * MAX_ROWS))
+
+    def _expand_dev(self, tmp, d_word, d_sig, ent_off, members, votes, expansion, out=None):
+        """one pvs_asmk_expand_dev call and one download of counts and sums.  -> dict(d_word, d_sig: rows of `cap` slots per query
+        over a fill that the score skips; cap; off: the host offsets q * cap of the rows; counts int64 (nq,); sums int64 (nq,))"""
+        if not isinstance(expansion, ASMKExpansion):
+            raise TypeError("expand must be a pvsim.ASMKExpansion")
+        ctx, dev, nq, W = self.ctx, self._resident(), len(ent_off) - 1, self.bits // 32
+        members, votes = _check_members(members, votes, nq, len(self))
+        R, h_max = members.shape[1], expansion.resolve_h_max(self.bits)
+        cap = self._expand_cap(ent_off, R) if out is None else out["cap"]
+        if out is None:
+            out = dict(d_word=tmp(nq * cap * 4), d_sig=tmp(nq * cap * 4 * W), cap=cap)
+        d_cs = tmp(nq * 12)                                    # sums int64 (nq,), then counts int32 (nq,)
+        d_mem, d_vote = tmp.upload(members), tmp.upload(votes)
+        out["d_word"].fill_bytes(PAD_BYTE)
+        ctx.asmk_expand_dev(nq, ent_off, d_word.ptr, d_sig.ptr, self.bits, self.n_words, dev["word_off"].ptr, dev["ent_img"].ptr,
+                            dev["ent_sig"].ptr, len(self), R, d_mem.ptr, d_vote.ptr, expansion.query_vote, h_max,
+                            expansion.min_support, dev["wt"].ptr, cap, out["d_word"].ptr, out["d_sig"].ptr, d_cs.ptr + nq * 8, d_cs.ptr)
+        raw = d_cs.download((nq * 12,), np.uint8)
+        sums, counts = raw[:nq * 8].view(np.int64).copy(), raw[nq * 8:].view(np.int32).astype(np.int64)
+        if int(counts.max(initial=0)) > cap:
+            raise RuntimeError(f"an expanded query holds {int(counts.max())} entries, more than the {cap} that can occur")
+        check_expanded_sums(sums, expansion)
+        return dict(out, off=np.arange(nq + 1, dtype=np.int64) * cap, counts=counts, sums=sums)
+
+    def expand_entries(self, ent_off, words, sigs, members, votes, expansion):
+        """The entries of queries, expanded by the entries the index stores for their members -> (ent_off', words', sigs') on the
+        host, in the layout of `query_entries`.  `members` int32 (nq, R): per query its image ids strictly ascending, -1 behind
+        them; `votes` int32 (nq, R) in 1..1023 (`ASMKExpansion.members_of` makes both from ranked lists).  One device call and
+        one download of counts and sums, then the entries themselves.  ValueError when the weights of an expanded query sum to
+        2^32 or more."""
+        ent_off, words, sigs = self._query_arrays(ent_off, words, sigs)
+        nq, W = len(ent_off) - 1, self.bits // 32
+        if nq == 0:
+            return np.zeros(1, np.int64), np.zeros(0, np.int32), np.zeros((0, W), np.uint32)
+        with self.ctx.scratch() as tmp:
+            x = self._expand_dev(tmp, tmp.upload(words), tmp.upload(sigs), ent_off, members, votes, expansion)
+            cap, counts = x["cap"], x["counts"]
+            keep = np.arange(cap)[None, :] < counts[:, None]
+            out_words = x["d_word"].download((nq, cap), np.int32)[keep]
+            out_sigs = x["d_sig"].download((nq, cap, W), np.uint32)[keep]
+        off = np.zeros(nq + 1, np.int64)
+        np.cumsum(counts, out=off[1:])
+        return off, np.ascontiguousarray(out_words), np.ascontiguousarray(out_sigs)
+
+    def _rank_expanded(self, ent_off, words, sigs, k, expansion, slice_images=0, members=None, votes=None):
+        """rank_entries with an ASMKExpansion.  `members` / `votes`: the members of the first pass where they do not come from a
+        ranking of the plain query (expand_verified)."""
+        if not isinstance(expansion, ASMKExpansion):
+            raise TypeError("expand must be a pvsim.ASMKExpansion")
+        nq, N, W = len(ent_off) - 1, len(self), self.bits // 32
+        sums = self._query_sums(ent_off, words)
+        if nq == 0 or N == 0:
+            return np.full((nq, k), -1, np.int64), np.full((nq, k), -np.inf, np.float32)
+        expansion.resolve_h_max(self.bits)
+        cap = self._expand_cap(ent_off, expansion.n)
+        qb = int(max(1, EXPAND_BYTES // (cap * 4 * (W + 1))))
+        if nq > qb:                                            # blocks of queries whose expanded entries fit the budget
+            parts = []
+            for q0 in range(0, nq, qb):
+                q1, lo, hi = min(q0 + qb, nq), int(ent_off[q0]), int(ent_off[min(q0 + qb, nq)])
+                parts.append(self._rank_expanded(ent_off[q0:q1 + 1] - lo, words[lo:hi], sigs[lo:hi], k, expansion, slice_images,
+                                                 None if members is None else members[q0:q1], None if votes is None else votes[q0:q1]))
+            return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+        n = expansion.n
+        with self.ctx.scratch() as tmp:
+            d_word, d_sig = tmp.upload(words), tmp.upload(sigs)
+            if members is None:
+                with self.ctx.scratch() as first:
+                    idx, _ = self._rank_dev(first, d_word, d_sig, ent_off, _gammas_of_sums(sums), n, slice_images)
+                members, votes = expansion.members_of(idx)
+            out = dict(d_word=tmp(nq * cap * 4), d_sig=tmp(nq * cap * 4 * W), cap=cap)
+            for p in range(expansion.passes):
+                last = p == expansion.passes - 1
+                with self.ctx.scratch() as step:
+                    x = self._expand_dev(step, d_word, d_sig, ent_off, members, votes, expansion, out)
+                    idx, val = self._rank_dev(step, x["d_word"], x["d_sig"], x["off"], _gammas_of_sums(x["sums"]), k if last else n,
+                                              slice_images)
+                if not last:
+                    members, votes = expansion.members_of(idx)
         return idx, val
 
-    def rank_rows(self, rows_list, k: int, ma=1):
+    def expand_verified(self, query_image, ranked, k: int = 100, expand=None, min_inliers: int = 4, ma=1) -> list:
+        """Query expansion over spatially verified results, the analogue of `eval.expand_verified` for this index: `ranked` is what
+        `eval.rerank_spatial` returned, [(path, score, inliers)]; the members are its first `expand.n` paths with at least
+        `min_inliers` inliers (the default expansion is ASMKExpansion()), in that order for the votes of the "linear" scheme; the k
+        best images for the expanded query come back as [(path, score)].  With no verified path there is nothing to expand with:
+        the first k of `ranked`, without the inlier counts.  KeyError for a path the index does not hold."""
+        expand = ASMKExpansion() if expand is None else expand
+        if not isinstance(expand, ASMKExpansion):
+            raise TypeError("expand must be a pvsim.ASMKExpansion")
+        if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or min_inliers < 0:
+            raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers!r}")
+        if isinstance(k, bool) or int(k) != k or k < 1:
+            raise ValueError(f"k must be a positive integer, got {k!r}")
+        ma = check_ma(ma, self.n_words)
+        ranked = list(ranked)
+        verified = [path for path, _, inliers in ranked if inliers >= min_inliers][:expand.n]
+        if not verified or len(self) == 0:
+            return [(path, score) for path, score, _ in ranked[:int(k)]]
+        where = {p: i for i, p in enumerate(self._paths)}
+        for path in verified:
+            if path not in where:
+                raise KeyError(path)
+        members, votes = expand.members_of(np.array([[where[p] for p in verified]], np.int64))
+        ent_off, words, sigs = self._query_arrays(*self._image_entries([query_image], ma))
+        idx, val = self._rank_expanded(ent_off, words, sigs, int(k), expand, members=members, votes=votes)
+        return [(self._paths[int(i)], float(v)) for i, v in zip(idx[0], val[0]) if i >= 0]
+
+    def rank_rows(self, rows_list, k: int, ma=1, expand=None):
         """Rank the database for queries given as host descriptor rows (one (n, D) array per query, uint8 for DESC_U8_ROOTSIFT).
-        `ma`: the nearest words every query row is assigned to (the paper uses 5); the database stays single assignment."""
+        `ma`: the nearest words every query row is assigned to (the paper uses 5); the database stays single assignment.
+        `expand`: None or an `ASMKExpansion` (rank_entries)."""
         ma = check_ma(ma, self.n_words)
         D = self.centroids.shape[1]
         dt = _row_dtype(self.desc_kind)
@@ -703,26 +936,31 @@ class ASMKIndex:
         with self.ctx.scratch() as tmp:
             d_rows = tmp.upload(np.concatenate(rows_list) if total else np.zeros((0, D), dt))
             ent = self.query_entries(d_rows.ptr, off, ma)
-        return self.rank_entries(*ent, k)
+        return self.rank_entries(*ent, k, expand=expand)
 
-    def rank_images(self, images, k: int, ma=1):
-        """Rank the database for query images (arrays or paths), extracted with the index's extractor; `ma` as in rank_rows."""
+    def _image_entries(self, images, ma):
+        """the entries of query images (arrays or paths), extracted with the index's extractor -> (ent_off, words, sigs)"""
         from .verify import LocalFeatureIndex
-        ma = check_ma(ma, self.n_words)
         if self.desc_kind != DESC_U8_ROOTSIFT:
             raise ValueError("images are extracted as uint8 rows: the index must read DESC_U8_ROOTSIFT")
         q = LocalFeatureIndex.from_images(list(images), self.extractor, ctx=self.ctx)
         try:
             if int(np.diff(q.offsets).max(initial=0)) > MAX_ROWS:
                 raise NotImplementedError(f"a query of more than {MAX_ROWS} rows is not supported")
-            ent = self.query_entries(q.rows.ptr, q.offsets, ma)
+            return self.query_entries(q.rows.ptr, q.offsets, ma)
         finally:
             q.close()
-        return self.rank_entries(*ent, k)
 
-    def retrieve(self, query_image, k: int = 100, ma=1) -> list:
-        """-> [(path, score)] best first: the `hits` that eval.rerank_spatial takes.  `ma`: words per query row (rank_rows)."""
-        idx, val = self.rank_images([query_image], k, ma)
+    def rank_images(self, images, k: int, ma=1, expand=None):
+        """Rank the database for query images (arrays or paths), extracted with the index's extractor; `ma` and `expand` as in
+        rank_rows."""
+        ma = check_ma(ma, self.n_words)
+        return self.rank_entries(*self._image_entries(images, ma), k, expand=expand)
+
+    def retrieve(self, query_image, k: int = 100, ma=1, expand=None) -> list:
+        """-> [(path, score)] best first: the `hits` that eval.rerank_spatial takes.  `ma`: words per query row (rank_rows);
+        `expand`: None or an `ASMKExpansion` (rank_entries)."""
+        idx, val = self.rank_images([query_image], k, ma, expand)
         return [(self._paths[int(i)], float(v)) for i, v in zip(idx[0], val[0]) if i >= 0]
 
     # -------------------------------------------------------------------------------------------------- persistence

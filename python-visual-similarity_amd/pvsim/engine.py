@@ -616,6 +616,20 @@ class Context:
         check(_ffi.lib().pvs_asmk_remove_dev(self.handle, int(K), int(bits), int(N), ptr(d_word_off), ptr(h), ptr(d_ent_img),
                                              ptr(d_ent_sig), ptr(d_keep), ptr(d_pos), ptr(d_out_word_off), ptr(d_out_img), ptr(d_out_sig)))
 
+    # ASMK query expansion
+    def asmk_expand_dev(self, nq, h_q_off, d_q_word, d_q_sig, bits, K, d_word_off, d_ent_img, d_ent_sig, N, R, d_members, d_votes,
+                        query_vote, h_max, min_support, d_wt, cap, d_out_word, d_out_sig, d_out_count, d_out_sum, tile_words=0):
+        """pvs_asmk_expand_dev: the entries of nq queries, refined and extended by the entries of their members (int32 (nq, R) ids
+        ascending, -1 padded, with votes) -> out_word int32 (nq, cap), out_sig uint32 (nq, cap, bits / 32), the true count int32
+        (nq,) and weight sum int64 (nq,).  h_q_off: host int64 (nq + 1,)"""
+        h = np.ascontiguousarray(h_q_off, dtype=np.int64)
+        if h.shape != (int(nq) + 1,):
+            raise ValueError(f"h_q_off must have nq + 1 = {int(nq) + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_asmk_expand_dev(self.handle, int(nq), ptr(h), ptr(d_q_word), ptr(d_q_sig), int(bits), int(K), ptr(d_word_off),
+                                             ptr(d_ent_img), ptr(d_ent_sig), int(N), int(R), ptr(d_members), ptr(d_votes), int(query_vote),
+                                             int(h_max), int(min_support), ptr(d_wt), int(tile_words), int(cap), ptr(d_out_word),
+                                             ptr(d_out_sig), ptr(d_out_count), ptr(d_out_sum)))
+
     # index maintenance (DESIGN.md section 15)
     SCAN_TILE = _ffi.SCAN_TILE
 
