@@ -7,11 +7,11 @@
 //                            pvs_topk_dev on that panel
 // Every value is DEFINED in include/pvsim.h: the residual sum is float32 in row order with separate roundings (this unit is compiled
 // with -ffp-contract=off), the score is a sum of integers, exact in uint32, so the scan may be cut anywhere and may use atomics.
-// tests/asmk_numpy.py restates both.
+// tests/asmk_numpy.py restates both.  From list_common.hpp: the block scan, the lane searches, signatures, QueryOffsets, the score slice.
 #include <algorithm>
 
-#include "common.hpp"
 #include "desc_load.hpp"
+#include "list_common.hpp"
 
 namespace pvs {
 
@@ -22,9 +22,6 @@ constexpr int ASMK_MAX_D = 128;
 constexpr int ASMK_MAX_M = 8;                  // labels per row (pvs_asmk_aggregate_ma_dev)
 constexpr int ASMK_MAX_KEYS = 16384;           // rows x labels of one image: 16384 keys of 4 bytes are 64 KiB, their heads 32 KiB
 constexpr size_t ASMK_LDS_BUDGET = 160 * 1024 - 64;   // dynamic LDS of the aggregate kernel beside its static words
-constexpr int ASMK_MAX_SLICE = 32768;          // uint32 accumulators of one workgroup: 128 KiB
-constexpr int64_t ASMK_MIN_SLICE = 1024;       // images a workgroup serves at least when the host chooses (the rule of section 14)
-constexpr int ASMK_QUERY_BLOCK = 128;          // queries of one launch: their entry offsets travel as kernel arguments
 
 // ------------------------------------------------------------------------------------------------- aggregate
 // One workgroup per image.  LDS: keys [npad] (label and row in one integer), heads uint16 [npad] (first position of every run of equal
@@ -107,19 +104,8 @@ __global__ __launch_bounds__(ASMK_THREADS) void asmk_aggregate_kernel(const void
   const int p_lo = tid * per, p_hi = min(p_lo + per, n);
   int mine = 0;
   for (int p = p_lo; p < p_hi; ++p) mine += (p == 0 || (keys[p] >> SHIFT) != (keys[p - 1] >> SHIFT)) ? 1 : 0;
-  int incl = mine;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const int o = __shfl_up(incl, s, 64);
-    if (lane >= s) incl += o;
-  }
-  if (lane == 63) stmp[wave] = incl;
-  __syncthreads();
-  int before = incl - mine, E = 0;
-  for (int w = 0; w < ASMK_WAVES; ++w) {
-    if (w < wave) before += stmp[w];
-    E += stmp[w];
-  }
+  int E;
+  int before = block_excl_scan<ASMK_WAVES, false>(mine, stmp, lane, wave, E);   // stmp is not written again
   for (int p = p_lo; p < p_hi; ++p)
     if (p == 0 || (keys[p] >> SHIFT) != (keys[p - 1] >> SHIFT)) heads[before++] = (unsigned short)p;
   __syncthreads();
@@ -165,56 +151,18 @@ __global__ __launch_bounds__(ASMK_THREADS) void asmk_aggregate_kernel(const void
     const unsigned long long m0 = __ballot(z0 >= 0.f), m1 = __ballot(z1 >= 0.f);
     const int64_t slot = r0 * mm + e;
     if (lane == 0) ent_word[slot] = w;
-    if (lane < W) {
-      const unsigned long long mk = lane < 2 ? m0 : m1;
-      ent_sig[slot * W + lane] = (unsigned)(lane & 1 ? mk >> 32 : mk);
-    }
+    store_sig_ballots(ent_sig, slot, W, m0, m1, lane);
   }
 }
 
 // ------------------------------------------------------------------------------------------------- score
-struct AsmkQueryOffsets {
-  int64_t o[ASMK_QUERY_BLOCK + 1];   // entry offsets of the launch's queries
-  int64_t first;                     // global index of its first query
-};
-
-// the first p in [a, b) with img[p] >= key, b without one; img ascending in [a, b).  One lane's own search: 64 entries of a query
-// are searched side by side, so the dependent loads of a search are paid once per 64 entries.
-__device__ __forceinline__ int64_t asmk_lower_bound(const int32_t* __restrict__ img, int64_t a, int64_t b, int key) {
-  while (a < b) {
-    const int64_t m = a + ((b - a) >> 1);
-    if (img[m] < key) a = m + 1;
-    else b = m;
-  }
-  return a;
-}
-
-__device__ __forceinline__ int64_t asmk_shfl64(int64_t v, int src) {
-  const int lo = __shfl((int)(v & 0xffffffff), src, 64), hi = __shfl((int)(v >> 32), src, 64);
-  return ((int64_t)hi << 32) | (unsigned)lo;
-}
-
-template <int W>
-__device__ __forceinline__ void asmk_load_sig(const uint32_t* __restrict__ p, uint32_t (&s)[W]) {
-  if constexpr (W == 4) {
-    const uint4 v = *reinterpret_cast<const uint4*>(p);
-    s[0] = v.x, s[1] = v.y, s[2] = v.z, s[3] = v.w;
-  } else if constexpr (W == 2) {
-    const uint2 v = *reinterpret_cast<const uint2*>(p);
-    s[0] = v.x, s[1] = v.y;
-  } else {
-#pragma unroll
-    for (int i = 0; i < W; ++i) s[i] = p[i];
-  }
-}
-
 // Workgroup (g, q) of a grid (G, queries of the launch) serves query q and the images [g S, min((g + 1) S, N)).  acc[S] in LDS.
 // A wave takes 64 of the query's entries at a time.  First every lane finds, by two searches of its own, the part of one entry's
 // list that falls into the slice (the lists are sorted by image).  Then the wave walks the 64 parts: GW lanes per part and 64 / GW
 // parts side by side, GW = 16, 32 or 64 by the longest part of the batch, with coalesced reads of id and signature, xor, popcount,
 // a sel look-up and one LDS atomic add per entry.  After one barrier the slice is converted, scaled and stored.
 template <int W>
-__global__ __launch_bounds__(ASMK_THREADS) void asmk_score_kernel(AsmkQueryOffsets qo, const int32_t* __restrict__ q_word,
+__global__ __launch_bounds__(ASMK_THREADS) void asmk_score_kernel(QueryOffsets qo, const int32_t* __restrict__ q_word,
                                                                    const uint32_t* __restrict__ q_sig, int K,
                                                                    const int64_t* __restrict__ word_off,
                                                                    const int32_t* __restrict__ ent_img,
@@ -245,9 +193,9 @@ __global__ __launch_bounds__(ASMK_THREADS) void asmk_score_kernel(AsmkQueryOffse
         wgt = (unsigned)wt[w];
         const int64_t a = word_off[w], b = word_off[w + 1];
         if (wgt != 0u && b > a) {
-          lo = asmk_lower_bound(ent_img, a, b, s0);
+          lo = lower_bound_i32(ent_img, a, b, s0);
           // an image appears once per word: the slice holds at most sn entries of this list
-          cnt = (int)(asmk_lower_bound(ent_img, lo, min(b, lo + sn), s0 + sn) - lo);
+          cnt = (int)(lower_bound_i32(ent_img, lo, min(b, lo + sn), s0 + sn) - lo);
         }
       }
     }
@@ -265,22 +213,19 @@ __global__ __launch_bounds__(ASMK_THREADS) void asmk_score_kernel(AsmkQueryOffse
         if (g == grp) mine = l;
       }
       const int src = mine < 0 ? lane : mine;
-      const int64_t plo = asmk_shfl64(lo, src);
+      const int64_t plo = shfl64(lo, src);
       const int pn = __shfl(cnt, src, 64);
       const unsigned pw = (unsigned)__shfl((int)wgt, src, 64);
       const int n = mine < 0 ? 0 : pn;
       if (n > 0) {
         uint32_t qs[W];
-        asmk_load_sig<W>(q_sig + (eb + src) * W, qs);
+        load_sig<W>(q_sig + (eb + src) * W, qs);
         for (int t = gl; t < n; t += GW) {
           const int64_t p = plo + t;
           const unsigned i = (unsigned)(ent_img[p] - s0);
           uint32_t xs[W];
-          asmk_load_sig<W>(ent_sig + p * W, xs);
-          int h = 0;
-#pragma unroll
-          for (int u = 0; u < W; ++u) h += __popc(xs[u] ^ qs[u]);
-          if (i < (unsigned)sn) atomicAdd(&asmk_acc[i], pw * sel_s[h]);
+          load_sig<W>(ent_sig + p * W, xs);
+          if (i < (unsigned)sn) atomicAdd(&asmk_acc[i], pw * sel_s[hamming<W>(xs, qs)]);
         }
       }
     }
@@ -296,7 +241,7 @@ __global__ __launch_bounds__(ASMK_THREADS) void asmk_score_kernel(AsmkQueryOffse
 using namespace pvs;
 
 static int asmk_check_bits(const char* fn, int bits) {
-  if (bits != 32 && bits != 64 && bits != 96 && bits != 128) PVS_FAIL(PVS_ERR_INVALID, "%s: bits must be 32, 64, 96 or 128 (got %d)", fn, bits);
+  if (!sig_bits_ok(bits)) PVS_FAIL(PVS_ERR_INVALID, "%s: bits must be 32, 64, 96 or 128 (got %d)", fn, bits);
   return PVS_OK;
 }
 
@@ -313,7 +258,7 @@ static int asmk_aggregate_impl(const char* fn, pvs_ctx* ctx, const pvs_codebook*
     PVS_FAIL(PVS_ERR_INVALID, "%s: unknown descriptor kind %d", fn, desc_kind);
   const int D = cb->D, K = cb->K;
   if (D < 1 || D > ASMK_MAX_D) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= D <= %d (got %d)", fn, ASMK_MAX_D, D);
-  if (K < 1 || K > 65536) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= K <= 65536 (got %d)", fn, K);
+  if (!word_count_ok(K)) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= K <= 65536 (got %d)", fn, K);
   if (ma && (m < 1 || m > ASMK_MAX_M || m > K)) PVS_FAIL(PVS_ERR_INVALID, "%s: m must lie in 1..min(K, %d) (m = %d, K = %d)", fn, ASMK_MAX_M, m, K);
   if (!d_proj && bits != D) PVS_FAIL(PVS_ERR_INVALID, "%s: without a projection bits must equal D (bits=%d, D=%d)", fn, bits, D);
   if (n_images < 0 || total_desc < 0) PVS_FAIL(PVS_ERR_INVALID, "%s: negative sizes", fn);
@@ -380,68 +325,35 @@ PVS_EXPORT int pvs_asmk_score_dev(pvs_ctx* ctx, int64_t nq, const int64_t* h_q_o
                                   int slice_images, float* d_scores, int64_t ld) {
   PVS_NEED(ctx, "ctx");
   PVS_TRY(asmk_check_bits(__func__, bits));
-  if (K < 1 || K > 65536) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: need 1 <= K <= 65536 (got %d)", K);
+  if (!word_count_ok(K)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: need 1 <= K <= 65536 (got %d)", K);
   if (nq < 0 || N < 0 || N >= ((int64_t)1 << 31)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: need nq >= 0 and 0 <= N < 2^31");
   if (ld < N) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: ld = %lld is below N = %lld", (long long)ld, (long long)N);
   if (slice_images != 0 && (slice_images < 64 || slice_images > ASMK_MAX_SLICE || slice_images % 64))
     PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: slice_images must be 0 or a multiple of 64 in 64..%d (got %d)", ASMK_MAX_SLICE, slice_images);
   if (nq == 0 || N == 0) return PVS_OK;
-  PVS_NEED(h_q_off, "host query offsets");
-  for (int64_t q = 0; q < nq; ++q)
-    if (h_q_off[q] < 0 || h_q_off[q + 1] < h_q_off[q])
-      PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_score_dev: query offsets must be non-negative and must not decrease (query %lld)", (long long)q);
-  if (h_q_off[nq] > h_q_off[0]) {
-    PVS_NEED(d_q_word, "query words");
-    PVS_NEED(d_q_sig, "query signatures");
-  }
-  PVS_NEED(d_word_off, "word offsets");
-  PVS_NEED(d_ent_img, "entry images");
-  PVS_NEED(d_ent_sig, "entry signatures");
-  PVS_NEED(d_wt, "word weights");
+  const int W = bits / 32;
+  PVS_TRY(check_query_and_file(__func__, nq, h_q_off, d_q_word, d_q_sig, W, d_word_off, d_ent_img, d_ent_sig, true, d_wt));
   PVS_NEED(d_sel, "selectivity table");
   PVS_NEED(d_gamma_q, "query normalisers");
   PVS_NEED(d_gamma_db, "database normalisers");
   PVS_NEED(d_scores, "scores");
-  const int W = bits / 32;
-  const int sig_align = W == 4 ? 16 : (W == 2 ? 8 : 4);
-  PVS_ALIGNED(d_q_word, 4, "query words");
-  PVS_ALIGNED(d_q_sig, sig_align, "query signatures");
-  PVS_ALIGNED(d_word_off, 8, "word offsets");
-  PVS_ALIGNED(d_ent_img, 4, "entry images");
-  PVS_ALIGNED(d_ent_sig, sig_align, "entry signatures");
-  PVS_ALIGNED(d_wt, 4, "word weights");
   PVS_ALIGNED(d_sel, 4, "selectivity table");
   PVS_ALIGNED(d_gamma_q, 4, "query normalisers");
   PVS_ALIGNED(d_gamma_db, 4, "database normalisers");
   PVS_ALIGNED(d_scores, 4, "scores");
   PVS_HIP(hipSetDevice(ctx->device));
 
-  for (int64_t q0 = 0; q0 < nq; q0 += ASMK_QUERY_BLOCK) {
-    const int64_t qn = std::min<int64_t>(ASMK_QUERY_BLOCK, nq - q0);
-    int64_t S = slice_images;
-    if (S == 0) {
-      // about two workgroups per compute unit over the query block, no slice below ASMK_MIN_SLICE images
-      const int64_t want = (2 * (int64_t)ctx->num_cu + qn - 1) / qn;
-      const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>(want, N / ASMK_MIN_SLICE));
-      S = std::min<int64_t>(ASMK_MAX_SLICE, ((N + G0 - 1) / G0 + 63) / 64 * 64);
-    }
-    const int64_t G = (N + S - 1) / S;
-    AsmkQueryOffsets qo;
-    for (int64_t q = 0; q <= ASMK_QUERY_BLOCK; ++q) qo.o[q] = h_q_off[q0 + std::min(q, qn)];
-    qo.first = q0;
+  for (int64_t q0 = 0; q0 < nq; q0 += LIST_QUERY_BLOCK) {
+    const int64_t qn = std::min<int64_t>(LIST_QUERY_BLOCK, nq - q0);
+    const int64_t S = score_slice(ctx->num_cu, qn, N, slice_images), G = (N + S - 1) / S;
+    const QueryOffsets qo = query_offsets(h_q_off, q0, qn);
     ScopedTimer t(ctx, T_GEMM);   // the scoring slot, as the scans of the compact index
     const dim3 grid((unsigned)G, (unsigned)qn), block(ASMK_THREADS);
     const size_t lds = (size_t)S * sizeof(unsigned int);
-#define PVS_ASMK_SCORE(WORDS)                                                                                                        \
-  PVS_TRY(launch_lds(ctx, asmk_score_kernel<WORDS>, grid, block, lds, qo, d_q_word, d_q_sig, K, d_word_off, d_ent_img, d_ent_sig, (int)N, \
-                     d_wt, d_sel, d_gamma_q, d_gamma_db, (int)S, d_scores, ld))
-    switch (W) {
-      case 1: PVS_ASMK_SCORE(1); break;
-      case 2: PVS_ASMK_SCORE(2); break;
-      case 3: PVS_ASMK_SCORE(3); break;
-      default: PVS_ASMK_SCORE(4); break;
-    }
-#undef PVS_ASMK_SCORE
+    PVS_TRY(dispatch_sig_words(W, [&](auto w) -> int {
+      return launch_lds(ctx, asmk_score_kernel<decltype(w)::value>, grid, block, lds, qo, d_q_word, d_q_sig, K, d_word_off, d_ent_img, d_ent_sig,
+                        (int)N, d_wt, d_sel, d_gamma_q, d_gamma_db, (int)S, d_scores, ld);
+    }));
   }
   return PVS_OK;
 }

@@ -9,9 +9,10 @@
 //
 // The sort moves 8-byte items, (key << 32) | source slot, with key = the word, or K for a slot that is no entry: K's digit is 256 in
 // every pass, behind every word.  The signatures move once, in the final gather, as one load and one store of their full width.
+// From list_common.hpp: the block scan, last_le, move_sig, the two offset kernels, the tile and grid rules, the overlap and offset checks.
 #include <algorithm>
 
-#include "common.hpp"
+#include "list_common.hpp"
 
 namespace pvs {
 
@@ -20,59 +21,9 @@ constexpr int AU_WAVES = AU_THREADS / WAVE;
 constexpr int AU_BINS = 257;                              // 256 digits and the one behind them
 constexpr int AU_SCAN_PER = 8;
 constexpr int AU_SCAN_BLOCK = AU_THREADS * AU_SCAN_PER;   // counts one workgroup scans
-constexpr int AU_TILE_DEFAULT = 4096;
-constexpr int AU_TILE_MAX = 65536;
-constexpr int64_t AU_MAX_TILES = 65536;
 constexpr int64_t AU_MAX_ENTRIES = ((int64_t)1 << 31) - 1;
 
-typedef uint32_t au32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t au32x2 __attribute__((ext_vector_type(2)));
-
-template <int W>
-__device__ __forceinline__ void au_move_sig(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst) {
-  if constexpr (W == 4) {
-    *reinterpret_cast<au32x4*>(dst) = *reinterpret_cast<const au32x4*>(src);
-  } else if constexpr (W == 2) {
-    *reinterpret_cast<au32x2*>(dst) = *reinterpret_cast<const au32x2*>(src);
-  } else {
-    uint32_t v[W];
-#pragma unroll
-    for (int t = 0; t < W; ++t) v[t] = src[t];
-#pragma unroll
-    for (int t = 0; t < W; ++t) dst[t] = v[t];
-  }
-}
-
-// the last i in [0, n - 1] with off[i] <= s; off non-decreasing with off[0] <= s.  `steps` >= log2(n) bounds the loop.
-__device__ __forceinline__ int au_last_le(const int64_t* __restrict__ off, int n, int64_t s, int steps) {
-  int lo = 0, hi = n - 1;
-  for (int it = 0; it < steps; ++it) {
-    if (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (off[mid] <= s) lo = mid;
-      else hi = mid - 1;
-    }
-  }
-  return lo;
-}
-
 __device__ __forceinline__ int au_digit(uint32_t key, int K, int shift) { return key >= (uint32_t)K ? 256 : (int)((key >> shift) & 0xffu); }
-
-// block-wide inclusive scan of one int per thread; tmp: LDS int[AU_WAVES]; the caller may reuse tmp after the call
-__device__ __forceinline__ int au_scan_incl(int v, int* tmp, int lane, int wave) {
-  int incl = v;
-#pragma unroll
-  for (int s = 1; s < WAVE; s <<= 1) {
-    const int o = __shfl_up(incl, s, WAVE);
-    if (lane >= s) incl += o;
-  }
-  if (lane == WAVE - 1) tmp[wave] = incl;
-  __syncthreads();
-  int off = 0;
-  for (int w = 0; w < wave; ++w) off += tmp[w];
-  __syncthreads();
-  return incl + off;
-}
 
 // ------------------------------------------------------------------------------------------------- exclusive scan of int32 counts
 __global__ __launch_bounds__(AU_THREADS) void au_scan_sums_kernel(const int32_t* __restrict__ data, int64_t M, int32_t* __restrict__ partials) {
@@ -82,7 +33,7 @@ __global__ __launch_bounds__(AU_THREADS) void au_scan_sums_kernel(const int32_t*
   int mine = 0;
 #pragma unroll
   for (int e = 0; e < AU_SCAN_PER; ++e) mine += i0 + e < M ? data[i0 + e] : 0;
-  const int incl = au_scan_incl(mine, tmp, tid & 63, tid >> 6);
+  const int incl = block_incl_scan(mine, tmp, tid & 63, tid >> 6);
   if (tid == AU_THREADS - 1) partials[blockIdx.x] = incl;
 }
 
@@ -94,7 +45,7 @@ __global__ __launch_bounds__(AU_THREADS) void au_scan_partials_kernel(int32_t* _
   int carry = 0;
   for (int base = 0; base < nb; base += AU_THREADS) {
     const int v = base + tid < nb ? partials[base + tid] : 0;
-    const int incl = au_scan_incl(v, tmp, tid & 63, tid >> 6);
+    const int incl = block_incl_scan(v, tmp, tid & 63, tid >> 6);
     if (base + tid < nb) partials[base + tid] = carry + incl - v;
     if (tid == AU_THREADS - 1) chunk_total = incl;
     __syncthreads();
@@ -113,7 +64,7 @@ __global__ __launch_bounds__(AU_THREADS) void au_scan_apply_kernel(int32_t* __re
     v[e] = i0 + e < M ? data[i0 + e] : 0;
     mine += v[e];
   }
-  const int incl = au_scan_incl(mine, tmp, tid & 63, tid >> 6);
+  const int incl = block_incl_scan(mine, tmp, tid & 63, tid >> 6);
   int run = partials[blockIdx.x] + incl - mine;
 #pragma unroll
   for (int e = 0; e < AU_SCAN_PER; ++e) {
@@ -138,7 +89,7 @@ __global__ __launch_bounds__(AU_THREADS) void au_items_kernel(const int64_t* __r
                                                               const int32_t* __restrict__ count, const int32_t* __restrict__ word, int K,
                                                               int64_t total, uint64_t* __restrict__ items) {
   for (int64_t s = (int64_t)blockIdx.x * AU_THREADS + threadIdx.x; s < total; s += (int64_t)gridDim.x * AU_THREADS) {
-    const int i = au_last_le(offsets, n, s, steps);
+    const int i = last_le([&](int t) { return offsets[t]; }, n, s, steps);
     const int64_t first = offsets[i], rows = offsets[i + 1] - first;
     const int64_t c = min(max((int64_t)count[i], (int64_t)0), rows);
     uint32_t key = (uint32_t)K;
@@ -236,8 +187,8 @@ __global__ __launch_bounds__(AU_THREADS) void au_gather_kernel(const uint64_t* _
     if ((uint32_t)(item >> 32) >= (uint32_t)K) continue;
     const int64_t s = (int64_t)(uint32_t)item;
     if (s >= total) continue;
-    out_img[j] = (int32_t)(img_base + au_last_le(offsets, n, s, steps));
-    au_move_sig<W>(sig + s * W, out_sig + j * W);
+    out_img[j] = (int32_t)(img_base + last_le([&](int t) { return offsets[t]; }, n, s, steps));
+    move_sig<W>(sig + s * W, out_sig + j * W);
   }
 }
 
@@ -265,11 +216,6 @@ __global__ __launch_bounds__(AU_THREADS) void au_weight_sums_kernel(const int64_
 }
 
 // ------------------------------------------------------------------------------------------------- insert and remove
-__global__ void au_sum_offsets_kernel(const int64_t* __restrict__ a, const int64_t* __restrict__ b, int count, int64_t* __restrict__ out) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l < count) out[l] = a[l] + b[l];
-}
-
 // One lane per merged entry j: its word is the last w with word_off[w] + new_off[w] <= j; inside the list the old entries come first.
 template <int W>
 __global__ __launch_bounds__(AU_THREADS) void au_insert_kernel(const int64_t* __restrict__ word_off, const int64_t* __restrict__ new_off, int K,
@@ -279,25 +225,18 @@ __global__ __launch_bounds__(AU_THREADS) void au_insert_kernel(const int64_t* __
                                                                uint32_t* __restrict__ out_sig) {
   const int64_t total = E + b;
   for (int64_t j = (int64_t)blockIdx.x * AU_THREADS + threadIdx.x; j < total; j += (int64_t)gridDim.x * AU_THREADS) {
-    int lo = 0, hi = K - 1;
-    for (int it = 0; it < 17; ++it) {
-      if (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (word_off[mid] + new_off[mid] <= j) lo = mid;
-        else hi = mid - 1;
-      }
-    }
+    const int lo = last_le([&](int w) { return word_off[w] + new_off[w]; }, K, j, 17);   // K <= 2^16
     const int64_t first = word_off[lo], old_len = word_off[lo + 1] - first, r = j - (first + new_off[lo]);
     if (r < old_len) {
       const int64_t s = first + r;
       if (s < 0 || s >= E) continue;                  // the device offsets disagree with the host's: a broken precondition, nothing is read out of bounds
       out_img[j] = img[s];
-      au_move_sig<W>(sig + s * W, out_sig + j * W);
+      move_sig<W>(sig + s * W, out_sig + j * W);
     } else {
       const int64_t s = new_off[lo] + (r - old_len);
       if (s < 0 || s >= b) continue;
       out_img[j] = new_img[s];
-      au_move_sig<W>(new_sig + s * W, out_sig + j * W);
+      move_sig<W>(new_sig + s * W, out_sig + j * W);
     }
   }
 }
@@ -326,23 +265,8 @@ __global__ __launch_bounds__(AU_THREADS) void au_remove_kernel(const int32_t* __
     const int64_t p = spos[e];
     if (p < 0 || p >= E) continue;
     out_img[p] = (int32_t)pos[id];
-    au_move_sig<W>(sig + e * W, out_sig + p * W);
+    move_sig<W>(sig + e * W, out_sig + p * W);
   }
-}
-
-__global__ void au_remap_offsets_kernel(const int64_t* __restrict__ word_off, const int32_t* __restrict__ spos, int64_t E, int count,
-                                        int64_t* __restrict__ out) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l < count) out[l] = spos[min(max(word_off[l], (int64_t)0), E)];
-}
-
-static unsigned au_grid(const pvs_ctx* ctx, int64_t n) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + AU_THREADS - 1) / AU_THREADS, (int64_t)ctx->num_cu * 8));
-}
-
-static bool au_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a_bytes > 0 && b_bytes > 0 && a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
 }
 
 static int au_log2_steps(int64_t n) {
@@ -352,29 +276,16 @@ static int au_log2_steps(int64_t n) {
 }
 
 static int au_check_shape(const char* fn, int K, int bits) {
-  if (K < 1 || K > 65536) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= K <= 65536 (got %d)", fn, K);
-  if (bits != 32 && bits != 64 && bits != 96 && bits != 128) PVS_FAIL(PVS_ERR_INVALID, "%s: bits must be 32, 64, 96 or 128 (got %d)", fn, bits);
+  if (!word_count_ok(K)) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= K <= 65536 (got %d)", fn, K);
+  if (!sig_bits_ok(bits)) PVS_FAIL(PVS_ERR_INVALID, "%s: bits must be 32, 64, 96 or 128 (got %d)", fn, bits);
   return PVS_OK;
 }
 
 static int au_check_offsets(const char* fn, const char* what, const int64_t* h, int64_t count) {
-  if (h[0] != 0) PVS_FAIL(PVS_ERR_INVALID, "%s: %s[0] must be 0", fn, what);
-  for (int64_t l = 0; l < count; ++l)
-    if (h[l + 1] < h[l]) PVS_FAIL(PVS_ERR_INVALID, "%s: %s must not decrease (at %lld)", fn, what, (long long)l);
+  const int64_t bad = offsets_first_break(h, count);
+  if (bad == 0) PVS_FAIL(PVS_ERR_INVALID, "%s: %s[0] must be 0", fn, what);
+  if (bad > 0) PVS_FAIL(PVS_ERR_INVALID, "%s: %s must not decrease (at %lld)", fn, what, (long long)(bad - 1));
   return PVS_OK;
-}
-
-static int au_sig_align(int W) { return W == 4 ? 16 : W == 2 ? 8 : 4; }
-
-// f(std::integral_constant<int, W>{}) for W = bits / 32
-template <class F>
-static int au_dispatch_w(int W, F&& f) {
-  switch (W) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    default: return f(std::integral_constant<int, 4>{});
-  }
 }
 
 }  // namespace pvs
@@ -412,16 +323,14 @@ PVS_EXPORT int pvs_asmk_invert_dev(pvs_ctx* ctx, int K, int bits, const int64_t*
   PVS_ALIGNED(d_ent_count, 4, "ent_count");
   PVS_ALIGNED(d_ent_word, 4, "ent_word");
   PVS_ALIGNED(d_out_img, 4, "out img");
-  PVS_ALIGNED(d_ent_sig, au_sig_align(W), "ent_sig");
-  PVS_ALIGNED(d_out_sig, au_sig_align(W), "out sig");
-  if (au_overlap(d_out_sig, total * W * 4, d_ent_sig, total * W * 4) || au_overlap(d_out_img, total * 4, d_ent_word, total * 4) ||
-      au_overlap(d_out_img, total * 4, d_ent_sig, total * W * 4) || au_overlap(d_out_sig, total * W * 4, d_ent_word, total * 4) ||
-      au_overlap(d_word_off, (int64_t)(K + 1) * 8, d_offsets, (n_images + 1) * 8))
+  PVS_ALIGNED(d_ent_sig, sig_align(W), "ent_sig");
+  PVS_ALIGNED(d_out_sig, sig_align(W), "out sig");
+  if (ranges_overlap(d_out_sig, total * W * 4, d_ent_sig, total * W * 4) || ranges_overlap(d_out_img, total * 4, d_ent_word, total * 4) ||
+      ranges_overlap(d_out_img, total * 4, d_ent_sig, total * W * 4) || ranges_overlap(d_out_sig, total * W * 4, d_ent_word, total * 4) ||
+      ranges_overlap(d_word_off, (int64_t)(K + 1) * 8, d_offsets, (n_images + 1) * 8))
     PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_invert_dev: an output overlaps an input");
 
-  int64_t tile = tile_entries == 0 ? AU_TILE_DEFAULT : std::min<int64_t>(std::max<int64_t>((tile_entries + 255) / 256 * 256, 256), AU_TILE_MAX);
-  const int64_t need = ((total + AU_MAX_TILES - 1) / AU_MAX_TILES + 255) / 256 * 256;   // at most AU_MAX_TILES tiles: need <= 32768
-  tile = std::max(tile, need);
+  const int64_t tile = invert_tile(tile_entries, total);
   const int64_t ntiles = (total + tile - 1) / tile, ncounts = (int64_t)AU_BINS * ntiles;
   const AsmkInvertLayout lay = asmk_invert_layout((size_t)total, (size_t)ncounts, (size_t)((ncounts + AU_SCAN_BLOCK - 1) / AU_SCAN_BLOCK));
   void* block = nullptr;
@@ -431,7 +340,7 @@ PVS_EXPORT int pvs_asmk_invert_dev(pvs_ctx* ctx, int K, int bits, const int64_t*
   const int n = (int)n_images, steps = au_log2_steps(n_images);
 
   ScopedTimer t(ctx, T_MISC);
-  hipLaunchKernelGGL(au_items_kernel, dim3(au_grid(ctx, total)), dim3(AU_THREADS), 0, ctx->stream, d_offsets, n, steps, d_ent_count, d_ent_word, K,
+  hipLaunchKernelGGL(au_items_kernel, dim3(flat_grid(ctx->num_cu, total)), dim3(AU_THREADS), 0, ctx->stream, d_offsets, n, steps, d_ent_count, d_ent_word, K,
                      total, src);
   PVS_HIP(hipGetLastError());
   const int passes = K <= 256 ? 1 : 2;
@@ -447,8 +356,8 @@ PVS_EXPORT int pvs_asmk_invert_dev(pvs_ctx* ctx, int K, int bits, const int64_t*
   }
   hipLaunchKernelGGL(au_word_off_kernel, dim3((K + 1 + AU_THREADS - 1) / AU_THREADS), dim3(AU_THREADS), 0, ctx->stream, src, total, K, d_word_off);
   PVS_HIP(hipGetLastError());
-  return au_dispatch_w(W, [&](auto w) -> int {
-    hipLaunchKernelGGL((au_gather_kernel<decltype(w)::value>), dim3(au_grid(ctx, total)), dim3(AU_THREADS), 0, ctx->stream, src, total, K,
+  return dispatch_sig_words(W, [&](auto w) -> int {
+    hipLaunchKernelGGL((au_gather_kernel<decltype(w)::value>), dim3(flat_grid(ctx->num_cu, total)), dim3(AU_THREADS), 0, ctx->stream, src, total, K,
                        d_offsets, n, steps, d_ent_sig, img_base, d_out_img, d_out_sig);
     PVS_HIP(hipGetLastError());
     return PVS_OK;
@@ -458,7 +367,7 @@ PVS_EXPORT int pvs_asmk_invert_dev(pvs_ctx* ctx, int K, int bits, const int64_t*
 PVS_EXPORT int pvs_asmk_weight_sums_dev(pvs_ctx* ctx, int K, const int64_t* d_offsets, const int64_t* h_offsets, int64_t n_images,
                                         const int32_t* d_ent_count, const int32_t* d_ent_word, const int32_t* d_wt, int64_t* d_sums) {
   PVS_NEED(ctx, "ctx");
-  if (K < 1 || K > 65536) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_weight_sums_dev: need 1 <= K <= 65536 (got %d)", K);
+  if (!word_count_ok(K)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_weight_sums_dev: need 1 <= K <= 65536 (got %d)", K);
   if (n_images < 0 || n_images > AU_MAX_ENTRIES) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_weight_sums_dev: need 0 <= n_images < 2^31 (got %lld)", (long long)n_images);
   PVS_NEED(h_offsets, "host offsets");
   PVS_TRY(au_check_offsets(__func__, "offsets", h_offsets, n_images));
@@ -476,8 +385,8 @@ PVS_EXPORT int pvs_asmk_weight_sums_dev(pvs_ctx* ctx, int K, const int64_t* d_of
   for (int64_t i = 0; i < n_images; ++i) longest = std::max(longest, h_offsets[i + 1] - h_offsets[i]);
   if (longest > AU_MAX_ENTRIES) PVS_FAIL(PVS_ERR_UNSUPPORTED, "pvs_asmk_weight_sums_dev: an image of %lld slots", (long long)longest);
   if (longest > 0) PVS_NEED(d_ent_word, "ent_word");
-  if (au_overlap(d_sums, n_images * 8, d_offsets, (n_images + 1) * 8) || au_overlap(d_sums, n_images * 8, d_ent_count, n_images * 4) ||
-      au_overlap(d_sums, n_images * 8, d_wt, (int64_t)K * 4) || au_overlap(d_sums, n_images * 8, d_ent_word, h_offsets[n_images] * 4))
+  if (ranges_overlap(d_sums, n_images * 8, d_offsets, (n_images + 1) * 8) || ranges_overlap(d_sums, n_images * 8, d_ent_count, n_images * 4) ||
+      ranges_overlap(d_sums, n_images * 8, d_wt, (int64_t)K * 4) || ranges_overlap(d_sums, n_images * 8, d_ent_word, h_offsets[n_images] * 4))
     PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_weight_sums_dev: sums overlaps an input");
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer t(ctx, T_MISC);
@@ -521,25 +430,22 @@ PVS_EXPORT int pvs_asmk_insert_dev(pvs_ctx* ctx, int K, int bits, const int64_t*
   for (const void* p : {(const void*)d_ent_img, (const void*)d_new_img, (const void*)d_out_img})
     if (reinterpret_cast<uintptr_t>(p) % 4) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: ids must be 4-byte aligned");
   for (const void* p : {(const void*)d_ent_sig, (const void*)d_new_sig, (const void*)d_out_sig})
-    if (reinterpret_cast<uintptr_t>(p) % au_sig_align(W))
-      PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: signatures must be %d-byte aligned", au_sig_align(W));
+    if (reinterpret_cast<uintptr_t>(p) % sig_align(W))
+      PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: signatures must be %d-byte aligned", sig_align(W));
   const int64_t off_bytes = (int64_t)(K + 1) * 8, sw = (int64_t)W * 4;
-  const struct { const void* p; int64_t bytes; } ins[] = {{d_word_off, off_bytes}, {d_new_off, off_bytes}, {d_ent_img, E * 4}, {d_ent_sig, E * sw},
-                                                         {d_new_img, b * 4},      {d_new_sig, b * sw}},
-                                                 outs[] = {{d_out_word_off, off_bytes}, {d_out_img, total * 4}, {d_out_sig, total * sw}};
-  for (const auto& o : outs)
-    for (const auto& i : ins)
-      if (au_overlap(o.p, o.bytes, i.p, i.bytes)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: an output overlaps an input");
-  if (au_overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes) || au_overlap(outs[0].p, outs[0].bytes, outs[2].p, outs[2].bytes) ||
-      au_overlap(outs[1].p, outs[1].bytes, outs[2].p, outs[2].bytes))
-    PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: two outputs overlap");
+  const ByteRange ins[] = {{d_word_off, off_bytes}, {d_new_off, off_bytes}, {d_ent_img, E * 4}, {d_ent_sig, E * sw}, {d_new_img, b * 4},
+                           {d_new_sig, b * sw}},
+                  outs[] = {{d_out_word_off, off_bytes}, {d_out_img, total * 4}, {d_out_sig, total * sw}};
+  const int clash = outputs_overlap(outs, 3, ins, 6);
+  if (clash == 1) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: an output overlaps an input");
+  if (clash == 2) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_insert_dev: two outputs overlap");
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer t(ctx, T_MISC);
-  hipLaunchKernelGGL(au_sum_offsets_kernel, dim3((K + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_word_off, d_new_off, K + 1, d_out_word_off);
+  hipLaunchKernelGGL(sum_offsets_kernel<int64_t>, dim3((K + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_word_off, d_new_off, K + 1, d_out_word_off);
   PVS_HIP(hipGetLastError());
   if (total == 0) return PVS_OK;
-  return au_dispatch_w(W, [&](auto w) -> int {
-    hipLaunchKernelGGL((au_insert_kernel<decltype(w)::value>), dim3(au_grid(ctx, total)), dim3(AU_THREADS), 0, ctx->stream, d_word_off, d_new_off,
+  return dispatch_sig_words(W, [&](auto w) -> int {
+    hipLaunchKernelGGL((au_insert_kernel<decltype(w)::value>), dim3(flat_grid(ctx->num_cu, total)), dim3(AU_THREADS), 0, ctx->stream, d_word_off, d_new_off,
                        K, d_ent_img, d_ent_sig, d_new_img, d_new_sig, E, b, d_out_img, d_out_sig);
     PVS_HIP(hipGetLastError());
     return PVS_OK;
@@ -575,31 +481,27 @@ PVS_EXPORT int pvs_asmk_remove_dev(pvs_ctx* ctx, int K, int bits, int64_t N, con
   PVS_ALIGNED(d_pos, 8, "pos");
   PVS_ALIGNED(d_ent_img, 4, "ent_img");
   PVS_ALIGNED(d_out_img, 4, "out img");
-  PVS_ALIGNED(d_ent_sig, au_sig_align(W), "ent_sig");
-  PVS_ALIGNED(d_out_sig, au_sig_align(W), "out sig");
+  PVS_ALIGNED(d_ent_sig, sig_align(W), "ent_sig");
+  PVS_ALIGNED(d_out_sig, sig_align(W), "out sig");
   const int64_t off_bytes = (int64_t)(K + 1) * 8, sw = (int64_t)W * 4;
-  const struct { const void* p; int64_t bytes; } ins[] = {{d_word_off, off_bytes}, {d_ent_img, E * 4}, {d_ent_sig, E * sw}, {d_keep, N},
-                                                         {d_pos, (N + 1) * 8}},
-                                                 outs[] = {{d_out_word_off, off_bytes}, {d_out_img, E * 4}, {d_out_sig, E * sw}};
-  for (const auto& o : outs)
-    for (const auto& i : ins)
-      if (au_overlap(o.p, o.bytes, i.p, i.bytes)) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_remove_dev: an output overlaps an input");
-  if (au_overlap(outs[0].p, outs[0].bytes, outs[1].p, outs[1].bytes) || au_overlap(outs[0].p, outs[0].bytes, outs[2].p, outs[2].bytes) ||
-      au_overlap(outs[1].p, outs[1].bytes, outs[2].p, outs[2].bytes))
-    PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_remove_dev: two outputs overlap");
+  const ByteRange ins[] = {{d_word_off, off_bytes}, {d_ent_img, E * 4}, {d_ent_sig, E * sw}, {d_keep, N}, {d_pos, (N + 1) * 8}},
+                  outs[] = {{d_out_word_off, off_bytes}, {d_out_img, E * 4}, {d_out_sig, E * sw}};
+  const int clash = outputs_overlap(outs, 3, ins, 5);
+  if (clash == 1) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_remove_dev: an output overlaps an input");
+  if (clash == 2) PVS_FAIL(PVS_ERR_INVALID, "pvs_asmk_remove_dev: two outputs overlap");
   const int64_t M = E + 1;
   const AsmkRemoveLayout lay = asmk_remove_layout((size_t)E, (size_t)((M + AU_SCAN_BLOCK - 1) / AU_SCAN_BLOCK));
   void* block = nullptr;
   PVS_TRY(ws_reserve(ctx, WS_UPDATE, lay.bytes, &block));
   int32_t *spos = lay.spos(block), *partials = lay.partials(block);
   ScopedTimer t(ctx, T_MISC);
-  hipLaunchKernelGGL(au_survivor_flags_kernel, dim3(au_grid(ctx, M)), dim3(AU_THREADS), 0, ctx->stream, d_ent_img, d_keep, N, E, spos);
+  hipLaunchKernelGGL(au_survivor_flags_kernel, dim3(flat_grid(ctx->num_cu, M)), dim3(AU_THREADS), 0, ctx->stream, d_ent_img, d_keep, N, E, spos);
   PVS_HIP(hipGetLastError());
   PVS_TRY(au_launch_scan(ctx, spos, M, partials));
-  hipLaunchKernelGGL(au_remap_offsets_kernel, dim3((K + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_word_off, spos, E, K + 1, d_out_word_off);
+  hipLaunchKernelGGL(remap_offsets_kernel<int32_t>, dim3((K + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_word_off, spos, E, K + 1, d_out_word_off);
   PVS_HIP(hipGetLastError());
-  return au_dispatch_w(W, [&](auto w) -> int {
-    hipLaunchKernelGGL((au_remove_kernel<decltype(w)::value>), dim3(au_grid(ctx, E)), dim3(AU_THREADS), 0, ctx->stream, d_ent_img, d_ent_sig, d_keep,
+  return dispatch_sig_words(W, [&](auto w) -> int {
+    hipLaunchKernelGGL((au_remove_kernel<decltype(w)::value>), dim3(flat_grid(ctx->num_cu, E)), dim3(AU_THREADS), 0, ctx->stream, d_ent_img, d_ent_sig, d_keep,
                        d_pos, spos, N, E, d_out_img, d_out_sig);
     PVS_HIP(hipGetLastError());
     return PVS_OK;

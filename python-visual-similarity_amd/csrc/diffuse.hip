@@ -21,10 +21,10 @@
 // Per step: apply (Ap = p - alpha S p, block partials of p.Ap) -> one workgroup adds the partials in block order and forms a, retiring
 // columns with p.Ap <= 0 -> update (x, r, block partials of r.r) -> one workgroup forms b, rr and the flags of the next step -> p.
 // A column that does not step is not written.  The host reads one int (columns that still step) every check_every steps, only in
-// order to stop launching.
+// order to stop launching.  From list_common.hpp: ranges_overlap.
 #include <algorithm>
 
-#include "common.hpp"
+#include "list_common.hpp"
 
 namespace pvs {
 
@@ -373,11 +373,6 @@ static int df_dispatch_width(int cw, F&& f) {
   }
 }
 
-static bool df_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
-
 static int df_check_graph_shape(const char* who, int64_t N, int kg) {
   if (N < 2 || N >= ((int64_t)1 << 31)) PVS_FAIL(PVS_ERR_INVALID, "%s: need 2 <= N < 2^31 (got N=%lld)", who, (long long)N);
   if (kg < 1 || kg > N - 1) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= kg <= N - 1 (got kg=%d, N=%lld)", who, kg, (long long)N);
@@ -407,10 +402,10 @@ PVS_EXPORT int pvs_graph_affinity_dev(pvs_ctx* ctx, const int64_t* d_idx, const 
   PVS_ALIGNED(d_a, 8, "a");
   const size_t in_n = (size_t)b * (kg + 1), out_n = (size_t)N * kg;
   const size_t val_bytes = in_n * (val_f64 ? 8 : 4);
-  if (df_overlap(d_idx, in_n * 8, d_nbr, out_n * 4) || df_overlap(d_idx, in_n * 8, d_a, out_n * 8) ||
-      df_overlap(d_val, val_bytes, d_nbr, out_n * 4) || df_overlap(d_val, val_bytes, d_a, out_n * 8))
+  if (ranges_overlap(d_idx, in_n * 8, d_nbr, out_n * 4) || ranges_overlap(d_idx, in_n * 8, d_a, out_n * 8) ||
+      ranges_overlap(d_val, val_bytes, d_nbr, out_n * 4) || ranges_overlap(d_val, val_bytes, d_a, out_n * 8))
     PVS_FAIL(PVS_ERR_INVALID, "%s: an output overlaps a list", __func__);
-  if (df_overlap(d_nbr, out_n * 4, d_a, out_n * 8)) PVS_FAIL(PVS_ERR_INVALID, "%s: nbr overlaps a", __func__);
+  if (ranges_overlap(d_nbr, out_n * 4, d_a, out_n * 8)) PVS_FAIL(PVS_ERR_INVALID, "%s: nbr overlaps a", __func__);
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer tm(ctx, T_MISC);
   if (val_f64)
@@ -433,7 +428,7 @@ PVS_EXPORT int pvs_graph_mutual_dev(pvs_ctx* ctx, const int32_t* d_nbr, const do
   PVS_ALIGNED(d_a, 8, "a");
   PVS_ALIGNED(d_w, 8, "w");
   const size_t n = (size_t)N * kg;
-  if (df_overlap(d_w, n * 8, d_nbr, n * 4) || df_overlap(d_w, n * 8, d_a, n * 8)) PVS_FAIL(PVS_ERR_INVALID, "%s: w overlaps an input", __func__);
+  if (ranges_overlap(d_w, n * 8, d_nbr, n * 4) || ranges_overlap(d_w, n * 8, d_a, n * 8)) PVS_FAIL(PVS_ERR_INVALID, "%s: w overlaps an input", __func__);
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer tm(ctx, T_MISC);
   hipLaunchKernelGGL(df_mutual_kernel, dim3(df_grid(N * kg)), dim3(DF_THREADS), 0, ctx->stream, d_nbr, d_a, N, kg, d_w);
@@ -451,7 +446,7 @@ PVS_EXPORT int pvs_graph_degrees_dev(pvs_ctx* ctx, const double* d_w, int64_t N,
   PVS_ALIGNED(d_deg, 8, "deg");
   PVS_ALIGNED(d_r, 8, "r");
   const size_t n = (size_t)N * kg * 8, v = (size_t)N * 8;
-  if (df_overlap(d_w, n, d_deg, v) || df_overlap(d_w, n, d_r, v) || df_overlap(d_deg, v, d_r, v))
+  if (ranges_overlap(d_w, n, d_deg, v) || ranges_overlap(d_w, n, d_r, v) || ranges_overlap(d_deg, v, d_r, v))
     PVS_FAIL(PVS_ERR_INVALID, "%s: the arrays overlap", __func__);
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer tm(ctx, T_MISC);
@@ -473,7 +468,7 @@ PVS_EXPORT int pvs_graph_normalise_dev(pvs_ctx* ctx, const int32_t* d_nbr, const
   PVS_ALIGNED(d_r, 8, "r");
   PVS_ALIGNED(d_s, 8, "s");
   const size_t n = (size_t)N * kg;
-  if (df_overlap(d_s, n * 8, d_nbr, n * 4) || df_overlap(d_s, n * 8, d_r, (size_t)N * 8) || df_overlap(d_s, n * 8, d_w, n * 8))
+  if (ranges_overlap(d_s, n * 8, d_nbr, n * 4) || ranges_overlap(d_s, n * 8, d_r, (size_t)N * 8) || ranges_overlap(d_s, n * 8, d_w, n * 8))
     PVS_FAIL(PVS_ERR_INVALID, "%s: s overlaps an input", __func__);
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer tm(ctx, T_MISC);
@@ -497,7 +492,7 @@ PVS_EXPORT int pvs_diffuse_rhs_dev(pvs_ctx* ctx, const int64_t* d_idx, const voi
   PVS_ALIGNED(d_val, val_f64 ? 8 : 4, "val");
   PVS_ALIGNED(d_Y, 8, "Y");
   const size_t yb = (size_t)N * (size_t)C * 8, lb = (size_t)C * kq * 8;
-  if (df_overlap(d_Y, yb, d_idx, lb) || df_overlap(d_Y, yb, d_val, val_f64 ? lb : lb / 2)) PVS_FAIL(PVS_ERR_INVALID, "%s: Y overlaps a list", __func__);
+  if (ranges_overlap(d_Y, yb, d_idx, lb) || ranges_overlap(d_Y, yb, d_val, val_f64 ? lb : lb / 2)) PVS_FAIL(PVS_ERR_INVALID, "%s: Y overlaps a list", __func__);
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer tm(ctx, T_MISC);
   PVS_HIP(hipMemsetAsync(d_Y, 0, yb, ctx->stream));
@@ -567,7 +562,7 @@ PVS_EXPORT int pvs_diffuse_cg_dev(pvs_ctx* ctx, const int32_t* d_nbr, const doub
                 {d_X, vb, true},        {d_steps, (size_t)C * 4, true}, {d_rr, (size_t)C * 8, true}, {d_yy, (size_t)C * 8, true}};
   for (const Range& o : ranges)
     for (const Range& q : ranges)
-      if (o.out && &o != &q && df_overlap(o.p, o.n, q.p, q.n)) PVS_FAIL(PVS_ERR_INVALID, "%s: an output or the work buffer overlaps another array", __func__);
+      if (o.out && &o != &q && ranges_overlap(o.p, o.n, q.p, q.n)) PVS_FAIL(PVS_ERR_INVALID, "%s: an output or the work buffer overlaps another array", __func__);
   const int cw = df_width(C, width);
   const int64_t nb = (N + DF_THREADS - 1) / DF_THREADS, chunks = (C + cw - 1) / cw;
   if (chunks > 65535) PVS_FAIL(PVS_ERR_INVALID, "%s: %lld columns at width %d are more than 65535 column chunks", __func__, (long long)C, cw);
@@ -614,7 +609,7 @@ PVS_EXPORT int pvs_rank_f64_dev(pvs_ctx* ctx, const double* d_scores, int64_t nq
   PVS_ALIGNED(d_idx, 8, "idx");
   PVS_ALIGNED(d_val, 8, "val");
   const size_t sb = (size_t)nq * (size_t)ld * 8, lb = (size_t)nq * k * 8;
-  if (df_overlap(d_scores, sb, d_idx, lb) || df_overlap(d_scores, sb, d_val, lb) || df_overlap(d_idx, lb, d_val, lb))
+  if (ranges_overlap(d_scores, sb, d_idx, lb) || ranges_overlap(d_scores, sb, d_val, lb) || ranges_overlap(d_idx, lb, d_val, lb))
     PVS_FAIL(PVS_ERR_INVALID, "%s: the arrays overlap", __func__);
   PVS_HIP(hipSetDevice(ctx->device));
   return launch_rank_f64(ctx, d_scores, nq, ncols, ld, k, d_idx, d_val);

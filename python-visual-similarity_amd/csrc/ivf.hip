@@ -8,8 +8,10 @@
 // scalar, the coarse term, as the start of the sum.  Every sum is DEFINED (include/pvsim.h): float32, ascending index, a multiply and
 // an add rounded separately; this unit is compiled with -ffp-contract=off like pq.hip, and tests/ivf_numpy.py restates it.  The
 // scan shares its table copy, dword gather and segment plan with the flat scan of pq.hip (pq_common.hpp).
+// From list_common.hpp: the block scan over the probed lists' lengths, the check of the host offsets.
 #include <functional>
 
+#include "list_common.hpp"
 #include "pq_common.hpp"
 
 namespace pvs {
@@ -23,22 +25,6 @@ constexpr int64_t IVF_CAND_BYTES = (int64_t)64 << 20;   // candidate rows of one
 constexpr int64_t IVF_MIN_SLICE = 1024;        // candidate slots a workgroup serves at least: a table copy is m * ksub * 4 bytes
 
 // ------------------------------------------------------------------------------------------------- probed scan
-// block-wide inclusive scan of one int per thread (512 threads); tmp: LDS int[8]
-__device__ __forceinline__ int ivf_block_incl_scan(int v, int* tmp, int lane, int wave) {
-  int incl = v;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const int o = __shfl_up(incl, s, 64);
-    if (lane >= s) incl += o;
-  }
-  if (lane == 63) tmp[wave] = incl;
-  __syncthreads();
-  int off = 0;
-  for (int w = 0; w < wave; ++w) off += tmp[w];
-  __syncthreads();
-  return incl + off;
-}
-
 // Workgroup (g, q) of a grid (G, queries of the block).  The candidate row of query q is the concatenation of its probed lists in
 // probe order: probe j owns the slots [incl[j] - len[j], incl[j]), and slot p of it is stored row start[j] + p; the slots from
 // incl[nprobe - 1] up to W are padding (id -1).  The workgroup serves the slice [g S, (g + 1) S) of that row, S a multiple of the
@@ -80,7 +66,7 @@ __global__ __launch_bounds__(IVF_THREADS) void ivf_scan_kernel(const float* __re
         cterm[j] = pval[q * nprobe + j];
       }
     }
-    const int both = ivf_block_incl_scan(len[0] + len[1], stmp, lane, wave);
+    const int both = block_incl_scan(len[0] + len[1], stmp, lane, wave);
     if (2 * tid < nprobe) incl[2 * tid] = both - len[1];
     if (2 * tid + 1 < nprobe) incl[2 * tid + 1] = both;
   }
@@ -207,9 +193,9 @@ PVS_EXPORT int pvs_ivf_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t n
   if (k < 1 || k > 1024) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: need 1 <= k <= 1024 (got %d)", k);
   if (nq < 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: negative nq");
   PVS_NEED(h_list_off, "host list_off");
-  if (h_list_off[0] != 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: list_off[0] must be 0");
-  for (int l = 0; l < nlist; ++l)
-    if (h_list_off[l + 1] < h_list_off[l]) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: list_off must not decrease (list %d)", l);
+  const int64_t bad = offsets_first_break(h_list_off, nlist);
+  if (bad == 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: list_off[0] must be 0");
+  if (bad > 0) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: list_off must not decrease (list %d)", (int)(bad - 1));
   const int64_t N = h_list_off[nlist];
   if (N >= ((int64_t)1 << 31)) PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_scan_topk_dev: need N < 2^31 (got %lld)", (long long)N);
   if (nq == 0) return PVS_OK;

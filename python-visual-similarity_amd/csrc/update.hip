@@ -12,9 +12,10 @@
 // The movers are bandwidth kernels.  A row of row_bytes moves as row_bytes / V units of V bytes, V the widest of 16, 8, 4, 2, 1
 // that divides the row length and both base addresses; a lane owns one unit at a time and keeps MOVE_U of them in flight.  The
 // only indirection is one keep byte and one position (or one source index) per unit, read from arrays that neighbouring lanes share.
+// From list_common.hpp: the block scan, the two offset kernels, the grid rule, the overlap and offset checks.
 #include <algorithm>
 
-#include "common.hpp"
+#include "list_common.hpp"
 
 namespace pvs {
 
@@ -29,22 +30,6 @@ constexpr int64_t UPDATE_STAGE_BYTES = (int64_t)64 << 20;   // staging block of 
 constexpr int64_t MOVE_MAX_ROW_BYTES = (int64_t)1 << 30;
 
 // ------------------------------------------------------------------------------------------------- keep positions
-// block-wide inclusive scan of one int per thread (256 threads); tmp: LDS int[4]
-__device__ __forceinline__ int scan_block_incl(int v, int* tmp, int lane, int wave) {
-  int incl = v;
-#pragma unroll
-  for (int s = 1; s < 64; s <<= 1) {
-    const int o = __shfl_up(incl, s, 64);
-    if (lane >= s) incl += o;
-  }
-  if (lane == 63) tmp[wave] = incl;
-  __syncthreads();
-  int off = 0;
-  for (int w = 0; w < wave; ++w) off += tmp[w];
-  __syncthreads();
-  return incl + off;
-}
-
 // the 8 flags of a lane as bits 0..7 (bit e: keep[i0 + e] != 0); entries at or beyond n count as 0
 __device__ __forceinline__ unsigned load_flags(const uint8_t* __restrict__ keep, int64_t i0, int64_t n, bool aligned8) {
   unsigned bits = 0;
@@ -67,7 +52,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_tile_count_kernel(const uin
   const int tid = threadIdx.x;
   const int64_t i0 = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)tid * SCAN_PER_LANE;
   const int c = __popc(load_flags(keep, i0, n, aligned8));
-  const int incl = scan_block_incl(c, tmp, tid & 63, tid >> 6);
+  const int incl = block_incl_scan(c, tmp, tid & 63, tid >> 6);
   if (tid == SCAN_THREADS - 1) tile_sum[blockIdx.x] = incl;
 }
 
@@ -111,7 +96,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_final_kernel(const uint8_t*
   const int64_t i0 = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)tid * SCAN_PER_LANE;
   const unsigned bits = load_flags(keep, i0, n, aligned8);
   const int c = __popc(bits);
-  const int incl = scan_block_incl(c, tmp, tid & 63, tid >> 6);
+  const int incl = block_incl_scan(c, tmp, tid & 63, tid >> 6);
   int64_t run = block_ex[blockIdx.x / SCAN_TILE] + tile_ex[blockIdx.x] + (incl - c);
 #pragma unroll
   for (int e = 0; e < SCAN_PER_LANE; ++e) {
@@ -230,8 +215,7 @@ static int move_width(int64_t row_bytes, std::initializer_list<const void*> base
 }
 
 static unsigned move_grid(const pvs_ctx* ctx, int64_t units) {
-  const int64_t per_block = (int64_t)MOVE_THREADS * MOVE_U;
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((units + per_block - 1) / per_block, (int64_t)ctx->num_cu * 8));
+  return flat_grid(ctx->num_cu, units, (int64_t)MOVE_THREADS * MOVE_U);
 }
 
 // f(V{}) for the unit type of `width` bytes
@@ -266,11 +250,6 @@ static int launch_move_rows(pvs_ctx* ctx, const void* src, void* dst, const uint
 }
 
 // ------------------------------------------------------------------------------------------------- inverted lists
-__global__ void ivf_sum_offsets_kernel(const int64_t* __restrict__ a, const int64_t* __restrict__ b, int count, int64_t* __restrict__ out) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l < count) out[l] = a[l] + b[l];
-}
-
 // One lane per merged stored row j: its list is the last l with out_off[l] <= j (a list that starts at j and is not empty); inside the
 // list the old rows come first, then the new rows of the list in arrival order.  Writes the source of the row's code (srcmap), its
 // id and its norm.
@@ -322,25 +301,10 @@ __global__ void ivf_remap_kernel(const int32_t* __restrict__ ids, const float* _
     }
 }
 
-__global__ void ivf_remap_offsets_kernel(const int64_t* __restrict__ list_off, const int64_t* __restrict__ spos, int64_t n, int count,
-                                         int64_t* __restrict__ out) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l < count) out[l] = spos[min(max(list_off[l], (int64_t)0), n)];
-}
-
-static unsigned flat_grid(const pvs_ctx* ctx, int64_t n) {
-  return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->num_cu * 8));
-}
-
-static bool ranges_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a && b && a_bytes > 0 && b_bytes > 0 && a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
-}
-
 static int check_offsets(const char* fn, const char* what, const int64_t* h, int nlist) {
-  if (h[0] != 0) PVS_FAIL(PVS_ERR_INVALID, "%s: %s[0] must be 0", fn, what);
-  for (int l = 0; l < nlist; ++l)
-    if (h[l + 1] < h[l]) PVS_FAIL(PVS_ERR_INVALID, "%s: %s must not decrease (list %d)", fn, what, l);
+  const int64_t bad = offsets_first_break(h, nlist);
+  if (bad == 0) PVS_FAIL(PVS_ERR_INVALID, "%s: %s[0] must be 0", fn, what);
+  if (bad > 0) PVS_FAIL(PVS_ERR_INVALID, "%s: %s must not decrease (list %d)", fn, what, (int)(bad - 1));
   return PVS_OK;
 }
 
@@ -374,7 +338,7 @@ PVS_EXPORT int pvs_keep_mask_dev(pvs_ctx* ctx, const int64_t* d_removed, int64_t
   ScopedTimer t(ctx, T_MISC);
   PVS_HIP(hipMemsetAsync(d_keep, 1, (size_t)n, ctx->stream));
   if (r > 0) {
-    hipLaunchKernelGGL(scatter_zero_kernel, dim3(flat_grid(ctx, r)), dim3(256), 0, ctx->stream, d_removed, r, n, d_keep);
+    hipLaunchKernelGGL(scatter_zero_kernel, dim3(flat_grid(ctx->num_cu, r)), dim3(256), 0, ctx->stream, d_removed, r, n, d_keep);
     PVS_HIP(hipGetLastError());
   }
   return PVS_OK;
@@ -497,13 +461,13 @@ PVS_EXPORT int pvs_ivf_insert_dev(pvs_ctx* ctx, int m, int nlist, const uint8_t*
     PVS_FAIL(PVS_ERR_INVALID, "pvs_ivf_insert_dev: an output overlaps an input");
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer t(ctx, T_MISC);
-  hipLaunchKernelGGL(ivf_sum_offsets_kernel, dim3((nlist + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_list_off, d_new_off, nlist + 1,
+  hipLaunchKernelGGL(sum_offsets_kernel<int64_t>, dim3((nlist + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_list_off, d_new_off, nlist + 1,
                      d_out_list_off);
   PVS_HIP(hipGetLastError());
   if (total == 0) return PVS_OK;
   int32_t* srcmap = nullptr;
   PVS_TRY(ws_reserve(ctx, WS_UPDATE, (size_t)total * sizeof(int32_t), &srcmap));
-  hipLaunchKernelGGL(ivf_insert_plan_kernel, dim3(flat_grid(ctx, total)), dim3(256), 0, ctx->stream, d_out_list_off, d_list_off, d_new_off,
+  hipLaunchKernelGGL(ivf_insert_plan_kernel, dim3(flat_grid(ctx->num_cu, total)), dim3(256), 0, ctx->stream, d_out_list_off, d_list_off, d_new_off,
                      nlist, d_ids, d_inv_db, d_perm, d_new_inv, n, b, total, srcmap, d_out_ids, d_out_inv);
   PVS_HIP(hipGetLastError());
   const int width = move_width(m, {(const void*)(n > 0 ? d_codes : nullptr), (const void*)(b > 0 ? d_new_codes : nullptr), (const void*)d_out_codes});
@@ -558,14 +522,14 @@ PVS_EXPORT int pvs_ivf_remove_dev(pvs_ctx* ctx, int m, int nlist, int64_t n, con
   int64_t* spos = lay.pos(block);
   {
     ScopedTimer t(ctx, T_MISC);
-    hipLaunchKernelGGL(ivf_stored_keep_kernel, dim3(flat_grid(ctx, n)), dim3(256), 0, ctx->stream, d_ids, d_keep, n, skeep);
+    hipLaunchKernelGGL(ivf_stored_keep_kernel, dim3(flat_grid(ctx->num_cu, n)), dim3(256), 0, ctx->stream, d_ids, d_keep, n, skeep);
     PVS_HIP(hipGetLastError());
   }
   PVS_TRY(launch_keep_positions(ctx, skeep, n, spos, {lay.tile(block), lay.block(block), lay.top(block)}));
   ScopedTimer t(ctx, T_MISC);
-  hipLaunchKernelGGL(ivf_remap_kernel, dim3(flat_grid(ctx, n)), dim3(256), 0, ctx->stream, d_ids, d_inv_db, skeep, spos, d_pos, n, d_out_ids,
+  hipLaunchKernelGGL(ivf_remap_kernel, dim3(flat_grid(ctx->num_cu, n)), dim3(256), 0, ctx->stream, d_ids, d_inv_db, skeep, spos, d_pos, n, d_out_ids,
                      d_out_inv);
-  hipLaunchKernelGGL(ivf_remap_offsets_kernel, dim3((nlist + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_list_off, spos, n, nlist + 1,
+  hipLaunchKernelGGL(remap_offsets_kernel<int64_t>, dim3((nlist + 1 + 255) / 256), dim3(256), 0, ctx->stream, d_list_off, spos, n, nlist + 1,
                      d_out_list_off);
   PVS_HIP(hipGetLastError());
   return launch_move_rows(ctx, d_codes, d_out_codes, skeep, spos, nullptr, 0, n, m);

@@ -132,6 +132,30 @@ def _row_dtype(kind):
     return np.uint8 if kind == DESC_U8_ROOTSIFT else np.float32
 
 
+def _check_k(k) -> int:
+    if isinstance(k, bool) or int(k) != k or k < 1:
+        raise ValueError(f"k must be a positive integer, got {k!r}")
+    return int(k)
+
+
+def _check_rows(offsets, query: bool = False) -> None:
+    """no image of the CSR `offsets` holds more than 8192 rows (pvs_asmk_aggregate_dev)"""
+    if int(np.diff(offsets).max(initial=0)) > MAX_ROWS:
+        raise NotImplementedError(f"a query of more than {MAX_ROWS} rows is not supported" if query else
+                                  f"an image of more than {MAX_ROWS} rows cannot be indexed")
+
+
+def _free_file(bufs) -> None:
+    """the three device buffers of a file set (ASMKIndex._file_buffers)"""
+    for name in ("word_off", "ent_img", "ent_sig"):
+        bufs[name].free()
+
+
+def _proj_ptr(buf):
+    """the device pointer of an optional projection buffer"""
+    return None if buf is None else buf.ptr
+
+
 # ------------------------------------------------------------------------------------------------ device steps
 def check_ma(ma, n_words: int, offsets=None) -> int:
     """`ma`, the words a query row is assigned to: an integer in 1..min(8, n_words).  With `offsets`, also the keys of the largest
@@ -421,8 +445,7 @@ class ASMKIndex:
                 raise ValueError(f"the projection must be (bits, D) = {(bits, D)}, got {projection.shape}")
         elif bits != D:
             raise ValueError(f"without a projection bits must equal D = {D}, got {bits}")
-        if int(np.diff(local.offsets).max(initial=0)) > MAX_ROWS:
-            raise NotImplementedError(f"an image of more than {MAX_ROWS} rows cannot be indexed")
+        _check_rows(local.offsets)
         ctx = local.ctx
         if on_device:
             return cls._build_on_device(local, cent, sel, bits, alpha, tau, idf, projection, desc_kind, ctx, extractor, weights)
@@ -567,8 +590,7 @@ class ASMKIndex:
             if p in have:
                 raise ValueError(f"{p!r} is already in the index (or named twice)")
             have.add(p)
-        if int(np.diff(off).max(initial=0)) > MAX_ROWS:
-            raise NotImplementedError(f"an image of more than {MAX_ROWS} rows cannot be indexed")
+        _check_rows(off)
         return paths, off, source, rows
 
     def _file_buffers(self, cap):
@@ -580,8 +602,7 @@ class ASMKIndex:
         sp, self._spare = self._spare, None
         if sp is None or sp["cap"] < need:
             if sp is not None:
-                for name in ("word_off", "ent_img", "ent_sig"):
-                    sp[name].free()
+                _free_file(sp)
             sp = self._file_buffers(max(need, 2 * self._cap_e if need > self._cap_e else self._cap_e, 1))
         return sp
 
@@ -612,8 +633,7 @@ class ASMKIndex:
             ctx.copy_dev(out["ent_sig"].ptr, dev["ent_sig"].ptr, E * 4 * W)
             self._swap(out)
             sp, self._spare = self._spare, None
-            for name in ("word_off", "ent_img", "ent_sig"):
-                sp[name].free()
+            _free_file(sp)
         return self
 
     def add(self, source=None, rows_list=None, *args, **kwargs):
@@ -633,7 +653,7 @@ class ASMKIndex:
         K, N, E = self.n_words, len(self._paths), int(self.word_off[-1])
         with ctx.scratch() as tmp:
             d_rows = local.rows.ptr if local is not None else tmp.upload(rows).ptr
-            d_proj = dev["projection"].ptr if dev["projection"] is not None else None
+            d_proj = _proj_ptr(dev["projection"])
             got = device_invert(ctx, tmp, dev["cb"], d_rows, off, self.desc_kind, d_proj, self.bits, img_base=N)
             new_off = got["word_off"]
             b = int(new_off[-1])
@@ -728,8 +748,7 @@ class ASMKIndex:
             self._dev = None
             self._cap_e = self._cap_n = 0
         if self._spare is not None:
-            for name in ("word_off", "ent_img", "ent_sig"):
-                self._spare[name].free()
+            _free_file(self._spare)
             self._spare = None
 
     def __enter__(self):
@@ -747,8 +766,7 @@ class ASMKIndex:
         """entries of query images whose rows are on the device -> (ent_off, words, sigs); `ma`: words per row (1..min(8, n_words))"""
         ma = check_ma(ma, self.n_words, offsets)
         dev = self._resident()
-        return device_entries(self.ctx, dev["cb"], d_rows, offsets, self.desc_kind,
-                              dev["projection"].ptr if dev["projection"] is not None else None, self.bits, ma)
+        return device_entries(self.ctx, dev["cb"], d_rows, offsets, self.desc_kind, _proj_ptr(dev["projection"]), self.bits, ma)
 
     def _query_arrays(self, ent_off, words, sigs):
         ent_off = np.ascontiguousarray(ent_off, dtype=np.int64)
@@ -793,9 +811,7 @@ class ASMKIndex:
         host, and gamma(Q), like the 2^32 guard, needs the weight sum the expansion found."""
         ent_off, words, sigs = self._query_arrays(ent_off, words, sigs)
         nq, N = len(ent_off) - 1, len(self)
-        if isinstance(k, bool) or int(k) != k or k < 1:
-            raise ValueError(f"k must be a positive integer, got {k!r}")
-        k = int(k)
+        k = _check_k(k)
         if expand is not None:
             return self._rank_expanded(ent_off, words, sigs, k, expand, slice_images)
         sums = self._query_sums(ent_off, words)
@@ -903,8 +919,7 @@ class ASMKIndex:
             raise TypeError("expand must be a pvsim.ASMKExpansion")
         if isinstance(min_inliers, bool) or int(min_inliers) != min_inliers or min_inliers < 0:
             raise ValueError(f"min_inliers must be a non-negative integer, got {min_inliers!r}")
-        if isinstance(k, bool) or int(k) != k or k < 1:
-            raise ValueError(f"k must be a positive integer, got {k!r}")
+        k = _check_k(k)
         ma = check_ma(ma, self.n_words)
         ranked = list(ranked)
         verified = [path for path, _, inliers in ranked if inliers >= min_inliers][:expand.n]
@@ -927,10 +942,9 @@ class ASMKIndex:
         D = self.centroids.shape[1]
         dt = _row_dtype(self.desc_kind)
         rows_list = [np.ascontiguousarray(r, dtype=dt).reshape(-1, D) for r in rows_list]
-        if any(len(r) > MAX_ROWS for r in rows_list):
-            raise NotImplementedError(f"a query of more than {MAX_ROWS} rows is not supported")
         off = np.zeros(len(rows_list) + 1, np.int64)
         np.cumsum([len(r) for r in rows_list], out=off[1:])
+        _check_rows(off, query=True)
         total = int(off[-1])
         check_ma(ma, self.n_words, off)
         with self.ctx.scratch() as tmp:
@@ -945,8 +959,7 @@ class ASMKIndex:
             raise ValueError("images are extracted as uint8 rows: the index must read DESC_U8_ROOTSIFT")
         q = LocalFeatureIndex.from_images(list(images), self.extractor, ctx=self.ctx)
         try:
-            if int(np.diff(q.offsets).max(initial=0)) > MAX_ROWS:
-                raise NotImplementedError(f"a query of more than {MAX_ROWS} rows is not supported")
+            _check_rows(q.offsets, query=True)
             return self.query_entries(q.rows.ptr, q.offsets, ma)
         finally:
             q.close()

@@ -63,7 +63,10 @@ INVERT_CASES = [  # n, E, K, W, flavor, img_base
     (0, 0, 5, 1, "random", 0), (1, 0, 5, 2, "random", 0), (1, 1, 1, 1, "random", 1000), (3, 1, 2, 3, "random", 0),
     (3, 255, 255, 4, "random", 0), (3, 256, 256, 2, "bad", 1000), (3, 257, 257, 1, "random", 0), (40, 0, 7, 4, "random", 0),
     (40, 36, 1, 3, "random", 1000), (40, 72, 2, 2, "random", 0), (40, 1000, 256, 3, "bad", 0), (40, 1000, 257, 1, "shared", 1000),
-    (40, 1000, 1000, 4, "shared", 0), (40, 1000, 65536, 4, "distinct", 1000), (40, 1000, 65536, 2, "bad", 0)]
+    (40, 1000, 1000, 4, "shared", 0), (40, 1000, 65536, 4, "distinct", 1000), (40, 1000, 65536, 2, "bad", 0),
+    # the digit counts of a pass over tiles of 256 are more than one scan block of 2048, and more than 256 of them
+    (40, 2000, 65536, 2, "random", 0), (40, 523000, 65536, 1, "random", 1000)]
+SCAN_BLOCK = 2048                                                                 # counts one workgroup of the int32 scan takes
 
 
 @pytest.mark.parametrize("n,E,K,W,flavor,img_base", INVERT_CASES)
@@ -77,6 +80,11 @@ def test_invert_and_weight_sums_match_the_twin(gpu_ctx, n, E, K, W, flavor, img_
         assert total > 3 * 256                                                    # lists cross at least three tiles of 256
     if K == 65536:
         assert want[0][1] >= 1 and want[0][K] - want[0][K - 1] >= 1              # words 0 and 65535 are held
+    ncounts = 257 * -(-total // 256)                                              # digit counts of a pass at tile 256
+    if E == 2000:
+        assert SCAN_BLOCK < ncounts <= 2 * SCAN_BLOCK                             # two scan blocks: a non-zero partial is applied
+    if E == 523000:
+        assert ncounts > 256 * SCAN_BLOCK                                         # 257 scan blocks: the partials carry between two rounds
     for tile in (256, 512, 0):
         word_off, img, osig = _invert(gpu_ctx, off, count, word, sig, K, W, img_base, tile)
         assert np.array_equal(word_off, want[0]), tile
@@ -202,6 +210,41 @@ def test_insert_and_remove_match_the_twin_and_a_rebuild(gpu_ctx, K, W):
                 out.free()
     finally:
         stored.free()
+
+
+@pytest.mark.parametrize("E", [2048, 524288])
+def test_remove_across_scan_blocks(gpu_ctx, E):
+    """E + 1 survivor flags are 2 and 257 blocks of the int32 scan: a non-zero partial is applied, and the scan of the partials
+    carries from its first round of 256 into a second.  Every word stores a sorted random subset of the images; 1000 are removed."""
+    K, W, N = 300, 1, 4096
+    assert -(-(E + 1) // SCAN_BLOCK) == (2 if E == 2048 else 257)                 # the test's own input
+    rng = np.random.RandomState(1960 + E % 1000)
+    sizes = np.full(K, E // K) + (np.arange(K) < E % K)
+    assert sizes.sum() == E and sizes.max() <= N
+    word_off = np.zeros(K + 1, np.int64)
+    np.cumsum(sizes, out=word_off[1:])
+    img = np.concatenate([np.sort(rng.permutation(N)[:c]) for c in sizes]).astype(np.int32)
+    sig = rng.randint(0, 1 << 32, (E, W), dtype=np.uint64).astype(np.uint32)
+    keep = np.ones(N, np.uint8)
+    keep[rng.permutation(N)[:1000]] = 0
+    pos = up.keep_positions(keep)
+    want = up.remove(word_off, img, sig, keep, pos)
+    left = keep[img] != 0
+    S = int(left.sum())
+    assert 0 < S < E and np.array_equal(want[1], pos[img[left]]) and np.array_equal(want[2], sig[left])
+    assert np.array_equal(want[0], np.concatenate([[0], np.cumsum(left)])[word_off])
+    stored = _File(gpu_ctx, (word_off, img, sig))
+    out = _File(gpu_ctx, (np.zeros(K + 1, np.int64), np.zeros(0, np.int32), np.zeros((0, W), np.uint32)), cap=E)
+    d_keep, d_pos = _up(gpu_ctx, keep), _up(gpu_ctx, pos)
+    try:
+        gpu_ctx.asmk_remove_dev(K, 32 * W, N, stored.d_off.ptr, word_off, stored.d_img.ptr, stored.d_sig.ptr, d_keep.ptr, d_pos.ptr,
+                                out.d_off.ptr, out.d_img.ptr, out.d_sig.ptr)
+        got_off, got_img, got_sig = out.read(E)
+        assert _same((got_off, got_img[:S], got_sig[:S]), want)
+        assert (got_img[S:].view(np.uint32) == FILL32).all() and (got_sig[S:] == FILL32).all()   # nothing is written beyond the survivors
+    finally:
+        for f in (stored, out, d_keep, d_pos):
+            f.free()
 
 
 def test_overlapping_buffers_are_refused(gpu_ctx):

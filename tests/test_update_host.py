@@ -279,6 +279,26 @@ def test_device_index_update_validation_touches_no_device():
     assert index._pending == [] and index._mirror_rows == 3 and index._hbuf.shape[0] == 3
 
 
+def test_list_core_host_rules(tmp_path):
+    """csrc/bench/list_common_check.cpp includes only list_common.hpp and runs as a stand-alone program under the address and
+    undefined-behaviour sanitizers (nothing is loaded into Python): byte ranges that touch, share a byte or are null or empty; the
+    offset predicates on good and bad arrays; the score slice, the expand tile and the invert tile against the expressions the entry
+    points carried inline, over a grid of inputs, with the invariants the kernels rely on."""
+    import os
+    import shutil
+    import subprocess
+    from conftest import REPO
+    src = os.path.join(REPO, "python-visual-similarity_amd", "csrc", "bench", "list_common_check.cpp")
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler (g++, c++ or clang++) on PATH"
+    exe = str(tmp_path / "list_common_check")
+    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", "-o", exe, src], capture_output=True, text=True, timeout=300)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
+
+
 def test_header_binding_and_constants_agree():
     import os
     import re
