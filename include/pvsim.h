@@ -634,6 +634,50 @@ int pvs_diffuse_cg_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_s, in
  * float64 [nq][k].  Timed on slot 3. */
 int pvs_rank_f64_dev(pvs_ctx* ctx, const double* d_scores, int64_t nq, int64_t ncols, int64_t ld, int k, int64_t* d_idx, double* d_val);
 
+/* ---------------------------------------------------------------- graph maintenance after add / remove
+ * A MUTABLE graph keeps, beside nbr and s, the forward similarities sim float32 [N][kg]: the values the ranking returned, in list
+ * order.  The LIST of row i is the first kg rows j != i of row i's ranking, in the order of the top-k block above: score descending,
+ * index ascending, NaN after every number, -0 and +0 tie.  drop self on a ranking to depth kg + 1 gives exactly that list.  After an
+ * add or a remove every list is brought to the one a ranking of the updated index gives, by the entry points below; a, w, deg, r and s
+ * are then derived again from sim by the rules of the GRAPH block.  float32 similarities only: see DESIGN.md for why a float64 score is
+ * not a function of its two rows alone.
+ *   lists     drop self with the similarity kept: row p of the rankings belongs to row own = row0 + p, or ids[p] where an id array is
+ *             given.  The first slot holding own leaves, or the last slot where there is none; the other kg slots go, in order, to
+ *             row own of nbr (an index outside [0, N) is stored as -1) and of sim (the value as it stands).  A row whose own lies
+ *             outside [0, N) is not written.
+ *   merge     per row, the stored list (kg entries, in list order) and c candidates (idx int64 [rows][c] relative to col_offset, val
+ *             float32, in list order; a candidate with idx < 0 is skipped, the others get the id idx + col_offset) are merged: entry x
+ *             comes before entry y iff x is a number and y a NaN, or both are numbers and x > y, or they tie (both NaN, or equal as
+ *             numbers) and the id of x is smaller; where neither comes before the other the stored entry goes first.  The first kg
+ *             entries of the merged sequence are written, ids as int32, values moved as they stand.  1 <= c.
+ *   damage    flag[i] = 1 iff keep[i] != 0 and some slot of row i names a row j in [0, N) with keep[j] == 0; 0 otherwise.
+ *   remap     out[i][t] = pos[nbr[i][t]] where keep[i] != 0, nbr[i][t] lies in [0, N) and keep[nbr[i][t]] != 0; -1 in the other slots
+ *             of a kept row; the rows with keep[i] == 0 are not written.  pos is monotone, so a list that named no removed row stays
+ *             in list order.  d_out may be d_nbr itself.
+ *   gather    out[p] = rows[ids[p]], rows of row_bytes bytes (a multiple of 4) moved as they stand; a row whose id lies outside [0, n)
+ *             is written as zeros.  It puts the damaged rows side by side, so that they can be ranked as one block of queries.
+ *   affinity  a[i][t] = the affinity of the GRAPH block of float64(sim[i][t]): the same product, the same bits as
+ *             pvs_graph_affinity_dev gives for the same value.
+ * Integer work, comparisons and data movement (and the affinity's products); one lane per row or per entry, every output element
+ * written once, no atomics.  Arguments are checked on the host before anything is launched, as in the block above; zero rows are a
+ * no-op.  Enqueued on the context's stream, timed on slot 6. */
+/* d_idx int64 [b][kg + 1], d_val float32 [b][kg + 1]; d_ids int64 [b] or NULL (then own = row0 + p, and row0 + b <= N is required;
+ * with d_ids, row0 is ignored) -> rows `own` of d_nbr int32 [N][kg] and d_sim float32 [N][kg]. */
+int pvs_graph_lists_dev(pvs_ctx* ctx, const int64_t* d_idx, const float* d_val, int64_t b, int kg, int64_t row0, const int64_t* d_ids,
+                        int64_t N, int32_t* d_nbr, float* d_sim);
+/* d_nbr int32 / d_sim float32 [rows][kg] (the stored rows), d_cidx int64 / d_cval float32 [rows][c] -> d_out_nbr int32 / d_out_sim
+ * float32 [rows][kg], disjoint from every input.  An id outside [0, N) is stored as -1.  2 <= N < 2^31, 1 <= kg <= N - 1. */
+int pvs_graph_merge_dev(pvs_ctx* ctx, const int32_t* d_nbr, const float* d_sim, const int64_t* d_cidx, const float* d_cval, int64_t rows,
+                        int kg, int c, int64_t col_offset, int64_t N, int32_t* d_out_nbr, float* d_out_sim);
+/* d_nbr int32 [N][kg], d_keep uint8 [N] -> d_flag uint8 [N] */
+int pvs_graph_damage_dev(pvs_ctx* ctx, const int32_t* d_nbr, int64_t N, int kg, const uint8_t* d_keep, uint8_t* d_flag);
+/* d_keep uint8 [N], d_pos int64 [N + 1] (pvs_keep_mask_dev / pvs_keep_positions_dev) -> d_out int32 [N][kg], old numbering of rows */
+int pvs_graph_remap_dev(pvs_ctx* ctx, const int32_t* d_nbr, int64_t N, int kg, const uint8_t* d_keep, const int64_t* d_pos, int32_t* d_out);
+/* d_rows [n][row_bytes], d_ids int64 [b] -> d_out [b][row_bytes], disjoint from both.  n >= 1; b == 0 is a no-op. */
+int pvs_graph_gather_rows_dev(pvs_ctx* ctx, const void* d_rows, int64_t n, int64_t row_bytes, const int64_t* d_ids, int64_t b, void* d_out);
+/* d_sim float32 [N][kg] -> d_a float64 [N][kg]; integer 0 <= gamma <= 8 */
+int pvs_graph_affinity_sim_dev(pvs_ctx* ctx, const float* d_sim, int64_t N, int kg, int gamma, double* d_a);
+
 /* ---------------------------------------------------------------- local-descriptor retrieval: ASMK* 
  * The aggregated selective match kernel with binary signatures (Tolias, Avrithis, Jegou, ICCV 2013; Hamming embedding: Jegou,
  * Douze, Schmid, ECCV 2008): a large vocabulary, per image and visual word ONE B-bit signature of the summed residual, an inverted

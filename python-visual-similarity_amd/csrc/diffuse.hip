@@ -5,7 +5,9 @@
 //
 // The graph is fixed-width rows (ELL): nbr int32 [N][kg] and s float64 [N][kg]; a slot that is not mutual holds s = +0 and adds
 // nothing.  The four graph kernels (drop self + affinity, the mutual pass, degrees, normalised entries) are one lane per entry or per
-// row; none of them is a throughput path.
+// row; none of them is a throughput path.  The five maintenance kernels of a mutable graph (lists with the
+// similarity kept, the merge of stored lists with candidates, damage flags, the remap through the keep positions, affinities from
+// stored similarities) are of the same kind: integer work, comparisons and moves, every output element written once.
 //
 // The solver is conjugate gradients on (I - alpha S) x = y for C columns at once.  Vectors are [N][C], columns innermost, so the values
 // of one neighbour for a tile of columns are one contiguous read.  One workgroup owns one block of 256 rows -- the block of the dot
@@ -116,6 +118,126 @@ __global__ __launch_bounds__(DF_THREADS) void df_rhs_kernel(const int64_t* __res
   const int64_t c = e / kq;
   const int64_t j = idx[e];
   if (j >= 0 && j < N) Y[j * C + c] = df_affinity((double)val[e], gamma);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- graph maintenance
+//   one lane per output entry: drop self as df_affinity_kernel, the similarity kept; a row's own number comes
+// from ids where given.  A row whose own number leaves [0, N) writes nothing.
+__global__ __launch_bounds__(DF_THREADS) void df_lists_kernel(const int64_t* __restrict__ idx, const float* __restrict__ val, int64_t b, int kg,
+                                                              int64_t row0, const int64_t* __restrict__ ids, int64_t N,
+                                                              int32_t* __restrict__ nbr, float* __restrict__ sim) {
+  const int64_t e = (int64_t)blockIdx.x * DF_THREADS + threadIdx.x;
+  if (e >= b * kg) return;
+  const int64_t p = e / kg;
+  const int t = (int)(e - p * kg);
+  const int64_t own = ids ? ids[p] : row0 + p;
+  if (own < 0 || own >= N) return;
+  const int64_t* li = idx + p * (kg + 1);
+  int drop = kg;
+  for (int u = 0; u <= kg; ++u)
+    if (li[u] == own) {
+      drop = u;
+      break;
+    }
+  const int src = t < drop ? t : t + 1;
+  const int64_t j = li[src];
+  const int64_t o = own * kg + t;
+  nbr[o] = (j >= 0 && j < N) ? (int32_t)j : -1;
+  sim[o] = val[p * (kg + 1) + src];
+}
+
+// the order of the lists: numbers before NaNs, larger before smaller (-0 and +0 tie), then the smaller id
+__device__ __forceinline__ bool df_before(float xv, int64_t xid, float yv, int64_t yid) {
+  const bool xn = xv != xv, yn = yv != yv;
+  if (xn != yn) return yn;
+  if (!xn) {
+    if (xv > yv) return true;
+    if (xv < yv) return false;
+  }
+  return xid < yid;
+}
+
+// one lane per row: a two-way merge of the stored list and the candidates, cut after kg entries; t entries out means at most t
+// stored ones taken, so the stored list never runs out
+__global__ __launch_bounds__(DF_THREADS) void df_merge_kernel(const int32_t* __restrict__ nbr, const float* __restrict__ sim,
+                                                              const int64_t* __restrict__ cidx, const float* __restrict__ cval, int64_t rows,
+                                                              int kg, int c, int64_t col_offset, int64_t N, int32_t* __restrict__ onbr,
+                                                              float* __restrict__ osim) {
+  const int64_t i = (int64_t)blockIdx.x * DF_THREADS + threadIdx.x;
+  if (i >= rows) return;
+  const int32_t* ln = nbr + i * kg;
+  const float* ls = sim + i * kg;
+  const int64_t* ci = cidx + i * c;
+  const float* cv = cval + i * c;
+  int p = 0, q = 0;
+  for (int t = 0; t < kg; ++t) {
+    while (q < c && ci[q] < 0) ++q;
+    const int32_t sj = ln[p];
+    const float sv = ls[p];
+    int64_t cj = 0;
+    float cs = 0.f;
+    bool take = false;
+    if (q < c) {
+      cj = ci[q] + col_offset;
+      cs = cv[q];
+      take = df_before(cs, cj, sv, (int64_t)sj);
+    }
+    if (take) {
+      onbr[i * kg + t] = (cj >= 0 && cj < N) ? (int32_t)cj : -1;
+      osim[i * kg + t] = cs;
+      ++q;
+    } else {
+      onbr[i * kg + t] = sj;
+      osim[i * kg + t] = sv;
+      ++p;
+    }
+  }
+}
+
+// one lane per row
+__global__ __launch_bounds__(DF_THREADS) void df_damage_kernel(const int32_t* __restrict__ nbr, int64_t N, int kg,
+                                                               const uint8_t* __restrict__ keep, uint8_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * DF_THREADS + threadIdx.x;
+  if (i >= N) return;
+  uint8_t f = 0;
+  if (keep[i] != 0)
+    for (int t = 0; t < kg; ++t) {
+      const int32_t j = nbr[i * kg + t];
+      if (j >= 0 && j < N && keep[j] == 0) {
+        f = 1;
+        break;
+      }
+    }
+  flag[i] = f;
+}
+
+// one lane per entry; a lane reads the entry it writes, so out may be nbr itself
+__global__ __launch_bounds__(DF_THREADS) void df_remap_kernel(const int32_t* nbr, int64_t N, int kg, const uint8_t* __restrict__ keep,
+                                                              const int64_t* __restrict__ pos, int32_t* out) {
+  const int64_t e = (int64_t)blockIdx.x * DF_THREADS + threadIdx.x;
+  if (e >= N * kg) return;
+  const int64_t i = e / kg;
+  if (keep[i] == 0) return;
+  const int32_t j = nbr[e];
+  out[e] = (j >= 0 && j < N && keep[j] != 0) ? (int32_t)pos[j] : -1;
+}
+
+// one lane per 4-byte word of the output: out[p] = rows[ids[p]], zeros where the id leaves [0, n)
+__global__ __launch_bounds__(DF_THREADS) void df_gather_rows_kernel(const uint32_t* __restrict__ rows, int64_t n, int64_t words,
+                                                                    const int64_t* __restrict__ ids, int64_t b, uint32_t* __restrict__ out) {
+  const int64_t e = (int64_t)blockIdx.x * DF_THREADS + threadIdx.x;
+  if (e >= b * words) return;
+  const int64_t p = e / words;
+  const int64_t w = e - p * words;
+  const int64_t i = ids[p];
+  out[e] = (i >= 0 && i < n) ? rows[i * words + w] : 0u;
+}
+
+__global__ __launch_bounds__(DF_THREADS) void df_affinity_sim_kernel(const float* __restrict__ sim, int64_t n, int gamma,
+                                                                     double* __restrict__ a) {
+  const int64_t e = (int64_t)blockIdx.x * DF_THREADS + threadIdx.x;
+  if (e >= n) return;
+  a[e] = df_affinity((double)sim[e], gamma);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- solver
@@ -473,6 +595,161 @@ PVS_EXPORT int pvs_graph_normalise_dev(pvs_ctx* ctx, const int32_t* d_nbr, const
   PVS_HIP(hipSetDevice(ctx->device));
   ScopedTimer tm(ctx, T_MISC);
   hipLaunchKernelGGL(df_normalise_kernel, dim3(df_grid(N * kg)), dim3(DF_THREADS), 0, ctx->stream, d_nbr, d_w, d_r, N, kg, d_s);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+// ---- graph maintenance
+PVS_EXPORT int pvs_graph_lists_dev(pvs_ctx* ctx, const int64_t* d_idx, const float* d_val, int64_t b, int kg, int64_t row0,
+                                   const int64_t* d_ids, int64_t N, int32_t* d_nbr, float* d_sim) {
+  PVS_NEED(ctx, "ctx");
+  PVS_TRY(df_check_graph_shape(__func__, N, kg));
+  if (b < 0 || b > N) PVS_FAIL(PVS_ERR_INVALID, "%s: need 0 <= b <= N (got b=%lld, N=%lld)", __func__, (long long)b, (long long)N);
+  if (!d_ids && (row0 < 0 || row0 + b > N))
+    PVS_FAIL(PVS_ERR_INVALID, "%s: rows [%lld, %lld) leave the index of %lld rows", __func__, (long long)row0, (long long)(row0 + b), (long long)N);
+  if (b == 0) return PVS_OK;
+  PVS_NEED(d_idx, "idx");
+  PVS_NEED(d_val, "val");
+  PVS_NEED(d_nbr, "nbr");
+  PVS_NEED(d_sim, "sim");
+  PVS_ALIGNED(d_idx, 8, "idx");
+  PVS_ALIGNED(d_val, 4, "val");
+  PVS_ALIGNED(d_nbr, 4, "nbr");
+  PVS_ALIGNED(d_sim, 4, "sim");
+  PVS_ALIGNED(d_ids, 8, "ids");   // NULL passes
+  const size_t in_n = (size_t)b * (kg + 1), out_b = (size_t)N * kg * 4;
+  struct Range {
+    const void* p;
+    size_t n;
+  } ins[] = {{d_idx, in_n * 8}, {d_val, in_n * 4}, {d_ids, d_ids ? (size_t)b * 8 : 0}};
+  for (const Range& r : ins)
+    if (r.n && (ranges_overlap(r.p, r.n, d_nbr, out_b) || ranges_overlap(r.p, r.n, d_sim, out_b)))
+      PVS_FAIL(PVS_ERR_INVALID, "%s: an output overlaps an input", __func__);
+  if (ranges_overlap(d_nbr, out_b, d_sim, out_b)) PVS_FAIL(PVS_ERR_INVALID, "%s: nbr overlaps sim", __func__);
+  PVS_HIP(hipSetDevice(ctx->device));
+  ScopedTimer tm(ctx, T_MISC);
+  hipLaunchKernelGGL(df_lists_kernel, dim3(df_grid(b * kg)), dim3(DF_THREADS), 0, ctx->stream, d_idx, d_val, b, kg, row0, d_ids, N, d_nbr,
+                     d_sim);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_graph_merge_dev(pvs_ctx* ctx, const int32_t* d_nbr, const float* d_sim, const int64_t* d_cidx, const float* d_cval,
+                                   int64_t rows, int kg, int c, int64_t col_offset, int64_t N, int32_t* d_out_nbr, float* d_out_sim) {
+  PVS_NEED(ctx, "ctx");
+  PVS_TRY(df_check_graph_shape(__func__, N, kg));
+  if (rows < 0 || rows > N) PVS_FAIL(PVS_ERR_INVALID, "%s: need 0 <= rows <= N (got rows=%lld, N=%lld)", __func__, (long long)rows, (long long)N);
+  if (c < 1 || c > N) PVS_FAIL(PVS_ERR_INVALID, "%s: need 1 <= c <= N candidates per row (got c=%d)", __func__, c);
+  if (col_offset < 0 || col_offset >= N)
+    PVS_FAIL(PVS_ERR_INVALID, "%s: need 0 <= col_offset < N (got %lld, N=%lld)", __func__, (long long)col_offset, (long long)N);
+  if (rows == 0) return PVS_OK;
+  PVS_NEED(d_nbr, "nbr");
+  PVS_NEED(d_sim, "sim");
+  PVS_NEED(d_cidx, "cidx");
+  PVS_NEED(d_cval, "cval");
+  PVS_NEED(d_out_nbr, "out_nbr");
+  PVS_NEED(d_out_sim, "out_sim");
+  PVS_ALIGNED(d_nbr, 4, "nbr");
+  PVS_ALIGNED(d_sim, 4, "sim");
+  PVS_ALIGNED(d_cidx, 8, "cidx");
+  PVS_ALIGNED(d_cval, 4, "cval");
+  PVS_ALIGNED(d_out_nbr, 4, "out_nbr");
+  PVS_ALIGNED(d_out_sim, 4, "out_sim");
+  const size_t lb = (size_t)rows * kg * 4, cn = (size_t)rows * c;
+  struct Range {
+    const void* p;
+    size_t n;
+  } ins[] = {{d_nbr, lb}, {d_sim, lb}, {d_cidx, cn * 8}, {d_cval, cn * 4}};
+  for (const Range& r : ins)
+    if (ranges_overlap(r.p, r.n, d_out_nbr, lb) || ranges_overlap(r.p, r.n, d_out_sim, lb))
+      PVS_FAIL(PVS_ERR_INVALID, "%s: an output overlaps an input", __func__);
+  if (ranges_overlap(d_out_nbr, lb, d_out_sim, lb)) PVS_FAIL(PVS_ERR_INVALID, "%s: out_nbr overlaps out_sim", __func__);
+  PVS_HIP(hipSetDevice(ctx->device));
+  ScopedTimer tm(ctx, T_MISC);
+  hipLaunchKernelGGL(df_merge_kernel, dim3(df_grid(rows)), dim3(DF_THREADS), 0, ctx->stream, d_nbr, d_sim, d_cidx, d_cval, rows, kg, c,
+                     col_offset, N, d_out_nbr, d_out_sim);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_graph_damage_dev(pvs_ctx* ctx, const int32_t* d_nbr, int64_t N, int kg, const uint8_t* d_keep, uint8_t* d_flag) {
+  PVS_NEED(ctx, "ctx");
+  PVS_TRY(df_check_graph_shape(__func__, N, kg));
+  PVS_NEED(d_nbr, "nbr");
+  PVS_NEED(d_keep, "keep");
+  PVS_NEED(d_flag, "flag");
+  PVS_ALIGNED(d_nbr, 4, "nbr");
+  if (ranges_overlap(d_flag, (size_t)N, d_nbr, (size_t)N * kg * 4) || ranges_overlap(d_flag, (size_t)N, d_keep, (size_t)N))
+    PVS_FAIL(PVS_ERR_INVALID, "%s: flag overlaps an input", __func__);
+  PVS_HIP(hipSetDevice(ctx->device));
+  ScopedTimer tm(ctx, T_MISC);
+  hipLaunchKernelGGL(df_damage_kernel, dim3(df_grid(N)), dim3(DF_THREADS), 0, ctx->stream, d_nbr, N, kg, d_keep, d_flag);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_graph_remap_dev(pvs_ctx* ctx, const int32_t* d_nbr, int64_t N, int kg, const uint8_t* d_keep, const int64_t* d_pos,
+                                   int32_t* d_out) {
+  PVS_NEED(ctx, "ctx");
+  PVS_TRY(df_check_graph_shape(__func__, N, kg));
+  PVS_NEED(d_nbr, "nbr");
+  PVS_NEED(d_keep, "keep");
+  PVS_NEED(d_pos, "pos");
+  PVS_NEED(d_out, "out");
+  PVS_ALIGNED(d_nbr, 4, "nbr");
+  PVS_ALIGNED(d_pos, 8, "pos");
+  PVS_ALIGNED(d_out, 4, "out");
+  const size_t nb = (size_t)N * kg * 4;
+  if ((d_out != d_nbr && ranges_overlap(d_out, nb, d_nbr, nb)) || ranges_overlap(d_out, nb, d_keep, (size_t)N) ||
+      ranges_overlap(d_out, nb, d_pos, (size_t)(N + 1) * 8))
+    PVS_FAIL(PVS_ERR_INVALID, "%s: out overlaps an input (only out == nbr is served in place)", __func__);
+  PVS_HIP(hipSetDevice(ctx->device));
+  ScopedTimer tm(ctx, T_MISC);
+  hipLaunchKernelGGL(df_remap_kernel, dim3(df_grid(N * kg)), dim3(DF_THREADS), 0, ctx->stream, d_nbr, N, kg, d_keep, d_pos, d_out);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_graph_gather_rows_dev(pvs_ctx* ctx, const void* d_rows, int64_t n, int64_t row_bytes, const int64_t* d_ids, int64_t b,
+                                         void* d_out) {
+  PVS_NEED(ctx, "ctx");
+  if (n < 1 || b < 0 || row_bytes < 4 || row_bytes % 4 != 0)
+    PVS_FAIL(PVS_ERR_INVALID, "%s: need n >= 1, b >= 0 and rows of a multiple of 4 bytes (got n=%lld, b=%lld, row_bytes=%lld)", __func__,
+             (long long)n, (long long)b, (long long)row_bytes);
+  if ((double)n * (double)row_bytes > 9e18 || (double)b * (double)(row_bytes / 4) > 5e11)
+    PVS_FAIL(PVS_ERR_INVALID, "%s: the rows are too large", __func__);
+  if (b == 0) return PVS_OK;
+  PVS_NEED(d_rows, "rows");
+  PVS_NEED(d_ids, "ids");
+  PVS_NEED(d_out, "out");
+  PVS_ALIGNED(d_rows, 4, "rows");
+  PVS_ALIGNED(d_ids, 8, "ids");
+  PVS_ALIGNED(d_out, 4, "out");
+  const size_t ob = (size_t)b * (size_t)row_bytes;
+  if (ranges_overlap(d_out, ob, d_rows, (size_t)n * (size_t)row_bytes) || ranges_overlap(d_out, ob, d_ids, (size_t)b * 8))
+    PVS_FAIL(PVS_ERR_INVALID, "%s: out overlaps an input", __func__);
+  PVS_HIP(hipSetDevice(ctx->device));
+  ScopedTimer tm(ctx, T_MISC);
+  const int64_t words = row_bytes / 4;
+  hipLaunchKernelGGL(df_gather_rows_kernel, dim3(df_grid(b * words)), dim3(DF_THREADS), 0, ctx->stream, (const uint32_t*)d_rows, n, words,
+                     d_ids, b, (uint32_t*)d_out);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_graph_affinity_sim_dev(pvs_ctx* ctx, const float* d_sim, int64_t N, int kg, int gamma, double* d_a) {
+  PVS_NEED(ctx, "ctx");
+  PVS_TRY(df_check_graph_shape(__func__, N, kg));
+  if (gamma < 0 || gamma > DF_GAMMA_MAX) PVS_FAIL(PVS_ERR_INVALID, "%s: gamma must be in 0..%d (got %d)", __func__, DF_GAMMA_MAX, gamma);
+  PVS_NEED(d_sim, "sim");
+  PVS_NEED(d_a, "a");
+  PVS_ALIGNED(d_sim, 4, "sim");
+  PVS_ALIGNED(d_a, 8, "a");
+  const size_t n = (size_t)N * kg;
+  if (ranges_overlap(d_a, n * 8, d_sim, n * 4)) PVS_FAIL(PVS_ERR_INVALID, "%s: a overlaps sim", __func__);
+  PVS_HIP(hipSetDevice(ctx->device));
+  ScopedTimer tm(ctx, T_MISC);
+  hipLaunchKernelGGL(df_affinity_sim_kernel, dim3(df_grid((int64_t)n)), dim3(DF_THREADS), 0, ctx->stream, d_sim, (int64_t)n, gamma, d_a);
   PVS_HIP(hipGetLastError());
   return PVS_OK;
 }

@@ -147,6 +147,12 @@ SIGNATURES = {
     "pvs_diffuse_workspace": [_i64, _i64, C.POINTER(_sz)],
     "pvs_diffuse_cg_dev": [_vp, _vp, _vp, _i64, _int, _vp, _i64, C.c_double, C.c_double, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp],
     "pvs_rank_f64_dev": [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp],
+    "pvs_graph_lists_dev": [_vp, _vp, _vp, _i64, _int, _i64, _vp, _i64, _vp, _vp],
+    "pvs_graph_merge_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _i64, _i64, _vp, _vp],
+    "pvs_graph_damage_dev": [_vp, _vp, _i64, _int, _vp, _vp],
+    "pvs_graph_remap_dev": [_vp, _vp, _i64, _int, _vp, _vp, _vp],
+    "pvs_graph_gather_rows_dev": [_vp, _vp, _i64, _i64, _vp, _i64, _vp],
+    "pvs_graph_affinity_sim_dev": [_vp, _vp, _i64, _int, _int, _vp],
     "pvs_asmk_aggregate_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp],
     "pvs_asmk_aggregate_ma_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp],
     "pvs_asmk_score_dev": [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _i64],

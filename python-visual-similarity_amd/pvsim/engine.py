@@ -541,6 +541,34 @@ class Context:
         """pvs_rank_f64_dev: rows of float64 scores -> the k best columns by (score descending, column ascending, NaN last)"""
         check(_ffi.lib().pvs_rank_f64_dev(self.handle, ptr(d_scores), int(nq), int(ncols), int(ld), int(k), ptr(d_idx), ptr(d_val)))
 
+    # graph maintenance after add / remove (DESIGN.md section 20)
+    def graph_lists_dev(self, d_idx, d_val, b, kg, row0, N, d_nbr, d_sim, d_ids=None):
+        """pvs_graph_lists_dev: float32 lists (b, kg + 1) of rows row0.. (or of the rows d_ids int64 (b,) names) -> those rows of nbr
+        int32 (N, kg) and sim float32 (N, kg): drop self, the similarity kept"""
+        check(_ffi.lib().pvs_graph_lists_dev(self.handle, ptr(d_idx), ptr(d_val), int(b), int(kg), int(row0), ptr(d_ids), int(N), ptr(d_nbr),
+                                             ptr(d_sim)))
+
+    def graph_merge_dev(self, d_nbr, d_sim, d_cidx, d_cval, rows, kg, c, col_offset, N, d_out_nbr, d_out_sim):
+        """pvs_graph_merge_dev: stored lists (rows, kg) + candidates (rows, c) with ids cidx + col_offset -> the first kg of both"""
+        check(_ffi.lib().pvs_graph_merge_dev(self.handle, ptr(d_nbr), ptr(d_sim), ptr(d_cidx), ptr(d_cval), int(rows), int(kg), int(c),
+                                             int(col_offset), int(N), ptr(d_out_nbr), ptr(d_out_sim)))
+
+    def graph_damage_dev(self, d_nbr, N, kg, d_keep, d_flag):
+        """pvs_graph_damage_dev: flag uint8 (N,) = 1 for a kept row that lists a removed one"""
+        check(_ffi.lib().pvs_graph_damage_dev(self.handle, ptr(d_nbr), int(N), int(kg), ptr(d_keep), ptr(d_flag)))
+
+    def graph_remap_dev(self, d_nbr, N, kg, d_keep, d_pos, d_out):
+        """pvs_graph_remap_dev: the slots of the kept rows through pos (-1 for a removed neighbour); d_out may be d_nbr"""
+        check(_ffi.lib().pvs_graph_remap_dev(self.handle, ptr(d_nbr), int(N), int(kg), ptr(d_keep), ptr(d_pos), ptr(d_out)))
+
+    def graph_gather_rows_dev(self, d_rows, n, row_bytes, d_ids, b, d_out):
+        """pvs_graph_gather_rows_dev: out[p] = rows[ids[p]] for the b int64 ids (zeros for an id outside [0, n))"""
+        check(_ffi.lib().pvs_graph_gather_rows_dev(self.handle, ptr(d_rows), int(n), int(row_bytes), ptr(d_ids), int(b), ptr(d_out)))
+
+    def graph_affinity_sim_dev(self, d_sim, N, kg, gamma, d_a):
+        """pvs_graph_affinity_sim_dev: a float64 (N, kg) from the stored float32 similarities, the product of graph_affinity_dev"""
+        check(_ffi.lib().pvs_graph_affinity_sim_dev(self.handle, ptr(d_sim), int(N), int(kg), int(gamma), ptr(d_a)))
+
     # local-descriptor retrieval, ASMK* (DESIGN.md section 17)
     def asmk_aggregate_dev(self, cb, d_desc, kind, d_offsets, h_offsets, n_images, total_desc, d_labels, d_proj, bits, d_ent_word,
                            d_ent_sig, d_ent_count):

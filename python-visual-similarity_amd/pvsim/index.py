@@ -163,7 +163,9 @@ class DeviceIndex(Mapping):
     `add`, `remove` / `del index[path]` and `reserve` change the resident index without a rebuild: rows move
     on the device, and after any sequence of them every array and every ranking equals those of DeviceIndex(dict of the surviving
     rows in surviving order), bit for bit.  `modifications` counts them: a pvsim.Diffusion graph is a snapshot of the rows it was built
-    from and refuses to rank once the count has moved."""
+    from and refuses to rank once the count has moved.  A mutable graph (`Diffusion.build(index, mutable=True)`)
+    is updated THROUGH the graph: `g.add` / `g.remove` change this index and bring the graph along; an `add` or `remove` called here
+    directly makes a mutable graph as stale as any other."""
 
     def __init__(self, encoding_map, ctx=None):
         from .engine import default_context
@@ -355,6 +357,27 @@ class DeviceIndex(Mapping):
         else:
             self.ctx.cosine_topk_dev(d_q, nq, self._db.ptr, n, L, d_invq.ptr, self._inv.ptr, int(k), 0, False, d_idx.ptr, d_val.ptr)
         return d_invq, d_idx, d_val
+
+    def _rank_dev_range(self, tmp, d_q: int, nq: int, k: int, lo: int, hi: int):
+        """`_rank_dev_buffers` of a float32 index against the resident rows [lo, hi) alone, 1 <= k <= hi - lo: the same entry points,
+        the same 512-query rule, the norms at _inv + lo -> (idx int64 (nq, k) counted FROM lo, val (nq, k)), DeviceBuffers of `tmp`.
+        No entry point refuses the base of a sub-range: with L % 4 == 0 every row starts on 16 bytes, and any other L takes the
+        generic GEMM for every call, whatever the base (the filtered entry declines such rows and ranks them by the plain one), so a
+        score has the bits it has in a ranking of all rows and no aligned copy is staged.  `_last_range_stats`: what the filtered
+        entry reported for this call, None where the plain one ranked."""
+        n, L = self.shape
+        if self.dtype != np.float32 or not 0 <= lo < hi <= n or not 1 <= k <= hi - lo:
+            raise ValueError(f"a sub-range ranking needs a float32 index, 0 <= lo < hi <= {n} and 1 <= k <= hi - lo")
+        d_invq, d_idx, d_val = tmp(nq * 4), tmp(nq * k * 8), tmp(nq * k * 4)
+        self._row_inv_norms(d_q, nq, d_invq.ptr)
+        d_rows, d_inv = self._db.ptr + lo * L * 4, self._inv.ptr + lo * 4
+        self._last_range_stats = None
+        if nq >= 512:
+            self._last_range_stats = self.ctx.cosine_topk_filtered_dev(d_q, nq, d_rows, hi - lo, L, d_invq.ptr, d_inv, int(k), d_idx.ptr,
+                                                                       d_val.ptr)
+        else:
+            self.ctx.cosine_topk_dev(d_q, nq, d_rows, hi - lo, L, d_invq.ptr, d_inv, int(k), 0, False, d_idx.ptr, d_val.ptr)
+        return d_idx, d_val
 
     def _rank_dev(self, d_q: int, nq: int, k: int, want_inv: bool = False):
         """`rank` of nq rows of the index's dtype that are on the device (raw pointer) -> (idx, val[, 1 / ||q|| (nq,)])."""
