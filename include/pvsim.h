@@ -678,6 +678,76 @@ int pvs_graph_gather_rows_dev(pvs_ctx* ctx, const void* d_rows, int64_t n, int64
 /* d_sim float32 [N][kg] -> d_a float64 [N][kg]; integer 0 <= gamma <= 8 */
 int pvs_graph_affinity_sim_dev(pvs_ctx* ctx, const float* d_sim, int64_t N, int kg, int gamma, double* d_a);
 
+/* ---------------------------------------------------------------- k-reciprocal re-ranking on the kNN lists
+ * Zhong, Zheng, Cao, Li (CVPR 2017): a database image near the query whose own neighbourhood does not share the query's is demoted
+ * by the Jaccard distance of k-reciprocal neighbourhoods.  The LISTS are those of the block above: nbr int32 [N][kg] (a slot outside
+ * [0, N) holds -1 and takes part in nothing) and sim float32 [N][kg].  ALL weights are float64; every multiply, add and divide is
+ * rounded on its own, in the stated order.  1 <= k1 <= min(kg, 64), k1h = (k1 + 1) / 2, 1 <= k2 <= kg + 1, integer 0 <= gamma <= 8.
+ * The two DEPARTURES from the paper (truncation, weights) are what makes the result a function of the lists alone, to the bit.
+ *
+ *   back slot  u(i, t), with j = nbr[i][t]: the FIRST slot of row j that holds i, or none.
+ *   sets       R_k(i) = { t < k : u(i, t) exists and u(i, t) < k }.  mask1[i] holds R_k1(i), maskh[i] holds R_k1h(i), bit t for slot t.
+ *              B(i) = {i} + { nbr[i][t] : t in R_k1(i) };  H(j) = {j} + { nbr[j][t] : t in R_k1h(j) }.
+ *   expansion  E(i) = B(i) + every H(j) with j in B(i) \ {i} and 3 |H(j) & B(i)| > 2 |H(j)|: the paper's rule, tested against the
+ *              unexpanded B, so the order of j is immaterial.  Sets of ids: an id that sits in two slots counts once.
+ *   members    DEPARTURE 1: a member m of E(i) keeps a weight only if m = i or m sits in a slot of row i.  members[i][t] = 1 iff
+ *              nbr[i][t] is a member other than i and t is the first slot of row i that holds it, 0 otherwise; dropped[i] = the
+ *              number of members that are neither i nor in row i.  Every sparse vector lives on {i} + nbr[i][.]: kg + 1 wide.
+ *   weights    DEPARTURE 2: the weight of a member is the affinity of the GRAPH block of float64(sim[i][t]), of i itself exactly 1.
+ *              sum = +0, then + 1, then + the members' affinities for t ascending; v0[i] = 1 / sum, v[i][t] = affinity / sum, +0
+ *              in the slots that are not members.
+ *   V_j[m]     v0[j] when m = j; v[j][s] with s the first slot of row j that holds m; +0 otherwise.
+ *   expand     for m = i (w0[i]) and for m = nbr[i][t] (w[i][t]; +0 where the slot holds -1): acc = +0, then + V_j[m] for j = i,
+ *              nbr[i][0], .., nbr[i][k2 - 2] in that order, -1 slots skipped; the result is acc / float64(k2).  The sources are the
+ *              unexpanded V of all rows.  ws[i] = +0, then + w0[i], then + w[i][t] for t ascending.  k2 = 1 gives w = v to the bit.
+ *
+ * QUERY, from its ranking qidx int64 / qval float32 [kq] against the index, 1 <= kq <= min(N, PVS_KRR_MAX_KQ); an id outside [0, N)
+ * is an empty slot.  The query is not a database row and has no self entry.
+ *   B(q)       slot t < min(k1, kq) with g = qidx[t] is reciprocal iff slot k1 - 1 of row g does not hold -1 and
+ *              qval[t] >= sim[g][k1 - 1], compared as float32 (false for a NaN): the query would enter g's first k1.
+ *   E(q)       the expansion rule with the database's H; the members outside the query's own list are dropped and counted; a member
+ *              keeps its weight at the first slot of the list that holds it.
+ *   weights    sum = +0, then + the affinity of qval[t] over the member slots, t ascending; vq[t] = affinity / sum in the member
+ *              slots, +0 elsewhere, and +0 everywhere where the sum is not > 0.
+ *   expand     wq[t], m = qidx[t]: acc = +0, then + vq[first slot holding m], then + V_g[m] for g = qidx[0 .. k2 - 2] (those < kq,
+ *              empty slots skipped); wq[t] = acc / float64(k2), +0 in an empty slot.  sq = +0, then + wq[t] for t ascending.
+ * SCORE of candidate r < kr <= kq, c = qidx[r]:
+ *   m_sum      +0, then + min(wq[pos(c)], w0[c]), then for the slots s of row c ascending + min(wq[pos(m)], w[c][s]) with
+ *              m = nbr[c][s] -- only where m is an id other than c that row c holds at no earlier slot and that the query's list
+ *              holds; pos(m) is the first slot of the query's list that holds m.  min(a, b) is b where b < a, else a.
+ *   J          m_sum / ((sq + ws[c]) - m_sum), +0 where that denominator is not > 0 and for an empty slot c.
+ *   score      (1 - lambda) * J + lambda * float64(qval[r]), 0 <= lambda <= 1: 1 - lambda is formed in float64 on the host, the
+ *              two products are formed first and then added.
+ * The candidates are then ranked by pvs_rank_f64_dev on [nq][kr]: score descending, position in the first ranking ascending, NaN
+ * last.  lambda = 1 gives back the first ranking.
+ *
+ * One wave per row or per query for the sets; one workgroup per query and one wave per candidate for the score.  No atomics, every
+ * output element written once.  Arguments are checked on the host before anything is launched (PVS_ERR_INVALID: sizes out of the
+ * ranges above, a missing or misaligned pointer, arrays that overlap); zero queries are a no-op.  The masks handed to members and
+ * query must be those pvs_krr_sets_dev gave for the same nbr; whatever they hold, no read leaves the arrays.  Enqueued on the
+ * context's stream, timed on slot 6. */
+#define PVS_KRR_MAX_K1 64
+#define PVS_KRR_MAX_KQ 1024  /* depth of a query's first ranking: its list and vectors live in LDS */
+/* d_nbr int32 [N][kg] -> d_mask1, d_maskh uint64 [N] */
+int pvs_krr_sets_dev(pvs_ctx* ctx, const int32_t* d_nbr, int64_t N, int kg, int k1, uint64_t* d_mask1, uint64_t* d_maskh);
+/* -> d_members uint8 [N][kg], d_dropped int32 [N] */
+int pvs_krr_members_dev(pvs_ctx* ctx, const int32_t* d_nbr, const uint64_t* d_mask1, const uint64_t* d_maskh, int64_t N, int kg,
+                        uint8_t* d_members, int32_t* d_dropped);
+/* d_sim float32 [N][kg], d_members uint8 [N][kg] -> d_v float64 [N][kg], d_v0 float64 [N] */
+int pvs_krr_weights_dev(pvs_ctx* ctx, const float* d_sim, const uint8_t* d_members, int64_t N, int kg, int gamma, double* d_v, double* d_v0);
+/* -> d_w float64 [N][kg], d_w0, d_ws float64 [N] */
+int pvs_krr_expand_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_v, const double* d_v0, int64_t N, int kg, int k2, double* d_w,
+                       double* d_w0, double* d_ws);
+/* d_qidx int64 [nq][kq], d_qval float32 [nq][kq] -> d_wq float64 [nq][kq], d_sq float64 [nq], d_kept int32 [nq] (the members that sit
+ * in the query's list) and d_dropped int32 [nq] (those that do not) */
+int pvs_krr_query_dev(pvs_ctx* ctx, const int32_t* d_nbr, const float* d_sim, const uint64_t* d_maskh, const double* d_v, const double* d_v0,
+                      int64_t N, int kg, int k1, int k2, int gamma, const int64_t* d_qidx, const float* d_qval, int64_t nq, int kq,
+                      double* d_wq, double* d_sq, int32_t* d_kept, int32_t* d_dropped);
+/* -> d_scores float64 [nq][kr] */
+int pvs_krr_score_dev(pvs_ctx* ctx, const int32_t* d_nbr, const double* d_w, const double* d_w0, const double* d_ws, int64_t N, int kg,
+                      const int64_t* d_qidx, const float* d_qval, const double* d_wq, const double* d_sq, int64_t nq, int kq, int kr,
+                      double lam, double* d_scores);
+
 /* ---------------------------------------------------------------- local-descriptor retrieval: ASMK* 
  * The aggregated selective match kernel with binary signatures (Tolias, Avrithis, Jegou, ICCV 2013; Hamming embedding: Jegou,
  * Douze, Schmid, ECCV 2008): a large vocabulary, per image and visual word ONE B-bit signature of the summed residual, an inverted

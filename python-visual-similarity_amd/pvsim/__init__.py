@@ -8,6 +8,7 @@
     from pvsim import IVFCompactIndex                  # the same cut into inverted lists: a query scans nprobe of nlist lists
     from pvsim import QueryExpansion                   # query expansion / database-side augmentation on a DeviceIndex
     from pvsim import Diffusion                        # diffusion re-ranking on the kNN graph of a DeviceIndex
+    from pvsim import KReciprocal                      # k-reciprocal re-ranking on the kNN lists of a DeviceIndex
     from pvsim import ASMKIndex                        # local-descriptor retrieval: ASMK* with binary signatures, an inverted file
     from pvsim import ASMKExpansion                    # its query expansion: majority-vote signatures and words the results agree on
 
@@ -21,8 +22,9 @@ from ._errors import CapacityError
 from .compact import CompactIndex, IVFCompactIndex, ProductQuantizer
 from .expand import QueryExpansion
 from .diffusion import Diffusion
+from .reciprocal import KReciprocal
 from .asmk import ASMKExpansion, ASMKIndex
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion", "ASMKIndex", "ASMKExpansion"]
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion"]

@@ -30,6 +30,7 @@ OPT_UPDATE_WINDOW_ROWS = 6        # 0: windows of the in-place row compaction fr
 SCAN_TILE = 2048                  # PVS_SCAN_TILE of include/pvsim.h
 COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
 DIFFUSE_DOT_BLOCK, DIFFUSE_MAX_COLUMNS = 256, 65536   # PVS_DIFFUSE_DOT_BLOCK, PVS_DIFFUSE_MAX_COLUMNS of include/pvsim.h
+KRR_MAX_K1, KRR_MAX_KQ = 64, 1024                     # PVS_KRR_MAX_K1, PVS_KRR_MAX_KQ of include/pvsim.h
 VLAD_PATH_AUTO, VLAD_PATH_GATHER, VLAD_PATH_STREAM, VLAD_PATH_FUSED = 0, 1, 2, 3
 TIMER_NAMES = ("assign", "aggregate", "cosine_gemm", "topk", "fisher_posterior", "fisher_moments", "misc", "rescore")
 
@@ -153,6 +154,12 @@ SIGNATURES = {
     "pvs_graph_remap_dev": [_vp, _vp, _i64, _int, _vp, _vp, _vp],
     "pvs_graph_gather_rows_dev": [_vp, _vp, _i64, _i64, _vp, _i64, _vp],
     "pvs_graph_affinity_sim_dev": [_vp, _vp, _i64, _int, _int, _vp],
+    "pvs_krr_sets_dev": [_vp, _vp, _i64, _int, _int, _vp, _vp],
+    "pvs_krr_members_dev": [_vp, _vp, _vp, _vp, _i64, _int, _vp, _vp],
+    "pvs_krr_weights_dev": [_vp, _vp, _vp, _i64, _int, _int, _vp, _vp],
+    "pvs_krr_expand_dev": [_vp, _vp, _vp, _vp, _i64, _int, _int, _vp, _vp, _vp],
+    "pvs_krr_query_dev": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp],
+    "pvs_krr_score_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _int, _vp, _vp, _vp, _vp, _i64, _int, _int, C.c_double, _vp],
     "pvs_asmk_aggregate_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _vp, _int, _vp, _vp, _vp],
     "pvs_asmk_aggregate_ma_dev": [_vp, _vp, _vp, _int, _vp, _vp, _i64, _i64, _vp, _int, _vp, _int, _vp, _vp, _vp],
     "pvs_asmk_score_dev": [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp, _i64],

@@ -569,6 +569,38 @@ class Context:
         """pvs_graph_affinity_sim_dev: a float64 (N, kg) from the stored float32 similarities, the product of graph_affinity_dev"""
         check(_ffi.lib().pvs_graph_affinity_sim_dev(self.handle, ptr(d_sim), int(N), int(kg), int(gamma), ptr(d_a)))
 
+    # k-reciprocal re-ranking (DESIGN.md section 21)
+    def krr_sets_dev(self, d_nbr, N, kg, k1, d_mask1, d_maskh):
+        """pvs_krr_sets_dev: nbr int32 (N, kg) -> the reciprocal slots of every row at k1 and at (k1 + 1) // 2, two uint64 (N,)"""
+        check(_ffi.lib().pvs_krr_sets_dev(self.handle, ptr(d_nbr), int(N), int(kg), int(k1), ptr(d_mask1), ptr(d_maskh)))
+
+    def krr_members_dev(self, d_nbr, d_mask1, d_maskh, N, kg, d_members, d_dropped):
+        """pvs_krr_members_dev: the members of the expanded set that sit in the row's own list, uint8 (N, kg), and the count of those
+        that do not, int32 (N,)"""
+        check(_ffi.lib().pvs_krr_members_dev(self.handle, ptr(d_nbr), ptr(d_mask1), ptr(d_maskh), int(N), int(kg), ptr(d_members),
+                                             ptr(d_dropped)))
+
+    def krr_weights_dev(self, d_sim, d_members, N, kg, gamma, d_v, d_v0):
+        """pvs_krr_weights_dev: v float64 (N, kg) and v0 (N,): the members' affinities and the self weight 1 over their sum"""
+        check(_ffi.lib().pvs_krr_weights_dev(self.handle, ptr(d_sim), ptr(d_members), int(N), int(kg), int(gamma), ptr(d_v), ptr(d_v0)))
+
+    def krr_expand_dev(self, d_nbr, d_v, d_v0, N, kg, k2, d_w, d_w0, d_ws):
+        """pvs_krr_expand_dev: the mean of V over a row and its first k2 - 1 neighbours on the row's support: w (N, kg), w0, ws (N,)"""
+        check(_ffi.lib().pvs_krr_expand_dev(self.handle, ptr(d_nbr), ptr(d_v), ptr(d_v0), int(N), int(kg), int(k2), ptr(d_w), ptr(d_w0),
+                                            ptr(d_ws)))
+
+    def krr_query_dev(self, d_nbr, d_sim, d_maskh, d_v, d_v0, N, kg, k1, k2, gamma, d_qidx, d_qval, nq, kq, d_wq, d_sq, d_kept, d_dropped):
+        """pvs_krr_query_dev: float32 query lists (nq, kq) -> the queries' expanded vectors wq float64 (nq, kq), their sums sq (nq,),
+        the members kept and the members dropped, int32 (nq,) both"""
+        check(_ffi.lib().pvs_krr_query_dev(self.handle, ptr(d_nbr), ptr(d_sim), ptr(d_maskh), ptr(d_v), ptr(d_v0), int(N), int(kg), int(k1),
+                                           int(k2), int(gamma), ptr(d_qidx), ptr(d_qval), int(nq), int(kq), ptr(d_wq), ptr(d_sq),
+                                           ptr(d_kept), ptr(d_dropped)))
+
+    def krr_score_dev(self, d_nbr, d_w, d_w0, d_ws, N, kg, d_qidx, d_qval, d_wq, d_sq, nq, kq, kr, lam, d_scores):
+        """pvs_krr_score_dev: (1 - lam) Jaccard + lam cosine of the first kr candidates of every query -> float64 (nq, kr)"""
+        check(_ffi.lib().pvs_krr_score_dev(self.handle, ptr(d_nbr), ptr(d_w), ptr(d_w0), ptr(d_ws), int(N), int(kg), ptr(d_qidx), ptr(d_qval),
+                                           ptr(d_wq), ptr(d_sq), int(nq), int(kq), int(kr), float(lam), ptr(d_scores)))
+
     # local-descriptor retrieval, ASMK* (DESIGN.md section 17)
     def asmk_aggregate_dev(self, cb, d_desc, kind, d_offsets, h_offsets, n_images, total_desc, d_labels, d_proj, bits, d_ent_word,
                            d_ent_sig, d_ent_count):

@@ -76,7 +76,7 @@ class _Plan:
         return self._index_of(path)
 
 
-def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None) -> _Plan:
+def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None, reciprocal=None) -> _Plan:
     """What `dataset` is (a dict, a DeviceIndex, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
     refusal is raised here, before anything is encoded), and how it ranks.  A DeviceIndex is never asked for its host rows."""
     from .compact import CompactIndex, IVFCompactIndex
@@ -92,6 +92,16 @@ def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=
             raise ValueError("diffuse= needs the DeviceIndex the graph was built on: this graph belongs to another index")
         if expand is not None or rerank or nprobe is not None:
             raise ValueError("diffuse= excludes expand=, rerank= and nprobe=")
+    if reciprocal is not None:                    # as diffuse=: the lists' own index only, and no other re-ranking option
+        from .reciprocal import KReciprocal
+        if not isinstance(reciprocal, KReciprocal):
+            raise TypeError("reciprocal must be a pvsim.KReciprocal")
+        if not dense:
+            raise TypeError("reciprocal= needs the pvsim.index.DeviceIndex the lists were built on, not a dict or a compact index")
+        if reciprocal.index is not dataset:
+            raise ValueError("reciprocal= needs the DeviceIndex the lists were built on: this KReciprocal belongs to another index")
+        if expand is not None or rerank or nprobe is not None or diffuse is not None:
+            raise ValueError("reciprocal= excludes expand=, rerank=, nprobe= and diffuse=")
     if expand is not None and compact:
         raise ValueError("query expansion needs the full-precision rows: use a dict or a DeviceIndex, not a CompactIndex")
     if rerank and not compact:
@@ -115,6 +125,11 @@ def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=
             return dataset.rank(q, kk)
         if diffuse is not None:
             rank = lambda q, k: _clamped(diffuse.rank, n, q, k, np.float64)
+        elif reciprocal is not None:              # rank's own kq where it holds k results, as many candidates as results beyond that
+            def reranked(q, kk):
+                _check_features(q, dataset.shape[1])
+                return reciprocal.rank(q, kk, kq=min(n, max(kk, 80)))       # k beyond the most rank serves is refused there
+            rank = lambda q, k: _clamped(reranked, n, q, k, np.float64)
         elif expand is not None:
             rank = lambda q, k, members=None: _clamped(dataset.rank_expanded, n, q, k, qe=expand, members=members)
         else:
@@ -138,14 +153,15 @@ def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=
 
 
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
-                           k: int = 5, rerank: int = 0, expand=None, nprobe=None, diffuse=None) -> list[tuple[str, float]]:
+                           k: int = 5, rerank: int = 0, expand=None, nprobe=None, diffuse=None, reciprocal=None) -> list[tuple[str, float]]:
     """[(image_path, similarity)] of the k most similar database entries, best first.  `rerank=R` (CompactIndex only): the
     ADC top-R re-ranked by the exact cosine of the kept projected rows.  `expand`: a pvsim.expand.QueryExpansion; the list is
     then the ranking of the expanded query (dict or DeviceIndex; a dict is uploaded for the call).  `nprobe` (IVFCompactIndex
     only, and required there): the inverted lists scanned; the list is shorter than k when they hold fewer rows.  `diffuse`: a
     pvsim.Diffusion graph built on `dataset` (a DeviceIndex); the list is then the diffusion ranking and its float64 scores, and
-    `rerank`, `expand` and `nprobe` are excluded."""
-    plan = _plan(dataset, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None))
+    `rerank`, `expand` and `nprobe` are excluded.  `reciprocal`: a pvsim.KReciprocal built on `dataset` (a DeviceIndex); the list is
+    then the k-reciprocal re-ranking of the first max(k, 80) results and its float64 scores, and every other option is excluded."""
+    plan = _plan(dataset, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal)
     idx, val = plan.rank(_first_row(encoder, uploaded_image), k)
     return [(plan.paths[i], s) for i, s in zip(idx[0], val[0]) if i >= 0]     # unfilled slots of an IVF list are dropped
 
@@ -197,20 +213,22 @@ def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: i
     return (front + back)[:k]
 
 
-def _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse):
+def _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal=None):
     """-> (ranked indices (nq, k'), -1 in the unfilled slots at the end of an IVF list; the label of every database entry)"""
-    plan = _plan(encoding_map, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None))
+    plan = _plan(encoding_map, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal)
     idx, _ = plan.rank(_first_rows(encoder, images), k)
     return idx, [path_labels_dict[p] for p in plan.paths]
 
 
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None, diffuse=None) -> float:
+              path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None, diffuse=None,
+              reciprocal=None) -> float:
     """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
-    there) and `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) as in retrieve_top_k_similar."""
+    there), `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) and `reciprocal` (a pvsim.KReciprocal of it) as in
+    retrieve_top_k_similar."""
     labels = list(image_labels)
-    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse)
+    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal)
     aps = []
     for row, true_label in zip(idx, labels):
         relevant_count, precision_sum = 0, 0.0
@@ -223,12 +241,14 @@ def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encodin
 
 
 def top_k_accuracy(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
-                   path_labels_dict: dict[str, int], encoder, k: int, expand=None, rerank: int = 0, nprobe=None, diffuse=None) -> float:
+                   path_labels_dict: dict[str, int], encoder, k: int, expand=None, rerank: int = 0, nprobe=None, diffuse=None,
+                   reciprocal=None) -> float:
     """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
-    there) and `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) as in retrieve_top_k_similar."""
+    there), `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) and `reciprocal` (a pvsim.KReciprocal of it) as in
+    retrieve_top_k_similar."""
     images = list(images)
     labels = list(image_labels)
-    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse)
+    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal)
     correct = sum(1 for row, true_label in zip(idx, labels) if any(i >= 0 and db_labels[i] == true_label for i in row))
     return float(correct / len(images))
