@@ -72,7 +72,9 @@ typedef enum {
   PVS_OPT_UPDATE_WINDOW_ROWS = 6, /* source rows per window of the in-place pvs_compact_rows_dev: 0 (default) what the staging byte budget  */
                                 /* holds; v in 1..2^20: at most v rows, so that a test reaches a window seam with a few hundred rows.      */
                                 /* Same bytes: the windows move the rows, they compute nothing.                                          */
-  PVS_OPT_COUNT_ = 7
+  PVS_OPT_SQ8_PATH = 7,         /* pvs_sq8_topk_dev: 0 (default) the row scan for up to 4 queries, the int8 GEMM beyond; 1: always the row   */
+                                /* scan; 2: always the GEMM.  Same bits: the dot product of two code rows is an integer.                  */
+  PVS_OPT_COUNT_ = 8
 } pvs_option;
 
 typedef struct pvs_ctx pvs_ctx;
@@ -934,6 +936,37 @@ int pvs_asmk_expand_dev(pvs_ctx* ctx, int64_t nq, const int64_t* h_q_off, const 
                         const int32_t* d_members, const int32_t* d_votes, int query_vote, int h_max, int min_support,
                         const int32_t* d_wt, int tile_words, int cap, int32_t* d_out_word, uint32_t* d_out_sig,
                         int32_t* d_out_count, int64_t* d_out_sum);
+
+/* ---------------------------------------------------------------- int8 resident index: one signed byte per dimension
+ * A scalar-quantised copy of float32 rows, a quarter of their size, ranked by the cosine of the CODE rows.  Every sum is an integer,
+ * so no tiling, split of a row or order of summation changes a bit, and a restatement with int64 sums gives the same bytes.
+ *   code row    x float32 [L], 1 <= L <= 131072, every element finite (a PRECONDITION of the entry point: it is not checked).
+ *               amax = max_t |x[t]|.  amax == 0 gives all-zero codes.  Otherwise c[t] = (int8) rint((x[t] / amax) * 127.0f): an IEEE
+ *               float32 division, then a float32 multiply, each rounded on its own; rint rounds half to even.  |x / amax| <= 1, so
+ *               |c| <= 127 and -128 never occurs.  No reciprocal is formed: a subnormal amax is no special case.
+ *   storage     int8 [N][ld], ld = PVS_SQ8_LD(L) = 64 ceil(L / 64); bytes L .. ld of every row are zero, so they add nothing to any
+ *               sum; every row starts on 64 bytes and a k-step of the matrix instruction never straddles a row end.
+ *   row factor  ss = sum_t c[t]^2 as an integer; inv = ss == 0 ? 0.0f : (float)(1.0 / sqrt((double)ss)): float64 square root and
+ *               division, then one rounding to float32.  One float32 per row.  The quantisation scale amax / 127 cancels in a
+ *               cosine of the codes and is not stored.
+ *   score       acc = sum_t cq[t] * cd[t] in int32, exact because 127^2 * 131072 = 2 114 060 288 < 2^31 (this bounds L);
+ *               score = ((float)acc * inv_q) * inv_d: the int32 -> float32 conversion rounds to nearest even, then two multiplies,
+ *               each rounded on its own.  The queries are quantised by the same rule.
+ *   ranking     (score descending, global index ascending): the rule of pvs_topk_dev.  (float)acc merges neighbouring integers
+ *               above 2^24, so ties happen and the index decides them.
+ * n == 0 and nq == 0 are no-ops.  Both entry points enqueue on the context's stream and do not wait for it. */
+#define PVS_SQ8_LD(L) (64 * (((L) + 63) / 64))
+/* d_x float32 [n][L] -> d_codes int8 [n][ld] (16-byte aligned; the padding bytes are written too, as zeros) and d_inv float32 [n].
+ * Nothing past row n of either output is touched.  Timed on slot 6. */
+int pvs_sq8_encode_dev(pvs_ctx* ctx, const float* d_x, int64_t n, int L, int8_t* d_codes, float* d_inv);
+/* Scores of nq code rows against N code rows (both [.][ld], 16-byte aligned, with their row factors) and their ranking, with the
+ * semantics of pvs_pq_scan_topk_dev and pvs_cosine_topk_dev: row 0 has global index col_offset; merge != 0 merges into the running
+ * lists already in d_idx / d_val; 1 <= k <= N (k > 1024 needs merge == 0 and N <= 2^28, as there).  The nq x N score matrix never
+ * exists: scores pass through a bounded workspace panel into the top-k kernels, panel by panel.  d_idx int64 [nq][k], d_val float32
+ * [nq][k].  Two device paths sit behind the entry, chosen by PVS_OPT_SQ8_PATH: a tiled int8 GEMM on v_mfma_i32_32x32x32_i8 and a
+ * one-pass row scan on v_dot4 for a handful of queries; they give the same bits.  Timed on slots 2 (scores) and 3 (ranking). */
+int pvs_sq8_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q, int64_t nq, const int8_t* d_codes,
+                     const float* d_inv_db, int64_t N, int L, int k, int64_t col_offset, int merge, int64_t* d_idx, float* d_val);
 
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,

@@ -6,7 +6,8 @@
     from pvsim import verify                   # LocalFeatureIndex, SpatialVerifier, match (spatial re-ranking)
     from pvsim import CompactIndex, ProductQuantizer   # product-quantised index, ADC search (m + 4 bytes per image)
     from pvsim import IVFCompactIndex                  # the same cut into inverted lists: a query scans nprobe of nlist lists
-    from pvsim import QueryExpansion                   # query expansion / database-side augmentation on a DeviceIndex
+    from pvsim import Int8Index                        # one signed byte per dimension: a quarter of a DeviceIndex, near-exact lists
+    from pvsim import QueryExpansion             # query expansion / database-side augmentation on a DeviceIndex
     from pvsim import Diffusion                        # diffusion re-ranking on the kNN graph of a DeviceIndex
     from pvsim import KReciprocal                      # k-reciprocal re-ranking on the kNN lists of a DeviceIndex
     from pvsim import ASMKIndex                        # local-descriptor retrieval: ASMK* with binary signatures, an inverted file
@@ -20,6 +21,7 @@ from .engine import Context, default_context, pack_descriptors
 from . import models
 from ._errors import CapacityError
 from .compact import CompactIndex, IVFCompactIndex, ProductQuantizer
+from .quantized import Int8Index
 from .expand import QueryExpansion
 from .diffusion import Diffusion
 from .reciprocal import KReciprocal
@@ -27,4 +29,4 @@ from .asmk import ASMKExpansion, ASMKIndex
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion"]
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "Int8Index", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion"]

@@ -27,7 +27,10 @@ OPT_TRAIN_BATCH_CHUNKS = 5        # 0: training batches from the byte budgets; 1
 PIX_U8_RGB, PIX_U8_GRAY, PIX_F32_RGB, PIX_F32_GRAY = 0, 1, 2, 3          # pvs_pixel_kind
 DSIFT_U8, DSIFT_F32, DSIFT_F32_RAW, DSIFT_F32_QUANT = 0, 1, 2, 3                         # pvs_dsift_out
 OPT_UPDATE_WINDOW_ROWS = 6        # 0: windows of the in-place row compaction from the staging byte budget; 1..2^20: at most that many rows
-SCAN_TILE = 2048                  # PVS_SCAN_TILE of include/pvsim.h
+OPT_SQ8_PATH = 7                  # pvs_sq8_topk_dev: 0 chooses by the number of queries, 1 the row scan, 2 the int8 GEMM; same bits
+SQ8_PATH_AUTO, SQ8_PATH_ROWS, SQ8_PATH_MATRIX = 0, 1, 2
+SQ8_MAX_L = 131072                # 127^2 * L < 2^31
+SCAN_TILE = 2048                # PVS_SCAN_TILE of include/pvsim.h
 COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
 DIFFUSE_DOT_BLOCK, DIFFUSE_MAX_COLUMNS = 256, 65536   # PVS_DIFFUSE_DOT_BLOCK, PVS_DIFFUSE_MAX_COLUMNS of include/pvsim.h
 KRR_MAX_K1, KRR_MAX_KQ = 64, 1024                     # PVS_KRR_MAX_K1, PVS_KRR_MAX_KQ of include/pvsim.h
@@ -169,6 +172,8 @@ SIGNATURES = {
     "pvs_asmk_remove_dev": [_vp, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "pvs_asmk_expand_dev": [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _i64, _int, _vp, _vp, _int, _int, _int, _vp, _int, _int,
                             _vp, _vp, _vp, _vp],
+    "pvs_sq8_encode_dev": [_vp, _vp, _i64, _int, _vp, _vp],
+    "pvs_sq8_topk_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _i64, _int, _vp, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

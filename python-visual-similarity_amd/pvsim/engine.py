@@ -482,6 +482,15 @@ class Context:
         check(_ffi.lib().pvs_rescore_rows_dev(self.handle, ptr(d_q), nq, ptr(d_x), N, d, ptr(d_invq), ptr(d_invdb), ptr(d_cand), R,
                                               ptr(d_val)))
 
+    # int8 resident index
+    def sq8_encode_dev(self, d_x, n, L, d_codes, d_inv):
+        """pvs_sq8_encode_dev: float32 rows (n, L) -> int8 codes (n, 64 ceil(L / 64)), zero padded, and 1 / sqrt(sum c^2) per row"""
+        check(_ffi.lib().pvs_sq8_encode_dev(self.handle, ptr(d_x), int(n), int(L), ptr(d_codes), ptr(d_inv)))
+
+    def sq8_topk_dev(self, d_qcodes, d_invq, nq, d_codes, d_invdb, N, L, k, col_offset, merge, d_idx, d_val):
+        check(_ffi.lib().pvs_sq8_topk_dev(self.handle, ptr(d_qcodes), ptr(d_invq), int(nq), ptr(d_codes), ptr(d_invdb), int(N), int(L),
+                                          int(k), int(col_offset), int(merge), ptr(d_idx), ptr(d_val)))
+
     # inverted lists of the compact index (DESIGN.md section 14)
     def ivf_assign_dev(self, d_x, n, d, d_centroids, nlist, d_list, d_residual):
         check(_ffi.lib().pvs_ivf_assign_dev(self.handle, ptr(d_x), n, d, ptr(d_centroids), nlist, ptr(d_list), ptr(d_residual)))

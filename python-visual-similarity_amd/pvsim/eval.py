@@ -77,12 +77,25 @@ class _Plan:
 
 
 def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None, reciprocal=None) -> _Plan:
-    """What `dataset` is (a dict, a DeviceIndex, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
+    """What `dataset` is (a dict, a DeviceIndex, an Int8Index, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
     refusal is raised here, before anything is encoded), and how it ranks.  A DeviceIndex is never asked for its host rows."""
     from .compact import CompactIndex, IVFCompactIndex
     from .index import DeviceIndex
+    from .quantized import Int8Index
     dense, compact = isinstance(dataset, DeviceIndex), isinstance(dataset, CompactIndex)
-    if diffuse is not None:                       # the graph's own index only, and none of the other re-ranking options
+    int8 = isinstance(dataset, Int8Index)
+    if int8:                                      # one ranking, the cosine of the codes: every option names what it needs instead
+        if expand is not None:
+            raise ValueError("expand= needs the full-precision rows: use a dict or a DeviceIndex, not an Int8Index")
+        if rerank:
+            raise ValueError("rerank= needs the kept projected rows of a CompactIndex: an Int8Index has no second stage")
+        if nprobe is not None:
+            raise ValueError("nprobe= needs the inverted lists of an IVFCompactIndex: an Int8Index scans every row")
+        if diffuse is not None:
+            raise ValueError("diffuse= needs the DeviceIndex the graph was built on, not an Int8Index")
+        if reciprocal is not None:
+            raise ValueError("reciprocal= needs the DeviceIndex the lists were built on, not an Int8Index")
+    if diffuse is not None:                      # the graph's own index only, and none of the other re-ranking options
         from .diffusion import Diffusion
         if not isinstance(diffuse, Diffusion):
             raise TypeError("diffuse must be a pvsim.Diffusion")
@@ -119,6 +132,12 @@ def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=
                                  "full-precision rows -- use a dict or a DeviceIndex for that)")
             args = () if nprobe is None else (nprobe,)
             return _clamped(lambda q, kk: dataset.rank(q, kk, *args, rerank=rerank), n, q, k)
+    elif int8:
+        def rank(q, k):
+            if k is None:
+                raise ValueError("an Int8Index ranks a finite list: pass k (k=None asks for the complete ranking, which needs the "
+                                 "full-precision rows -- use a dict or a DeviceIndex for that)")
+            return _clamped(dataset.rank, n, q, k)
     elif dense:
         def plain(q, kk):
             _check_features(q, dataset.shape[1])
