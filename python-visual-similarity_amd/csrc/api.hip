@@ -5,7 +5,7 @@
 #include <limits>
 #include <memory>
 
-#include "common.hpp"
+#include "panel_plan.hpp"
 
 namespace pvs {
 
@@ -831,10 +831,9 @@ static int cosine_topk_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const voi
   PVS_HIP(hipSetDevice(ctx->device));
   if (N == 0) return launch_topk(ctx, nullptr, nq, 0, 0, k, col_offset, merge, d_idx, d_val);
   PVS_NEED(d_DB, "DB");
-  // score panel: at most 8192 x 32768 fp32 = 1 GiB, written by the GEMM and consumed by the select.
-  // Ranking deeper than 1024 pages through complete rows, so the panel then spans all N columns.
-  const bool deep = k > 1024;
-  if (deep && (merge || N > (int64_t)1 << 28)) PVS_FAIL(PVS_ERR_UNSUPPORTED, "ranking depth %d needs a single panel", k);
+  // score panel: written by the GEMM and consumed by the select (panel_plan.hpp: the dense rule, complete rows for k > 1024)
+  PanelPlan plan;
+  PVS_TRY(panel_ranking_plan(panel_dense, nq, N, k, merge, &plan));
   // one or two queries (eval.retrieve_top_k_similar against a resident index): a 1 x N score row in ONE pass over the database at
   // HBM speed instead of 128-row MFMA tiles with 127 idle rows; the same scores bit for bit (filter.hip)
   if (!f16 && N <= ((int64_t)1 << 28) && cosine_dense_rows_eligible(static_cast<const float*>(d_Q), static_cast<const float*>(d_DB), nq, L)) {
@@ -843,30 +842,16 @@ static int cosine_topk_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const voi
     PVS_TRY(launch_cosine_dense_rows(ctx, static_cast<const float*>(d_Q), nq, static_cast<const float*>(d_DB), N, L, d_inv_q, d_inv_db, row, N));
     return launch_topk(ctx, row, nq, N, N, k, col_offset, merge, d_idx, d_val);
   }
-  const int64_t NC = deep ? N : std::min<int64_t>(N, 32768);
-  const int64_t QT = deep ? std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 28) / N))
-                          : std::min<int64_t>(nq, 8192);
   const size_t esz = f16 ? 2 : 4;
   const char* q = static_cast<const char*>(d_Q);
   const char* db = static_cast<const char*>(d_DB);
-  float* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
-    for (int64_t c0 = 0; c0 < N; c0 += NC) {
-      const int64_t cn = std::min(NC, N - c0);
-      const float* iq = d_inv_q ? d_inv_q + q0 : nullptr;
-      const float* idb = d_inv_db ? d_inv_db + c0 : nullptr;
-      if (f16)
-        PVS_TRY(launch_cosine_f16(ctx, q + (size_t)q0 * L * esz, qn, db + (size_t)c0 * L * esz, cn, L, iq, idb, panel, cn));
-      else
-        PVS_TRY(launch_cosine_f32(ctx, reinterpret_cast<const float*>(q) + q0 * L, qn,
-                                  reinterpret_cast<const float*>(db) + c0 * L, cn, L, iq, idb, panel, cn));
-      PVS_TRY(launch_topk(ctx, panel, qn, cn, cn, k, col_offset + c0, (merge || c0 > 0) ? 1 : 0, d_idx + q0 * k,
-                          d_val + q0 * k));
-    }
-  }
-  return PVS_OK;
+  return panel_topk(ctx, plan, k, col_offset, merge, d_idx, d_val, [&](int64_t q0, int64_t qn, int64_t c0, int64_t cn, float* panel) -> int {
+    const float* iq = d_inv_q ? d_inv_q + q0 : nullptr;
+    const float* idb = d_inv_db ? d_inv_db + c0 : nullptr;
+    if (f16) return launch_cosine_f16(ctx, q + (size_t)q0 * L * esz, qn, db + (size_t)c0 * L * esz, cn, L, iq, idb, panel, cn);
+    return launch_cosine_f32(ctx, reinterpret_cast<const float*>(q) + q0 * L, qn, reinterpret_cast<const float*>(db) + c0 * L, cn, L, iq,
+                             idb, panel, cn);
+  });
 }
 
 PVS_EXPORT int pvs_cosine_topk_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_DB, int64_t N, int64_t L,
@@ -1004,16 +989,12 @@ PVS_EXPORT int pvs_cosine_topk_f64_dev(pvs_ctx* ctx, const double* d_Q, int64_t 
   if (N <= 0) PVS_FAIL(PVS_ERR_INVALID, "empty database");
   if (k < 1 || k > N) PVS_FAIL(PVS_ERR_INVALID, "k = %d out of range 1..%lld", k, (long long)N);
   PVS_HIP(hipSetDevice(ctx->device));
-  const int64_t QT = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / N));
-  double* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * N * sizeof(double), &panel));
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
+  return panel_for_each<double>(ctx, panel_full_rows(nq, N, panel_elems<double>()),
+                                [&](int64_t q0, int64_t qn, int64_t, int64_t, double* panel) -> int {
     // the whole problem in one panel and Q == DB: the symmetric kernel (launch_cosine_f64_dev detects it)
     PVS_TRY(launch_cosine_f64_dev(ctx, d_Q + q0 * L, qn, d_DB, N, L, d_inv_q ? d_inv_q + q0 : nullptr, d_inv_db, panel, N));
-    PVS_TRY(launch_rank_f64(ctx, panel, qn, N, N, k, d_idx + q0 * k, d_val + q0 * k));
-  }
-  return PVS_OK;
+    return launch_rank_f64(ctx, panel, qn, N, N, k, d_idx + q0 * k, d_val + q0 * k);
+  });
 }
 
 // host pointers: the database is uploaded ONCE per call, the queries in blocks; norms, panels and lists stay on the device
@@ -1030,9 +1011,7 @@ PVS_EXPORT int pvs_cosine_topk_f64(pvs_ctx* ctx, const double* Q, int64_t nq, co
   if (k < 1 || k > N) PVS_FAIL(PVS_ERR_INVALID, "k = %d out of range 1..%lld", k, (long long)N);
   PVS_HIP(hipSetDevice(ctx->device));
   const bool same = (Q == DB && nq == N);
-  // query block: as many rows as one score panel of pvs_cosine_topk_f64_dev holds, at most 2 GiB of rows
-  const int64_t QB = same ? nq : std::max<int64_t>(1, std::min<int64_t>(nq, std::min<int64_t>(((int64_t)128 << 20) / N,
-                                                                                             ((int64_t)256 << 20) / L)));
+  const int64_t QB = host_f64_query_block(nq, N, L, same);
   char* d_in = nullptr;
   char* d_s = nullptr;
   WsLayout<> in, res;

@@ -22,7 +22,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "panel_plan.hpp"
 
 namespace pvs {
 
@@ -270,14 +270,12 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
   if (L % 8 != 0 || L < 8 || reinterpret_cast<uintptr_t>(Q) % 16 || reinterpret_cast<uintptr_t>(DB) % 16)
     PVS_FAIL(PVS_ERR_UNSUPPORTED, "filtered top-k needs 16-B aligned rows with L %% 8 == 0");
   if (k < 1 || k > 128) PVS_FAIL(PVS_ERR_UNSUPPORTED, "filtered top-k: k <= 128");
-  const int64_t NC = std::min<int64_t>(N, 32768);       // database rows per score panel
-  const bool multi = N > NC;
   const bool same = (Q == DB) && (nq == N) && (invq == invdb);
-  const bool square = same && !multi && (int64_t)nq * N <= ((int64_t)1 << 28);   // one symmetric launch covers everything
+  const PanelPlan plan = panel_filter(nq, N, same);   // all queries at once where one symmetric launch covers everything
+  const bool multi = N > plan.NC;
   // candidate slots: a multiple of k; over several database panels the running threshold admits more columns early on
   const int cap_lists = ((multi ? 16 : 4) * k + (multi ? 128 : 64) + k - 1) / k;
   const int cap = cap_lists * k;
-  const int64_t QT = square ? nq : std::min<int64_t>(nq, std::max<int64_t>(256, ((int64_t)1 << 28) / NC));
   const double eps = filter_eps(L);
   const float margin = (float)(2.0 * eps);
 
@@ -291,7 +289,7 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
   }
   _Float16* q16 = q16_p(w5);
   _Float16* db16 = same ? q16 : db16_p(w5);
-  const FilterListsLayout lay = filter_lists_layout(nq, N, QT, k, cap);
+  const FilterListsLayout lay = filter_lists_layout(nq, N, plan.QT, k, cap);
   char* w6 = nullptr;
   PVS_TRY(ws_reserve(ctx, WS_LISTS, lay.bytes, &w6));
   float* invq16 = lay.invq(w6);
@@ -302,8 +300,6 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
   int64_t* cidx = lay.cidx(w6);
   float* cval = lay.cval(w6);
   int* cnt = lay.cnt(w6);
-  float* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
   PVS_HIP(hipMemsetAsync(stats, 0, 32, ctx->stream));
 
   // ---- 1. scaled fp16 rows
@@ -320,13 +316,11 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
   if (hs[0]) PVS_FAIL(PVS_ERR_UNSUPPORTED, "filtered top-k: %llu rows hold non-finite values or an extreme dynamic range", hs[0]);
 
   std::vector<int> h_cnt;
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
-    // step 7 of the previous block may have called cosine_topk_exact, which reserves WS_PANEL_OUT for a panel of its own size
-    PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
+  for (int64_t q0 = 0; q0 < nq; q0 += plan.QT) {
+    const int64_t qn = plan.qn(q0);
     PVS_HIP(hipMemsetAsync(cidx, 0xff, (size_t)qn * cap * 8, ctx->stream));
-    for (int64_t c0 = 0; c0 < N; c0 += NC) {
-      const int64_t cn = std::min(NC, N - c0);
+    // the panel is reserved again for every query block: step 7 of the previous one may have called cosine_topk_exact, which takes the slot
+    PVS_TRY(panel_query_block<float>(ctx, plan, q0, [&](int64_t, int64_t, int64_t c0, int64_t cn, float* panel) -> int {
       // ---- 2. bounded-error approximate scores, 3. approximate k-th best (running over the database panels)
       PVS_TRY(launch_cosine_f16_bounded(ctx, q16 + q0 * L, qn, db16 + c0 * L, cn, L, invq16 + q0, invd16 + c0, panel, cn));
       PVS_TRY(launch_topk(ctx, panel, qn, cn, cn, k, c0, c0 > 0 ? 1 : 0, aidx, aval));
@@ -334,7 +328,8 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
       ScopedTimer tm(ctx, T_TOPK);
       hipLaunchKernelGGL(filter_collect_kernel, dim3((unsigned)((qn + 3) / 4)), dim3(256), 0, ctx->stream, panel, qn, cn, cn, aidx, aval, k,
                          margin, cap, c0, c0 == 0 ? 1 : 0, cidx, cnt, stats);
-    }
+      return PVS_OK;
+    }));
     // scores too crowded for the filter (more than a tenth of the queries have more candidates than slots, e.g. nearly
     // orthogonal rows whose best scores sit inside the error margin of the bulk): the all-pairs path is the faster exact one
     PVS_HIP(hipMemcpyAsync(hs, stats, 24, hipMemcpyDeviceToHost, ctx->stream));
@@ -359,7 +354,7 @@ int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const 
       for (int64_t i = 0; i < qn; ++i)
         if (h_cnt[(size_t)i] > cap) rows.push_back(i);
       const int64_t nr = (int64_t)rows.size();
-      const int64_t rb = std::max<int64_t>(1, std::min<int64_t>(nr, ((int64_t)1 << 28) / N));   // rows per exact batch (score rows <= 1 GiB)
+      const int64_t rb = panel_full_rows(nr, N, panel_elems<float>()).QT;   // rows per exact batch (score rows <= 1 GiB)
       char* w3 = nullptr;
       WsLayout<> ovf;
       const auto rows_p = ovf.add<int64_t>((size_t)nr);

@@ -35,7 +35,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "panel_plan.hpp"
 
 namespace pvs {
 
@@ -289,11 +289,10 @@ static int nb_sqnorms(pvs_ctx* ctx, const T* x, int64_t rows, int64_t L, double*
 // could order two identical rows by rounding; the re-score makes the value a function of the two rows.
 static int knn_f64_rows(pvs_ctx* ctx, const double* Q, int64_t nq, const double* X, int64_t N, int64_t L, const double* xn,
                         const double* yn, const double* d_ymax2, int k, int64_t* d_idx, double* d_dist) {
-  const int64_t QT = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / N));
+  const PanelPlan plan = panel_full_rows(nq, N, panel_elems<double>());
+  const int64_t QT = plan.QT;
   const int cap = std::min(NB_CAP_MAX, std::max(256, 8 * k));
   const bool filt = k <= NB_K_MAX;
-  double* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * N * sizeof(double), &panel));
   char* w6 = nullptr;
   WsLayout<> lay;
   const auto aidx_p = lay.add<int64_t>((size_t)QT * k);
@@ -310,8 +309,7 @@ static int knn_f64_rows(pvs_ctx* ctx, const double* Q, int64_t nq, const double*
   double* key = key_p(w6);
   unsigned long long* ovf = ovf_p(w6);
   PVS_HIP(hipMemsetAsync(ovf, 0, 8, ctx->stream));
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
+  return panel_for_each<double>(ctx, plan, [&](int64_t q0, int64_t qn, int64_t, int64_t, double* panel) -> int {
     PVS_TRY(launch_cosine_f64_dev(ctx, Q + q0 * L, qn, X, N, L, nullptr, nullptr, panel, N));
     {
       ScopedTimer tm(ctx, T_MISC);
@@ -323,7 +321,7 @@ static int knn_f64_rows(pvs_ctx* ctx, const double* Q, int64_t nq, const double*
       ScopedTimer tm(ctx, T_MISC);
       hipLaunchKernelGGL(nb_negate_kernel, dim3(nb_grid(qn * k)), dim3(256), 0, ctx->stream, d_dist + q0 * k, qn * k, d_dist + q0 * k);
       PVS_HIP(hipGetLastError());
-      continue;
+      return PVS_OK;
     }
     PVS_TRY(launch_rank_f64(ctx, panel, qn, N, N, k, aidx, aval));
     ScopedTimer tm(ctx, T_RESCORE);
@@ -335,8 +333,8 @@ static int knn_f64_rows(pvs_ctx* ctx, const double* Q, int64_t nq, const double*
     hipLaunchKernelGGL(nb_rank_kernel, dim3((unsigned)qn), dim3(256), 0, ctx->stream, cand, key, count, cap, k, aidx, aval,
                        d_idx + q0 * k, d_dist + q0 * k);
     PVS_HIP(hipGetLastError());
-  }
-  return PVS_OK;
+    return PVS_OK;
+  });
 }
 
 // float32 rows -> float64 copies in WS_NB_F64_ROWS (the full f64 pass); Q == X shares one copy
@@ -404,13 +402,12 @@ PVS_EXPORT int pvs_l2_knn_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const v
   bool filtered = k <= NB_K_MAX && std::isfinite(h_max) && h_max <= 0x1p100;
   if (filtered) {
     const int cap = std::min(NB_CAP_MAX, std::max(256, 8 * k));
-    const int64_t NC = std::min<int64_t>(N, 32768);
-    const int64_t QT = std::min<int64_t>(nq, 8192);
+    const PanelPlan plan = panel_dense(nq, N);
     // which f32 GEMM kernel launch_cosine_f32 picks for these panels (panel offsets keep the 16-B alignment of the bases)
     const bool mfma = L % 4 == 0 && reinterpret_cast<uintptr_t>(Q) % 16 == 0 && reinterpret_cast<uintptr_t>(X) % 16 == 0 &&
                       L <= (int64_t)8 * 1024 * 1024;
     const double chain = mfma ? 1025.0 + (double)L / 1024.0 : (double)L + 1.0;
-    const KnnF32Layout lay = knn_f32_layout(N, QT, k, cap);
+    const KnnF32Layout lay = knn_f32_layout(N, plan.QT, k, cap);
     char* w6 = nullptr;
     PVS_TRY(ws_reserve(ctx, WS_LISTS, lay.bytes, &w6));
     float* hy = lay.hy(w6);
@@ -420,16 +417,13 @@ PVS_EXPORT int pvs_l2_knn_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const v
     int* count = lay.count(w6);
     double* key = lay.key(w6);
     unsigned long long* ovf = lay.ovf(w6);
-    float* panel = nullptr;
-    PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
     PVS_HIP(hipMemsetAsync(ovf, 0, 8, ctx->stream));
     hipLaunchKernelGGL(nb_half_f32_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, yn, N, hy);
     PVS_HIP(hipGetLastError());
     int64_t n_cand = 0;
-    for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-      const int64_t qn = std::min(QT, nq - q0);
-      for (int64_t c0 = 0; c0 < N; c0 += NC) {
-        const int64_t cn = std::min(NC, N - c0);
+    for (int64_t q0 = 0; q0 < nq; q0 += plan.QT) {
+      const int64_t qn = plan.qn(q0);
+      PVS_TRY(panel_query_block<float>(ctx, plan, q0, [&](int64_t, int64_t, int64_t c0, int64_t cn, float* panel) -> int {
         PVS_TRY(launch_cosine_f32(ctx, Q + q0 * L, qn, X + c0 * L, cn, L, nullptr, nullptr, panel, cn));
         {
           ScopedTimer tm(ctx, T_MISC);
@@ -443,7 +437,8 @@ PVS_EXPORT int pvs_l2_knn_dev(pvs_ctx* ctx, const void* d_Q, int64_t nq, const v
                              xn + q0, d_max, L, chain, cap, c0, c0 == 0 ? 1 : 0, cand, count, ovf);
           PVS_HIP(hipGetLastError());
         }
-      }
+        return PVS_OK;
+      }));
       {
         ScopedTimer tm(ctx, T_RESCORE);
         const int64_t waves = qn * cap;
@@ -511,11 +506,8 @@ static int radius_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_
   } else {
     PVS_HIP(hipMemsetAsync(cursor, 0, (size_t)nq * 8, ctx->stream));
   }
-  const int64_t QT = std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)128 << 20) / N));
-  double* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * N * sizeof(double), &panel));
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
+  PVS_TRY(panel_for_each<double>(ctx, panel_full_rows(nq, N, panel_elems<double>()),
+                                 [&](int64_t q0, int64_t qn, int64_t, int64_t, double* panel) -> int {
     PVS_TRY(launch_cosine_f64_dev(ctx, Q + q0 * L, qn, X, N, L, nullptr, nullptr, panel, N));
     ScopedTimer tm(ctx, T_MISC);
     if (fill)
@@ -525,7 +517,8 @@ static int radius_impl(pvs_ctx* ctx, const void* d_Q, int64_t nq, const void* d_
       hipLaunchKernelGGL(nb_radius_kernel<false>, dim3((unsigned)((qn + 3) / 4)), dim3(256), 0, ctx->stream, panel, qn, N, N, xn + q0, yn,
                          r, (int64_t)0, cursor + q0, (int64_t*)nullptr, (double*)nullptr);
     PVS_HIP(hipGetLastError());
-  }
+    return PVS_OK;
+  }));
   if (!fill) PVS_HIP(hipMemcpyAsync(d_counts, cursor, (size_t)nq * 8, hipMemcpyDeviceToDevice, ctx->stream));
   return PVS_OK;
 }

@@ -8,6 +8,7 @@
 // intrinsics are plain inline `a * b` / `a + b` in the HIP headers: without the flag hipcc fuses them into an fma), so a
 // NumPy restatement with np.float32 element operations gives the same bits (tests/pq_numpy.py).  The pieces the inverted lists
 // (ivf.hip) use as well -- both kernels above, the table copy, the dword gather, the segment plan -- live in pq_common.hpp.
+#include "panel_plan.hpp"
 #include "pq_common.hpp"
 
 struct pvs_pq {
@@ -22,9 +23,6 @@ constexpr int PQ_SCAN_QB = 4;                  // queries per workgroup: the cod
 constexpr int PQ_SCAN_RPL = 4;                 // rows per lane at most
 constexpr int PQ_SCAN_REG_DW = 16;             // code dwords a lane keeps per row in registers (m <= 64)
 constexpr int PQ_SEG_ENTRIES = 40960;          // table entries per LDS segment: 160 KiB
-constexpr int64_t PQ_PANEL_ELEMS = (int64_t)1 << 22;   // score panel: 16 MiB, stays in the last-level cache between scan and select
-constexpr int64_t PQ_PANEL_MIN_COLS = 4096;
-constexpr int64_t PQ_PANEL_QUERIES = 1024;
 
 // ------------------------------------------------------------------------------------------------- scan
 // Workgroup = 512 lanes x rpl rows per lane (row = tile + r * 512 + lane: panel stores stay coalesced) x up to PQ_SCAN_QB
@@ -259,28 +257,15 @@ PVS_EXPORT int pvs_pq_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t nq
   PVS_ALIGNED(d_val, 4, "val");
   if (d_inv_q) PVS_ALIGNED(d_inv_q, 4, "inv_q");
   if (d_inv_db) PVS_ALIGNED(d_inv_db, 4, "inv_db");
-  // ranking deeper than 1024 pages through complete score rows (topk.hip), so the panel then spans all N columns
-  const bool deep = k > 1024;
-  if (deep && (merge || N > (int64_t)1 << 28)) PVS_FAIL(PVS_ERR_UNSUPPORTED, "ranking depth %d needs a single panel", k);
+  PanelPlan plan;   // panel_plan.hpp: the scan rule, complete rows for k > 1024
+  PVS_TRY(panel_ranking_plan(panel_scan, nq, N, k, merge, &plan));
   PVS_HIP(hipSetDevice(ctx->device));
-  const int64_t QT = deep ? std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 28) / N)) : std::min<int64_t>(nq, PQ_PANEL_QUERIES);
-  const int64_t NC = deep ? N : std::min<int64_t>(N, std::max<int64_t>(PQ_PANEL_MIN_COLS, PQ_PANEL_ELEMS / QT));
-  float* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, (size_t)QT * NC * sizeof(float), &panel));
   const int64_t tsize = (int64_t)m * ksub;
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
-    for (int64_t c0 = 0; c0 < N; c0 += NC) {
-      const int64_t cn = std::min(NC, N - c0);
-      {
-        ScopedTimer t(ctx, T_GEMM);   // the scoring slot: the scan stands where the similarity GEMM stands in the dense path
-        PVS_TRY(launch_pq_scan(ctx, d_lut + q0 * tsize, qn, m, ksub, d_codes + c0 * m, cn, d_inv_q ? d_inv_q + q0 : nullptr,
-                               d_inv_db ? d_inv_db + c0 : nullptr, panel));
-      }
-      PVS_TRY(launch_topk(ctx, panel, qn, cn, cn, k, col_offset + c0, (merge || c0 > 0) ? 1 : 0, d_idx + q0 * k, d_val + q0 * k));
-    }
-  }
-  return PVS_OK;
+  return panel_topk(ctx, plan, k, col_offset, merge, d_idx, d_val, [&](int64_t q0, int64_t qn, int64_t c0, int64_t cn, float* panel) -> int {
+    ScopedTimer t(ctx, T_GEMM);   // the scoring slot: the scan stands where the similarity GEMM stands in the dense path
+    return launch_pq_scan(ctx, d_lut + q0 * tsize, qn, m, ksub, d_codes + c0 * m, cn, d_inv_q ? d_inv_q + q0 : nullptr,
+                          d_inv_db ? d_inv_db + c0 : nullptr, panel);
+  });
 }
 
 PVS_EXPORT int pvs_rescore_rows_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_X, int64_t N, int64_t d,

@@ -5,7 +5,7 @@
 // gives the same bits: the matrix path (v_mfma_i32_32x32x32_i8) and the row path (v_dot4 on 16-byte loads) agree exactly, and a
 // NumPy restatement with int64 sums does too (tests/sq8_numpy.py).  The score is ((float)acc * inv_q) * inv_d: a conversion and
 // two multiplies, each rounded on its own; nothing here is a multiply followed by an add, so the unit needs no -ffp-contract=off.
-#include "common.hpp"
+#include "panel_plan.hpp"
 
 namespace pvs {
 namespace {
@@ -24,10 +24,6 @@ constexpr int SQ_MM_BK = 128;        // bytes of a row per k-block (four k-steps
 constexpr int SQ_ROW_THREADS = 1024;             // sixteen waves, each walking whole database rows
 constexpr int SQ_ROW_LDS = 128 * 1024;           // bytes of query codes per workgroup: 4 queries at L <= 32768, 1 at L = 131072
 constexpr int SQ_ROW_MAX_Q = 4;                  // PVS_OPT_SQ8_PATH = 0 takes the row path up to this many queries
-
-constexpr int64_t SQ_PANEL_ELEMS = (int64_t)1 << 22;   // score panel: 16 MiB, as the ADC scan's
-constexpr int64_t SQ_PANEL_MIN_COLS = 4096;
-constexpr int64_t SQ_PANEL_QUERIES = 1024;
 
 __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
@@ -321,29 +317,14 @@ PVS_EXPORT int pvs_sq8_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const floa
   PVS_ALIGNED(d_inv_db, 4, "inv_db");
   PVS_ALIGNED(d_idx, 8, "idx");
   PVS_ALIGNED(d_val, 4, "val");
-  // ranking deeper than 1024 pages through complete score rows (topk.hip), so the panel then spans all N columns
-  const bool deep = k > 1024;
-  if (deep && (merge || N > (int64_t)1 << 28)) PVS_FAIL(PVS_ERR_UNSUPPORTED, "ranking depth %d needs a single panel", k);
+  PanelPlan plan;   // panel_plan.hpp: the scan rule, as the ADC scan; complete rows for k > 1024
+  PVS_TRY(panel_ranking_plan(panel_scan, nq, N, k, merge, &plan));
   PVS_HIP(hipSetDevice(ctx->device));
   const int ld = PVS_SQ8_LD(L);
   const int path = ctx->opt[PVS_OPT_SQ8_PATH];
   const bool rows = path == 1 || (path == 0 && nq <= SQ_ROW_MAX_Q);
-  const int64_t QT = deep ? std::max<int64_t>(1, std::min<int64_t>(nq, ((int64_t)1 << 28) / N)) : std::min<int64_t>(nq, SQ_PANEL_QUERIES);
-  const int64_t NC = deep ? N : std::min<int64_t>(N, std::max<int64_t>(SQ_PANEL_MIN_COLS, SQ_PANEL_ELEMS / QT));
-  const Sq8PanelLayout lay = sq8_panel_layout((size_t)QT, (size_t)NC);
-  char* block = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, lay.bytes, &block));
-  float* panel = lay.panel(block);
-  for (int64_t q0 = 0; q0 < nq; q0 += QT) {
-    const int64_t qn = std::min(QT, nq - q0);
-    for (int64_t c0 = 0; c0 < N; c0 += NC) {
-      const int64_t cn = std::min(NC, N - c0);
-      {
-        ScopedTimer t(ctx, T_GEMM);   // the scoring slot, as the ADC scan
-        PVS_TRY(launch_sq8_scores(ctx, rows, d_qcodes + q0 * ld, d_inv_q + q0, qn, d_codes + c0 * ld, d_inv_db + c0, cn, ld, panel));
-      }
-      PVS_TRY(launch_topk(ctx, panel, qn, cn, cn, k, col_offset + c0, (merge || c0 > 0) ? 1 : 0, d_idx + q0 * k, d_val + q0 * k));
-    }
-  }
-  return PVS_OK;
+  return panel_topk(ctx, plan, k, col_offset, merge, d_idx, d_val, [&](int64_t q0, int64_t qn, int64_t c0, int64_t cn, float* panel) -> int {
+    ScopedTimer t(ctx, T_GEMM);   // the scoring slot, as the ADC scan
+    return launch_sq8_scores(ctx, rows, d_qcodes + q0 * ld, d_inv_q + q0, qn, d_codes + c0 * ld, d_inv_db + c0, cn, ld, panel);
+  });
 }

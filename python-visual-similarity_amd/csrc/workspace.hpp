@@ -20,10 +20,10 @@ namespace pvs {
 //                     fisher.hip: launch_gmm_posterior, launch_gmm_em_step, launch_fisher (table | responsibilities | partials);
 //                     learn.hip: launch_kmeans_step (twice), launch_label_sums, launch_gram, launch_seed_distances, launch_kmeanspp_run
 //   WS_PANEL_OUT      api.hip: pvs_vlad_encode, pvs_fisher_encode, pvs_cosine (offsets | outputs of the host entry points),
-//                     cosine_topk_impl, pvs_cosine_topk_f64_dev (score panels), pvs_kmeans_step_dev, pvs_gmm_em_step_dev, pvs_label_sums_dev,
-//                     pvs_gram_dev, pvs_seed_distances_dev, pvs_seed_pick_dev, pvs_min_update_dev (statistics); filter.hip:
-//                     launch_cosine_topk_filtered; neighbors.hip: knn_f64_rows, pvs_l2_knn_dev, radius_impl; pq.hip: pvs_pq_scan_topk_dev;
-//                     sq8.hip: pvs_sq8_topk_dev (score panel)
+//                     cosine_topk_impl (score row of one or two queries), pvs_kmeans_step_dev, pvs_gmm_em_step_dev, pvs_label_sums_dev,
+//                     pvs_gram_dev, pvs_seed_distances_dev, pvs_seed_pick_dev, pvs_min_update_dev (statistics); panel_plan.hpp:
+//                     panel_query_block (score panel, per query block) for cosine_topk_impl, pvs_cosine_topk_f64_dev, launch_cosine_topk_filtered,
+//                     knn_f64_rows, pvs_l2_knn_dev, radius_impl, pvs_pq_scan_topk_dev, pvs_sq8_topk_dev
 //   WS_PROJECTED      api.hip: project_if_needed (PCA rows), pvs_kmeanspp_run_dev; learn.hip: launch_label_sums (zero centres);
 //                     filter.hip: launch_cosine_topk_filtered (rows and lists of the overflowing queries)
 //   WS_AUX_ROWS       fisher.hip: materialise_f32 (RootSIFT rows); cosine.hip: launch_gemm_mfma, launch_gemm_f64 (split-K partials);
@@ -215,16 +215,6 @@ struct AsmkExpandLayout {
 inline AsmkExpandLayout asmk_expand_layout(size_t queries, size_t nchunks) {
   WsLayout<> l;
   return {l.add<uint32_t>(queries * nchunks * 64), l.add<int32_t>(queries * nchunks), l.add<int32_t>(queries * nchunks), l.bytes()};
-}
-
-// pvs_sq8_topk_dev, WS_PANEL_OUT: the float32 scores of one block of QT queries against one block of NC database rows
-struct Sq8PanelLayout {
-  WsPiece<float> panel;
-  size_t bytes;
-};
-inline Sq8PanelLayout sq8_panel_layout(size_t QT, size_t NC) {
-  WsLayout<> l;
-  return {l.add<float>(QT * NC), l.bytes()};
 }
 
 // pvs_kmeans_topm_dev with splits > 1, WS_LISTS: the partial lists [row][split][m], indices then values

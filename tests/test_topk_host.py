@@ -261,3 +261,26 @@ def test_paging_rows_and_padding_meet_their_conditions():
     q = tc.padded(p, 3)
     assert q.shape == (9, 66) and np.isposinf(q[:, 63:]).all() and np.array_equal(tk.bits(q[:, :63]), tk.bits(p))
     assert not np.isposinf(p[[0, 2, 3]]).any()
+
+
+# ------------------------------------------------------------------------------------------------ the score panels around the ranking
+def test_panel_plan_rules_hold_their_literal_values(tmp_path):
+    """csrc/bench/panel_plan_check.cpp includes only panel_plan.hpp, whose host part needs no HIP header, and runs as a stand-alone
+    program under the address and undefined-behaviour sanitizers (nothing is loaded into Python): the block sizes of the dense, scan,
+    filter and complete-row rules, the refusal of a deep ranking that needs more than one panel (status and message), the byte rule
+    of a panel and the query block of the host float64 entry, each against literal values worked out by hand; then, over a sweep of
+    (nq, N, k), that the blocks tile [0, nq) x [0, N) exactly once and stay within the 1 GiB budget unless a panel is one row."""
+    import os
+    import shutil
+    import subprocess
+
+    from conftest import REPO
+    src = os.path.join(REPO, "python-visual-similarity_amd", "csrc", "bench", "panel_plan_check.cpp")
+    cxx = next((c for c in (os.environ.get("CXX"), "g++", "c++", "clang++") if c and shutil.which(c)), None)
+    assert cxx, "no host C++ compiler (g++, c++ or clang++) on PATH"
+    exe = str(tmp_path / "panel_plan_check")
+    cc = subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined",
+                         "-fno-sanitize-recover=all", "-o", exe, src], capture_output=True, text=True, timeout=300)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0, run.stdout + run.stderr
