@@ -968,6 +968,38 @@ int pvs_sq8_encode_dev(pvs_ctx* ctx, const float* d_x, int64_t n, int L, int8_t*
 int pvs_sq8_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q, int64_t nq, const int8_t* d_codes,
                      const float* d_inv_db, int64_t N, int L, int k, int64_t col_offset, int merge, int64_t* d_idx, float* d_val);
 
+/* ---------------------------------------------------------------- threshold join and pair components
+ * "Everything at least this similar": the pairs (i, j) of query row i and database row j whose score reaches a threshold, and the
+ * connected components of such a pair list.
+ *   score       s(i, j) is the float32 value pvs_cosine_dev writes for query row i and database row j with the same inverse-norm
+ *               arrays (NULL = 1): the defined recurrence of the f32 GEMM, whatever the path, the tile size or the capacity.
+ *   hit         s(i, j) >= threshold, compared in float32.  A NaN score is never a hit; -0 >= 0 holds; the returned score bits are
+ *               the stored ones, not canonicalised.
+ *   self-join   PVS_RANGE_UPPER: the caller promises that Q and DB hold the same rows (nq == N); only j > i is emitted.  s(i, j) and
+ *               s(j, i) are the same bits: fma(a, b, c) and inv_a * inv_b are symmetric in the operands.
+ * flags: PVS_RANGE_UPPER = 1.  path: 0 auto, 1 exact f32 panels, 2 fp16 prefilter + exact re-score (silently 1 where it
+ * does not qualify).  tile: 0 = the plan's geometry; 1..32768 = row blocks and column panels of that many rows (test seams).
+ * Writes min(total, capacity) triples, *h_total = total; total > capacity -> PVS_ERR_CAPACITY with both valid, nothing
+ * written at or beyond capacity (capacity 0 with NULL outputs = count only).  Synchronises.
+ * Order on the device: row blocks ascending, within a row block column panels ascending, within a tile (row, col) ascending.
+ * h_stats (optional, int64[6]): [0] 1 if the prefilter ran, [1] row blocks redone by the exact path, [2] candidates re-scored,
+ * [3] tiles scored, [4] tiles skipped below the diagonal, [5] 0.
+ * path 0 is path 2 from 1024 query rows on and path 1 below (the measurement behind the rule: DESIGN.md section 24).  Path 2 qualifies
+ * as pvs_cosine_topk_filtered_dev does (16-byte aligned rows, L % 8 == 0, finite values) and needs both norm arrays.
+ * PVS_ERR_INVALID, before anything is launched: a non-finite threshold, unknown flags, PVS_RANGE_UPPER with nq != N, path outside
+ * 0..2, tile outside 0..32768, capacity outside 0..PVS_RANGE_MAX_CAPACITY, a missing pointer that will be written, L < 1, nq or N
+ * beyond 2^31 - 1.  nq == 0 or N == 0 is a no-op with total 0.  Timed on slots 2 (scores), 3 (count, scan, emit), 6 (fp16 rows), 7. */
+#define PVS_RANGE_UPPER 1
+#define PVS_RANGE_MAX_CAPACITY ((int64_t)1 << 40)
+int pvs_cosine_range_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_DB, int64_t N, int64_t L,
+                         const float* d_inv_q, const float* d_inv_db, float threshold, int flags, int path, int tile,
+                         int64_t capacity, int64_t* d_row, int64_t* d_col, float* d_val, int64_t* h_total, int64_t* h_stats);
+/* Connected components of an undirected pair list over N nodes: d_label[i] (int32) = the smallest node index of i's component.
+ * E == 0 gives the identity.  N < 2^31.  h_stats (optional, int64[2]): [0] rounds, [1] components.  A node id outside [0, N) is
+ * PVS_ERR_INVALID (checked on the device before the first round).  Synchronises. */
+int pvs_pair_components_dev(pvs_ctx* ctx, const int64_t* d_a, const int64_t* d_b, int64_t E, int64_t N, int32_t* d_label,
+                            int64_t* h_stats);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

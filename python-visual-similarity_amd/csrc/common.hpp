@@ -248,6 +248,11 @@ int cosine_topk_exact(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d
 int launch_cosine_topk_filtered(pvs_ctx* ctx, const float* Q, int64_t nq, const float* DB, int64_t N, int64_t L,
                                 const float* invq, const float* invdb, int k, int64_t col_offset, int64_t* d_idx, float* d_val,
                                 int64_t* h_stats);
+// pieces of the filtered top-k that the threshold join shares (filter.hip): the proven bound eps(L) of the fp16 prefilter scores and
+// the scaled fp16 rows (stats[0] += rows that are not finite or whose scale falls outside 2^+-30)
+double filter_error_bound(int64_t L);
+int launch_filter_rows_to_f16(pvs_ctx* ctx, const float* x, int64_t rows, int64_t L, const float* inv_in, void* out16, float* inv_out,
+                              unsigned long long* stats);
 int launch_cosine_f64(pvs_ctx* ctx, const double* A, int64_t M, const double* B, int64_t N, int64_t L, double* out);
 int launch_row_inv_norms_f64(pvs_ctx* ctx, const double* d_x, int64_t rows, int64_t L, double* d_inv);
 int launch_cosine_f64_dev(pvs_ctx* ctx, const double* A, int64_t M, const double* B, int64_t N, int64_t L, const double* inva,

@@ -82,6 +82,17 @@ __global__ __launch_bounds__(256) void filter_rows_to_f16_kernel(const float* __
   }
 }
 
+double filter_error_bound(int64_t L) { return filter_eps(L); }
+int launch_filter_rows_to_f16(pvs_ctx* ctx, const float* x, int64_t rows, int64_t L, const float* inv_in, void* out16, float* inv_out,
+                              unsigned long long* stats) {
+  if (rows <= 0) return PVS_OK;
+  ScopedTimer tm(ctx, T_MISC);
+  hipLaunchKernelGGL(filter_rows_to_f16_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->stream, x, rows, L, inv_in,
+                     static_cast<_Float16*>(out16), inv_out, stats);
+  PVS_HIP(hipGetLastError());
+  return PVS_OK;
+}
+
 // ---- candidates of a query: columns with approximate score >= (approximate k-th best) - margin, in column order.
 // One wave per query.  Slot s of query q lives at list s / k, entry s % k of the [n_lists][nq][k] layout that the
 // top-k merge kernel reads.  count[q] may exceed cap (overflow: that query is redone by the exact path).

@@ -23,14 +23,17 @@ namespace pvs {
 //                     cosine_topk_impl (score row of one or two queries), pvs_kmeans_step_dev, pvs_gmm_em_step_dev, pvs_label_sums_dev,
 //                     pvs_gram_dev, pvs_seed_distances_dev, pvs_seed_pick_dev, pvs_min_update_dev (statistics); panel_plan.hpp:
 //                     panel_query_block (score panel, per query block) for cosine_topk_impl, pvs_cosine_topk_f64_dev, launch_cosine_topk_filtered,
-//                     knn_f64_rows, pvs_l2_knn_dev, radius_impl, pvs_pq_scan_topk_dev, pvs_sq8_topk_dev
+//                     knn_f64_rows, pvs_l2_knn_dev, radius_impl, pvs_pq_scan_topk_dev, pvs_sq8_topk_dev, pvs_cosine_range_dev
 //   WS_PROJECTED      api.hip: project_if_needed (PCA rows), pvs_kmeanspp_run_dev; learn.hip: launch_label_sums (zero centres);
-//                     filter.hip: launch_cosine_topk_filtered (rows and lists of the overflowing queries)
+//                     filter.hip: launch_cosine_topk_filtered (rows and lists of the overflowing queries);
+//                     range.hip: pvs_cosine_range_dev (candidate staging of the prefiltered path)
 //   WS_AUX_ROWS       fisher.hip: materialise_f32 (RootSIFT rows); cosine.hip: launch_gemm_mfma, launch_gemm_f64 (split-K partials);
 //                     learn.hip: launch_label_sums (squared rows), launch_gram (tile accumulator)
-//   WS_FP16_ROWS      filter.hip: launch_cosine_topk_filtered
+//   WS_FP16_ROWS      filter.hip: launch_cosine_topk_filtered; range.hip: pvs_cosine_range_dev (prefiltered path)
 //   WS_LISTS          filter.hip: launch_cosine_topk_filtered; api.hip: pvs_cosine_topk_f64; vlad.hip: launch_assign;
-//                     neighbors.hip: knn_f64_rows, pvs_l2_knn_dev; assign_topm.hip: pvs_kmeans_topm_dev (partial lists, splits > 1)
+//                     neighbors.hip: knn_f64_rows, pvs_l2_knn_dev; assign_topm.hip: pvs_kmeans_topm_dev (partial lists, splits > 1);
+//                     range.hip: pvs_cosine_range_dev (norms of the fp16 rows | counters | row counts | row offsets),
+//                     pvs_pair_components_dev (counters)
 //   WS_NB_NORMS       neighbors.hip: pvs_l2_knn_dev, radius_impl
 //   WS_NB_F64_ROWS    neighbors.hip: to_f64_copies
 //   WS_DSIFT_TABLE    dsift.hip: pvs_dsift_dev

@@ -12,6 +12,7 @@
     from pvsim import KReciprocal                      # k-reciprocal re-ranking on the kNN lists of a DeviceIndex
     from pvsim import ASMKIndex                        # local-descriptor retrieval: ASMK* with binary signatures, an inverted file
     from pvsim import ASMKExpansion                    # its query expansion: majority-vote signatures and words the results agree on
+    from pvsim import find_duplicates                  # near-duplicate groups of a DeviceIndex: cosine threshold join + components
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -26,7 +27,9 @@ from .expand import QueryExpansion
 from .diffusion import Diffusion
 from .reciprocal import KReciprocal
 from .asmk import ASMKExpansion, ASMKIndex
+from .duplicates import DuplicateGroups, find_duplicates
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "Int8Index", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion"]
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "Int8Index", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion",
+           "DuplicateGroups", "find_duplicates"]

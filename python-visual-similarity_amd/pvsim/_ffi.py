@@ -30,6 +30,9 @@ OPT_UPDATE_WINDOW_ROWS = 6        # 0: windows of the in-place row compaction fr
 OPT_SQ8_PATH = 7                  # pvs_sq8_topk_dev: 0 chooses by the number of queries, 1 the row scan, 2 the int8 GEMM; same bits
 SQ8_PATH_AUTO, SQ8_PATH_ROWS, SQ8_PATH_MATRIX = 0, 1, 2
 SQ8_MAX_L = 131072                # 127^2 * L < 2^31
+RANGE_UPPER = 1                   # PVS_RANGE_UPPER: the self-join, pairs j > i only
+RANGE_PATH_AUTO, RANGE_PATH_EXACT, RANGE_PATH_FILTERED = 0, 1, 2      # pvs_cosine_range_dev: same triples on every path
+RANGE_MAX_CAPACITY = 1 << 40      # PVS_RANGE_MAX_CAPACITY
 SCAN_TILE = 2048                # PVS_SCAN_TILE of include/pvsim.h
 COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
 DIFFUSE_DOT_BLOCK, DIFFUSE_MAX_COLUMNS = 256, 65536   # PVS_DIFFUSE_DOT_BLOCK, PVS_DIFFUSE_MAX_COLUMNS of include/pvsim.h
@@ -174,6 +177,8 @@ SIGNATURES = {
                             _vp, _vp, _vp, _vp],
     "pvs_sq8_encode_dev": [_vp, _vp, _i64, _int, _vp, _vp],
     "pvs_sq8_topk_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _i64, _int, _vp, _vp],
+    "pvs_cosine_range_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, C.c_float, _int, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp],
+    "pvs_pair_components_dev": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

@@ -491,6 +491,30 @@ class Context:
         check(_ffi.lib().pvs_sq8_topk_dev(self.handle, ptr(d_qcodes), ptr(d_invq), int(nq), ptr(d_codes), ptr(d_invdb), int(N), int(L),
                                           int(k), int(col_offset), int(merge), ptr(d_idx), ptr(d_val)))
 
+    # threshold join and pair components
+    def cosine_range_dev(self, d_q, nq, d_db, N, L, d_invq, d_invdb, threshold, capacity, d_row, d_col, d_val, flags=0, path=0, tile=0):
+        """pvs_cosine_range_dev: every (row, col, score) with score >= threshold into the COO outputs int64 / int64 / float32 of
+        `capacity` entries, in the device order of the header.  Waits for the stream.
+        -> (total, dict(filtered, redone_exact, rescored, tiles, tiles_skipped)); raises CapacityError (args[1] = the total, args[2] =
+        the dict) when the total exceeds the capacity: the entries below the capacity are written then, nothing beyond."""
+        total, st = C.c_int64(0), (C.c_int64 * 6)()
+        status = _ffi.lib().pvs_cosine_range_dev(self.handle, ptr(d_q), int(nq), ptr(d_db), int(N), int(L), ptr(d_invq), ptr(d_invdb),
+                                                 float(threshold), int(flags), int(path), int(tile), int(capacity), ptr(d_row),
+                                                 ptr(d_col), ptr(d_val), C.byref(total), st)
+        stats = {"filtered": bool(st[0]), "redone_exact": int(st[1]), "rescored": int(st[2]), "tiles": int(st[3]),
+                 "tiles_skipped": int(st[4])}
+        if status == _ffi.PVS_ERR_CAPACITY:
+            raise _ffi.CapacityError(_ffi.lib().pvs_last_error().decode("utf-8", "replace"), int(total.value), stats)
+        check(status)
+        return int(total.value), stats
+
+    def pair_components_dev(self, d_a, d_b, E, N, d_label):
+        """pvs_pair_components_dev: int64 pair arrays of E entries over N nodes -> d_label int32 (N,), the smallest member of every
+        node's component.  Waits for the stream.  -> dict(rounds, components)"""
+        st = (C.c_int64 * 2)()
+        check(_ffi.lib().pvs_pair_components_dev(self.handle, ptr(d_a), ptr(d_b), int(E), int(N), ptr(d_label), st))
+        return {"rounds": int(st[0]), "components": int(st[1])}
+
     # inverted lists of the compact index (DESIGN.md section 14)
     def ivf_assign_dev(self, d_x, n, d, d_centroids, nlist, d_list, d_residual):
         check(_ffi.lib().pvs_ivf_assign_dev(self.handle, ptr(d_x), n, d, ptr(d_centroids), nlist, ptr(d_list), ptr(d_residual)))

@@ -14,7 +14,8 @@ import numpy as np
 from ._utils import cosine_similarity  # re-exported like the reference's `from ._utils import *`
 from .engine import default_context
 
-__all__ = ["retrieve_top_k_similar", "top_k_map", "top_k_accuracy", "rerank_spatial", "expand_verified"]
+__all__ = ["retrieve_top_k_similar", "top_k_map", "top_k_accuracy", "rerank_spatial", "expand_verified", "retrieve_similar",
+           "find_duplicates"]
 
 
 
@@ -183,6 +184,54 @@ def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.nda
     plan = _plan(dataset, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal)
     idx, val = plan.rank(_first_row(encoder, uploaded_image), k)
     return [(plan.paths[i], s) for i, s in zip(idx[0], val[0]) if i >= 0]     # unfilled slots of an IVF list are dropped
+
+
+class _ResidentF32:
+    """`dataset` as the float32 DeviceIndex a threshold search runs on: the index itself, or a dict uploaded for the block (the
+    dict-or-DeviceIndex rule of retrieve_top_k_similar).  Anything else is refused by name before the device is touched."""
+
+    def __init__(self, dataset, ctx=None):
+        from .duplicates import _check_index
+        from .index import DeviceIndex
+        self.temp = None
+        if isinstance(dataset, dict):
+            rows = np.array(list(dataset.values()))
+            if rows.dtype != np.float32:
+                raise NotImplementedError(f"threshold search runs on a float32 pvsim.index.DeviceIndex: these encodings are {rows.dtype}")
+            self.index = self.temp = DeviceIndex(dataset, ctx or default_context())
+        else:
+            _check_index(dataset)
+            self.index = dataset
+
+    def __enter__(self):
+        return self.index
+
+    def __exit__(self, *exc):
+        if self.temp is not None:
+            self.temp.close()
+
+
+def retrieve_similar(uploaded_image: np.ndarray, dataset, encoder, threshold: float, max_results=None) -> list[tuple[str, float]]:
+    """[(image_path, similarity)] of EVERY database entry whose cosine with the image is at least `threshold`, best first: the
+    threshold form of retrieve_top_k_similar.  `dataset`: a dict of float32 encodings (uploaded for the call) or a float32 DeviceIndex.
+    More than `max_results` entries raise CapacityError carrying their number."""
+    from .duplicates import _check_threshold
+    _check_threshold(threshold)
+    with _ResidentF32(dataset, getattr(encoder, "context", None)) as index:
+        q = _first_row(encoder, uploaded_image)
+        _check_features(q, index.shape[1])
+        _, idx, val = index.range_search(q, threshold, max_results=max_results)
+        paths = index._ledger.paths
+        return [(paths[i], s) for i, s in zip(idx, val)]
+
+
+def find_duplicates(dataset, threshold: float) -> list[list[str]]:
+    """The groups of near duplicates of `dataset` (a dict of float32 encodings or a float32 DeviceIndex): lists of paths whose
+    entries are connected by pairs with cosine at least `threshold`, members in index order, groups by their first member."""
+    from .duplicates import _check_threshold, find_duplicates as _find
+    _check_threshold(threshold)
+    with _ResidentF32(dataset) as index:
+        return _find(index, threshold).paths
 
 
 def expand_verified(uploaded_image: np.ndarray, ranked, index, encoder, k: int = 5, qe=None,

@@ -404,6 +404,75 @@ class DeviceIndex(Mapping):
         with self.ctx.scratch() as tmp:
             return self._rank_dev(tmp.upload(np.ascontiguousarray(q, dtype=self.dtype)).ptr, q.shape[0], int(k))
 
+    # ---- threshold search: everything at least this similar (pvsim/duplicates.py)
+    def _range_dev(self, tmp, d_q: int, nq: int, d_invq: int, threshold, limit, path: str, upper: bool):
+        """The threshold join of nq device rows (with their norms) against the resident rows, the triples left on the device:
+        -> (rows int64, cols int64, vals float32: DeviceBuffers of the scratch scope `tmp`, total, stats).  The first call offers
+        max(4096, 4 nq) entries (`limit` if that is smaller); a CapacityError is answered by ONE retry at the reported total, unless
+        the total exceeds `limit`: then it is raised again, carrying the total."""
+        from . import _ffi
+        from .duplicates import _path_code
+        n, L = self.shape
+        flags = _ffi.RANGE_UPPER if upper else 0
+        cap = max(4096, 4 * nq) if limit is None else min(max(4096, 4 * nq), int(limit))
+        for attempt in (0, 1):
+            bufs = tmp(max(cap, 1) * 8), tmp(max(cap, 1) * 8), tmp(max(cap, 1) * 4)
+            try:
+                total, stats = self.ctx.cosine_range_dev(d_q, nq, self._db.ptr, n, L, d_invq, self._inv.ptr, threshold, cap, bufs[0].ptr,
+                                                         bufs[1].ptr, bufs[2].ptr, flags=flags, path=_path_code(path))
+                return bufs + (total, dict(stats, retried=bool(attempt), threshold=float(threshold)))
+            except _ffi.CapacityError as e:
+                total = e.args[1]
+                if attempt or (limit is not None and total > int(limit)):
+                    raise _ffi.CapacityError(f"{total} results exceed the limit of {cap if limit is None else int(limit)}", total) from None
+                cap = total
+
+    def range_search(self, query_vecs: np.ndarray, threshold: float, *, max_results=None, path: str = "auto"):
+        """Every database row whose cosine with a query is at least `threshold` (rounded once to float32; the comparison is in
+        float32 on the score `rank` reports) -> CSR (indptr int64 (nq + 1,), indices int64, scores float32): query i owns the
+        entries indptr[i]:indptr[i + 1], ordered (score descending, index ascending) as every ranking.  `max_results` bounds the
+        total over all queries: more raises CapacityError carrying the total (args[1]).  path: "auto", "exact" (float32 panels) or
+        "filtered" (fp16 prefilter + exact re-score); the result is the same bytes.  `last_range_stats` holds what the device reported."""
+        from .duplicates import _check_index, _check_limit, _check_threshold
+        _check_index(self)
+        t = _check_threshold(threshold)
+        limit = _check_limit("max_results", max_results)
+        q = np.asarray(query_vecs)
+        if q.ndim != 2 or q.shape[1] != self.shape[1]:
+            raise ValueError("query and database dimensions differ")
+        if q.dtype != np.float32:
+            raise TypeError(f"a threshold search scores in float32: float32 queries on a float32 DeviceIndex, got {q.dtype}")
+        nq, n = q.shape[0], self.shape[0]
+        if nq == 0 or n == 0:
+            self.last_range_stats = {"threshold": float(t)}
+            return np.zeros(nq + 1, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+        with self.ctx.scratch() as tmp:
+            d_q, d_invq = tmp.upload(np.ascontiguousarray(q)), tmp(nq * 4)
+            self._row_inv_norms(d_q.ptr, nq, d_invq.ptr)
+            d_row, d_col, d_val, total, self.last_range_stats = self._range_dev(tmp, d_q.ptr, nq, d_invq.ptr, t, limit, path, False)
+            row, col, val = (d_row.download((total,), np.int64), d_col.download((total,), np.int64), d_val.download((total,), np.float32))
+        order = np.lexsort((col, -val, row))                 # one stable sort; -0 and +0 tie and the index decides
+        indptr = np.zeros(nq + 1, np.int64)
+        np.cumsum(np.bincount(row, minlength=nq), out=indptr[1:])
+        return indptr, col[order], val[order]
+
+    def similar_pairs(self, threshold: float, *, max_pairs=None, path: str = "auto"):
+        """The self-join: every pair of rows i < j whose cosine is at least `threshold` -> (i int64, j int64, score float32) in
+        (i, j) order.  `max_pairs` bounds the number of pairs: more raises CapacityError carrying the total.  `path` as range_search."""
+        from .duplicates import _check_index, _check_limit, _check_threshold
+        _check_index(self)
+        t = _check_threshold(threshold)
+        limit = _check_limit("max_pairs", max_pairs)
+        n = self.shape[0]
+        if n == 0:
+            self.last_range_stats = {"threshold": float(t)}
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+        with self.ctx.scratch() as tmp:
+            d_row, d_col, d_val, total, self.last_range_stats = self._range_dev(tmp, self._db.ptr, n, self._inv.ptr, t, limit, path, True)
+            row, col, val = (d_row.download((total,), np.int64), d_col.download((total,), np.int64), d_val.download((total,), np.float32))
+        order = np.lexsort((col, row))
+        return row[order], col[order], val[order]
+
     # ---- query expansion and database-side augmentation (pvsim/expand.py, DESIGN.md section 13)
     def _list_weights(self, idx, val, scheme, alpha):
         """weights of list entries `idx` with similarities `val`: expansion_weights(...) * inv_norms[idx], 0 on the -1 slots"""
