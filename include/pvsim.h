@@ -1000,6 +1000,38 @@ int pvs_cosine_range_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float
 int pvs_pair_components_dev(pvs_ctx* ctx, const int64_t* d_a, const int64_t* d_b, int64_t E, int64_t N, int32_t* d_label,
                             int64_t* h_stats);
 
+/* ---------------------------------------------------------------- subset search: the k best among an allowed set
+ * S is a set of row indices of an index with N rows, 1 <= |S| <= N.  The subset ranking of a query is the full ranking of the index
+ * with the rows outside S deleted, cut to k, 1 <= k <= |S|: (score descending, index ascending), indices in the numbering of the full
+ * index, and the score bits those of the unrestricted entry for that pair -- the float32 value pvs_cosine_dev writes, or
+ * ((float)acc * inv_q) * inv_d on code rows.  A score depends on its two rows and two factors alone, so the result does not depend on
+ * the path, the tile, the chunk or how S was given; a row outside S never appears; S = all rows gives the unrestricted lists.
+ *   handle      h_ids is a HOST array of ns ids, strictly ascending within [0, N), N < 2^31; it is checked on the host before anything
+ *               is allocated (PVS_ERR_INVALID).  The handle owns the ids on the device, a bitmask of ceil(N / 32) uint32 words on the
+ *               device (row i is bit i & 31 of word i >> 5, built on the host; the bits beyond N are zero) and a host copy of the ids.
+ *               pvs_subset_create waits for the upload; pvs_subset_destroy waits for the stream.
+ *   path        0 auto (the listed path iff 4 ns <= N), 1 mask, 2 listed.
+ *               mask: the panels of the unrestricted entry (tile > 0: tile x tile blocks, a test seam); a column panel that holds no
+ *               id is skipped on the host, the others are scored by the unrestricted entry's scorer, the columns outside S are set to
+ *               -inf and the panel is ranked.  listed: the ids in chunks of at most 256 MiB of rows (tile > 0: at most tile rows);
+ *               rows and factors are gathered into the workspace, scored by the same scorer, ranked by position in the id list and
+ *               the positions are replaced by the ids at the end.
+ *   outputs     d_idx int64 [nq][k], d_val float32 [nq][k]; k <= |S| makes every entry a row of S with its score.
+ *   h_stats     optional int64[4]: [0] the path taken (1 or 2), [1] panels scored (mask: per query block and column panel) or chunks
+ *               gathered (listed), [2] column panels skipped (mask, per query block), [3] rows gathered (listed: ns).
+ * PVS_ERR_INVALID, before anything is launched: k < 1, k > ns, k > 1024, a handle made for another N, path outside 0..2, tile
+ * outside 0..32768.  nq == 0 is a no-op.  Both entries enqueue on the context's stream and do not wait for it.  The int8 entry reads
+ * PVS_OPT_SQ8_PATH as pvs_sq8_topk_dev does.  Timed on slots 2 (scores), 3 (mask, ranking), 6 (gather, positions -> ids). */
+typedef struct pvs_subset pvs_subset;
+int pvs_subset_create(pvs_ctx* ctx, const int64_t* h_ids, int64_t ns, int64_t N, pvs_subset** out);
+int pvs_subset_destroy(pvs_ctx* ctx, pvs_subset* subset);
+int pvs_cosine_topk_subset_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_DB, int64_t N, int64_t L,
+                               const float* d_inv_q, const float* d_inv_db, const pvs_subset* subset, int k, int path, int tile,
+                               int64_t* d_idx, float* d_val, int64_t* h_stats);
+int pvs_sq8_topk_subset_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q, int64_t nq, const int8_t* d_codes,
+                            const float* d_inv_db, int64_t N, int L, const pvs_subset* subset, int k, int path, int tile,
+                            int64_t* d_idx, float* d_val, int64_t* h_stats);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

@@ -260,6 +260,10 @@ int launch_cosine_f64_dev(pvs_ctx* ctx, const double* A, int64_t M, const double
 bool cosine_dense_rows_eligible(const float* Q, const float* DB, int64_t nq, int64_t L);
 int launch_cosine_dense_rows(pvs_ctx* ctx, const float* Q, int64_t nq, const float* DB, int64_t N, int64_t L, const float* invq,
                              const float* invdb, float* scores, int64_t ld);
+// the int8 scorer of one panel and the path rule in front of it (sq8.hip): rows = the one-pass row scan, otherwise the int8 GEMM
+bool sq8_row_scan(const pvs_ctx* ctx, int64_t nq);
+int launch_sq8_scores(pvs_ctx* ctx, bool rows, const int8_t* qc, const float* inv_q, int64_t qn, const int8_t* dc, const float* inv_d,
+                      int64_t cn, int ld, float* panel);
 int launch_topk(pvs_ctx* ctx, const float* scores, int64_t nq, int64_t ncols, int64_t ld, int k,
                 int64_t col_offset, int merge, int64_t* d_idx, float* d_val);
 int launch_topk_merge(pvs_ctx* ctx, const int64_t* idx_lists, const float* val_lists, int n_lists, int64_t nq,

@@ -256,7 +256,15 @@ int launch_sq8_rows_qb(pvs_ctx* ctx, const int8_t* qc, const float* inv_q, int64
                     panel, cn);
 }
 
-// one panel: scores of qn queries against cn rows into panel[qn][cn]
+}  // namespace
+
+// PVS_OPT_SQ8_PATH: 1 the row scan, 2 the int8 GEMM, 0 the row scan up to SQ_ROW_MAX_Q queries of the call (subset.hip reads it too)
+bool sq8_row_scan(const pvs_ctx* ctx, int64_t nq) {
+  const int path = ctx->opt[PVS_OPT_SQ8_PATH];
+  return path == 1 || (path == 0 && nq <= SQ_ROW_MAX_Q);
+}
+
+// one panel: scores of qn queries against cn rows into panel[qn][cn] (declared in common.hpp: subset.hip scores its panels with it)
 int launch_sq8_scores(pvs_ctx* ctx, bool rows, const int8_t* qc, const float* inv_q, int64_t qn, const int8_t* dc, const float* inv_d,
                       int64_t cn, int ld, float* panel) {
   if (rows) {
@@ -271,7 +279,6 @@ int launch_sq8_scores(pvs_ctx* ctx, bool rows, const int8_t* qc, const float* in
   return PVS_OK;
 }
 
-}  // namespace
 }  // namespace pvs
 
 using namespace pvs;
@@ -321,8 +328,7 @@ PVS_EXPORT int pvs_sq8_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const floa
   PVS_TRY(panel_ranking_plan(panel_scan, nq, N, k, merge, &plan));
   PVS_HIP(hipSetDevice(ctx->device));
   const int ld = PVS_SQ8_LD(L);
-  const int path = ctx->opt[PVS_OPT_SQ8_PATH];
-  const bool rows = path == 1 || (path == 0 && nq <= SQ_ROW_MAX_Q);
+  const bool rows = sq8_row_scan(ctx, nq);
   return panel_topk(ctx, plan, k, col_offset, merge, d_idx, d_val, [&](int64_t q0, int64_t qn, int64_t c0, int64_t cn, float* panel) -> int {
     ScopedTimer t(ctx, T_GEMM);   // the scoring slot, as the ADC scan
     return launch_sq8_scores(ctx, rows, d_qcodes + q0 * ld, d_inv_q + q0, qn, d_codes + c0 * ld, d_inv_db + c0, cn, ld, panel);

@@ -23,10 +23,12 @@ namespace pvs {
 //                     cosine_topk_impl (score row of one or two queries), pvs_kmeans_step_dev, pvs_gmm_em_step_dev, pvs_label_sums_dev,
 //                     pvs_gram_dev, pvs_seed_distances_dev, pvs_seed_pick_dev, pvs_min_update_dev (statistics); panel_plan.hpp:
 //                     panel_query_block (score panel, per query block) for cosine_topk_impl, pvs_cosine_topk_f64_dev, launch_cosine_topk_filtered,
-//                     knn_f64_rows, pvs_l2_knn_dev, radius_impl, pvs_pq_scan_topk_dev, pvs_sq8_topk_dev, pvs_cosine_range_dev
+//                     knn_f64_rows, pvs_l2_knn_dev, radius_impl, pvs_pq_scan_topk_dev, pvs_sq8_topk_dev, pvs_cosine_range_dev,
+//                     pvs_cosine_topk_subset_dev, pvs_sq8_topk_subset_dev
 //   WS_PROJECTED      api.hip: project_if_needed (PCA rows), pvs_kmeanspp_run_dev; learn.hip: launch_label_sums (zero centres);
 //                     filter.hip: launch_cosine_topk_filtered (rows and lists of the overflowing queries);
 //                     range.hip: pvs_cosine_range_dev (candidate staging of the prefiltered path)
+//                     subset.hip: pvs_cosine_topk_subset_dev, pvs_sq8_topk_subset_dev (gathered rows | factors of one chunk, listed path)
 //   WS_AUX_ROWS       fisher.hip: materialise_f32 (RootSIFT rows); cosine.hip: launch_gemm_mfma, launch_gemm_f64 (split-K partials);
 //                     learn.hip: launch_label_sums (squared rows), launch_gram (tile accumulator)
 //   WS_FP16_ROWS      filter.hip: launch_cosine_topk_filtered; range.hip: pvs_cosine_range_dev (prefiltered path)

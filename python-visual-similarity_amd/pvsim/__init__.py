@@ -13,6 +13,7 @@
     from pvsim import ASMKIndex                        # local-descriptor retrieval: ASMK* with binary signatures, an inverted file
     from pvsim import ASMKExpansion                    # its query expansion: majority-vote signatures and words the results agree on
     from pvsim import find_duplicates                  # near-duplicate groups of a DeviceIndex: cosine threshold join + components
+    from pvsim import Subset                           # an allowed set of images: index.rank(q, k, allowed=...) ranks within it
 
 The arithmetic (centroid assignment, VLAD / Fisher aggregation, normalisation, cosine GEMM, top-k) runs in
 hand-written HIP kernels for gfx950 behind a C-ABI (include/pvsim.h) bound with ctypes; there is no CPU
@@ -28,8 +29,9 @@ from .diffusion import Diffusion
 from .reciprocal import KReciprocal
 from .asmk import ASMKExpansion, ASMKIndex
 from .duplicates import DuplicateGroups, find_duplicates
+from .subset import Subset
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
            "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "Int8Index", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion",
-           "DuplicateGroups", "find_duplicates"]
+           "DuplicateGroups", "find_duplicates", "Subset"]

@@ -33,6 +33,8 @@ SQ8_MAX_L = 131072                # 127^2 * L < 2^31
 RANGE_UPPER = 1                   # PVS_RANGE_UPPER: the self-join, pairs j > i only
 RANGE_PATH_AUTO, RANGE_PATH_EXACT, RANGE_PATH_FILTERED = 0, 1, 2      # pvs_cosine_range_dev: same triples on every path
 RANGE_MAX_CAPACITY = 1 << 40      # PVS_RANGE_MAX_CAPACITY
+SUBSET_PATH_AUTO, SUBSET_PATH_MASK, SUBSET_PATH_LISTED = 0, 1, 2      # pvs_*_topk_subset_dev: same lists on every path
+SUBSET_MAX_K = 1024               # a subset ranking is one page of the top-k kernels
 SCAN_TILE = 2048                # PVS_SCAN_TILE of include/pvsim.h
 COMBINE_CHUNK_BYTES, COMBINE_BATCH = 8192, 8     # PVS_COMBINE_CHUNK_BYTES, PVS_COMBINE_BATCH of include/pvsim.h
 DIFFUSE_DOT_BLOCK, DIFFUSE_MAX_COLUMNS = 256, 65536   # PVS_DIFFUSE_DOT_BLOCK, PVS_DIFFUSE_MAX_COLUMNS of include/pvsim.h
@@ -179,6 +181,10 @@ SIGNATURES = {
     "pvs_sq8_topk_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _i64, _int, _vp, _vp],
     "pvs_cosine_range_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, C.c_float, _int, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp],
     "pvs_pair_components_dev": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
+    "pvs_subset_create": [_vp, _vp, _i64, _i64, _pp],
+    "pvs_subset_destroy": [_vp, _vp],
+    "pvs_cosine_topk_subset_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp],
+    "pvs_sq8_topk_subset_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _int, _int, _int, _vp, _vp, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

@@ -97,6 +97,11 @@ class PQTable(_Handle):
     m = ksub = dsub = 0
 
 
+class SubsetHandle(_Handle):
+    _destroy = "pvs_subset_destroy"
+    n = size = 0
+
+
 class DeviceBuffer:
     """A block of device memory owned by a Context (pvs_malloc / pvs_free); .ptr is the raw device address."""
 
@@ -507,6 +512,36 @@ class Context:
             raise _ffi.CapacityError(_ffi.lib().pvs_last_error().decode("utf-8", "replace"), int(total.value), stats)
         check(status)
         return int(total.value), stats
+
+    # subset search
+    def subset_create(self, ids: np.ndarray, n: int) -> SubsetHandle:
+        """pvs_subset_create: ids int64, strictly ascending within [0, n) (checked there: ValueError) -> the handle that owns the ids
+        and the bitmask on the device"""
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        h = C.c_void_p()
+        check(_ffi.lib().pvs_subset_create(self.handle, ptr(ids), int(ids.size), int(n), C.byref(h)))
+        s = SubsetHandle(self, h)
+        s.n, s.size = int(n), int(ids.size)
+        return s
+
+    @staticmethod
+    def _subset_stats(st) -> dict:
+        return {"path": ("auto", "mask", "listed")[int(st[0])] if 0 <= int(st[0]) <= 2 else int(st[0]), "scored": int(st[1]),
+                "panels_skipped": int(st[2]), "rows_gathered": int(st[3])}
+
+    def cosine_topk_subset_dev(self, d_q, nq, d_db, N, L, d_invq, d_invdb, subset, k, d_idx, d_val, path=0, tile=0) -> dict:
+        """pvs_cosine_topk_subset_dev -> dict(path, scored, panels_skipped, rows_gathered)"""
+        st = (C.c_int64 * 4)()
+        check(_ffi.lib().pvs_cosine_topk_subset_dev(self.handle, ptr(d_q), int(nq), ptr(d_db), int(N), int(L), ptr(d_invq), ptr(d_invdb),
+                                                    subset.handle, int(k), int(path), int(tile), ptr(d_idx), ptr(d_val), st))
+        return self._subset_stats(st)
+
+    def sq8_topk_subset_dev(self, d_qcodes, d_invq, nq, d_codes, d_invdb, N, L, subset, k, d_idx, d_val, path=0, tile=0) -> dict:
+        """pvs_sq8_topk_subset_dev -> dict(path, scored, panels_skipped, rows_gathered)"""
+        st = (C.c_int64 * 4)()
+        check(_ffi.lib().pvs_sq8_topk_subset_dev(self.handle, ptr(d_qcodes), ptr(d_invq), int(nq), ptr(d_codes), ptr(d_invdb), int(N), int(L),
+                                                 subset.handle, int(k), int(path), int(tile), ptr(d_idx), ptr(d_val), st))
+        return self._subset_stats(st)
 
     def pair_components_dev(self, d_a, d_b, E, N, d_label):
         """pvs_pair_components_dev: int64 pair arrays of E entries over N nodes -> d_label int32 (N,), the smallest member of every

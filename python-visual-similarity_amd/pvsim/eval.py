@@ -77,14 +77,52 @@ class _Plan:
         return self._index_of(path)
 
 
-def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None, reciprocal=None) -> _Plan:
+def _check_allowed(dataset, expand, rerank, nprobe, diffuse, reciprocal) -> None:
+    """allowed= ranks within a set on a dict, a float32 DeviceIndex and an Int8Index, first stage only: everything else is refused by name"""
+    from .asmk import ASMKIndex
+    from .compact import CompactIndex
+    for name, given in (("expand", expand is not None), ("rerank", bool(rerank)), ("nprobe", nprobe is not None),
+                        ("diffuse", diffuse is not None), ("reciprocal", reciprocal is not None)):
+        if given:
+            raise ValueError(f"allowed= together with {name}= is not built: a subset ranking is the first stage alone")
+    if isinstance(dataset, (CompactIndex, ASMKIndex)):
+        raise ValueError(f"allowed= on {'an' if type(dataset).__name__[0] in 'AI' else 'a'} {type(dataset).__name__} is not built: subset "
+                         "search covers a dict, a float32 DeviceIndex and an Int8Index")
+
+
+def _no_full_subset_ranking():
+    raise ValueError("allowed= together with k=None is not built: a subset ranking is a finite list, pass k")
+
+
+def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None, reciprocal=None, allowed=None) -> _Plan:
     """What `dataset` is (a dict, a DeviceIndex, an Int8Index, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
-    refusal is raised here, before anything is encoded), and how it ranks.  A DeviceIndex is never asked for its host rows."""
+    refusal is raised here, before anything is encoded), and how it ranks.  A DeviceIndex is never asked for its host rows.
+    `allowed`: one set of images for all queries (a pvsim.Subset of the index, indices, a boolean mask or paths); k is then clamped to
+    the size of the set.  A dict is cut to the allowed paths here, on the host, and ranked as any dict."""
     from .compact import CompactIndex, IVFCompactIndex
     from .index import DeviceIndex
     from .quantized import Int8Index
+    if allowed is not None:
+        _check_allowed(dataset, expand, rerank, nprobe, diffuse, reciprocal)
     dense, compact = isinstance(dataset, DeviceIndex), isinstance(dataset, CompactIndex)
     int8 = isinstance(dataset, Int8Index)
+    if allowed is not None and (dense or int8):
+        from .subset import Subset, _index_of, _kind, normalise
+        _kind(dataset)                                            # a float64 DeviceIndex: TypeError naming float32
+        if isinstance(allowed, Subset):
+            allowed.check(dataset)
+            size = len(allowed)
+        else:                                                     # sorted ids; rank makes and destroys the device copy per call
+            allowed = normalise(allowed, len(dataset), _index_of(dataset))
+            size = int(allowed.size)
+
+        def within(q, k):
+            if k is None:
+                _no_full_subset_ranking()
+            if dense:
+                _check_features(q, dataset.shape[1])
+            return _clamped(lambda q, kk: dataset.rank(q, kk, allowed=allowed), size, q, k)
+        return _Plan(len(dataset), dataset._ledger.paths, within, index_of=dataset._ledger.index_of)
     if int8:                                      # one ranking, the cosine of the codes: every option names what it needs instead
         if expand is not None:
             raise ValueError("expand= needs the full-precision rows: use a dict or a DeviceIndex, not an Int8Index")
@@ -156,6 +194,15 @@ def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=
             rank = lambda q, k: _clamped(plain, n, q, k)
     else:
         paths, matrix = list(dataset.keys()), np.array(list(dataset.values()))        # stacked as the reference does (eval.py:28)
+        if allowed is not None:                                     # the map cut to the allowed paths, in index order
+            from .subset import Subset, normalise
+            if isinstance(allowed, Subset):
+                raise ValueError("a pvsim.Subset belongs to the index it was made for: on a dict pass indices, a boolean mask or paths")
+            pos = {p: i for i, p in enumerate(paths)}
+            ids = normalise(allowed, len(paths), pos.__getitem__)
+            paths, matrix = [paths[i] for i in ids.tolist()], matrix[ids]
+            cut = lambda q, k: _no_full_subset_ranking() if k is None else _rank(q, matrix, k, ctx)
+            return _Plan(matrix.shape[0], paths, cut, matrix)
 
         def expanded(q, kk, members=None):                          # on a DeviceIndex that holds the dict for this call
             temp = DeviceIndex(dict(zip(paths, matrix)), ctx or default_context())
@@ -173,15 +220,18 @@ def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=
 
 
 def retrieve_top_k_similar(uploaded_image: np.ndarray, dataset: dict[str, np.ndarray], encoder,
-                           k: int = 5, rerank: int = 0, expand=None, nprobe=None, diffuse=None, reciprocal=None) -> list[tuple[str, float]]:
+                           k: int = 5, rerank: int = 0, expand=None, nprobe=None, diffuse=None, reciprocal=None,
+                           allowed=None) -> list[tuple[str, float]]:
     """[(image_path, similarity)] of the k most similar database entries, best first.  `rerank=R` (CompactIndex only): the
     ADC top-R re-ranked by the exact cosine of the kept projected rows.  `expand`: a pvsim.expand.QueryExpansion; the list is
     then the ranking of the expanded query (dict or DeviceIndex; a dict is uploaded for the call).  `nprobe` (IVFCompactIndex
     only, and required there): the inverted lists scanned; the list is shorter than k when they hold fewer rows.  `diffuse`: a
     pvsim.Diffusion graph built on `dataset` (a DeviceIndex); the list is then the diffusion ranking and its float64 scores, and
     `rerank`, `expand` and `nprobe` are excluded.  `reciprocal`: a pvsim.KReciprocal built on `dataset` (a DeviceIndex); the list is
-    then the k-reciprocal re-ranking of the first max(k, 80) results and its float64 scores, and every other option is excluded."""
-    plan = _plan(dataset, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal)
+    then the k-reciprocal re-ranking of the first max(k, 80) results and its float64 scores, and every other option is excluded.
+    `allowed`: rank within this set of images only (a pvsim.Subset of the index, indices, a boolean mask of the entries or paths; a
+    dict, a float32 DeviceIndex or an Int8Index; every other option is excluded); k is clamped to the size of the set."""
+    plan = _plan(dataset, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal, allowed)
     idx, val = plan.rank(_first_row(encoder, uploaded_image), k)
     return [(plan.paths[i], s) for i, s in zip(idx[0], val[0]) if i >= 0]     # unfilled slots of an IVF list are dropped
 
@@ -281,22 +331,22 @@ def rerank_spatial(uploaded_image: np.ndarray, hits, local_index, verifier, k: i
     return (front + back)[:k]
 
 
-def _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal=None):
+def _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal=None, allowed=None):
     """-> (ranked indices (nq, k'), -1 in the unfilled slots at the end of an IVF list; the label of every database entry)"""
-    plan = _plan(encoding_map, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal)
+    plan = _plan(encoding_map, expand, rerank, nprobe, diffuse, getattr(encoder, "context", None), reciprocal, allowed)
     idx, _ = plan.rank(_first_rows(encoder, images), k)
     return idx, [path_labels_dict[p] for p in plan.paths]
 
 
 def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
               path_labels_dict: dict[str, int], encoder, k: int = None, expand=None, rerank: int = 0, nprobe=None, diffuse=None,
-              reciprocal=None) -> float:
+              reciprocal=None, allowed=None) -> float:
     """Mean average precision; R is counted inside the (possibly truncated) ranked list (eval.py:95).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
     there), `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) and `reciprocal` (a pvsim.KReciprocal of it) as in
-    retrieve_top_k_similar."""
+    retrieve_top_k_similar.  `allowed`: one set of database images for all queries, as there (k is required then)."""
     labels = list(image_labels)
-    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal)
+    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal, allowed)
     aps = []
     for row, true_label in zip(idx, labels):
         relevant_count, precision_sum = 0, 0.0
@@ -310,13 +360,13 @@ def top_k_map(images: Iterable[np.ndarray], image_labels: Iterable[int], encodin
 
 def top_k_accuracy(images: Iterable[np.ndarray], image_labels: Iterable[int], encoding_map: dict[str, np.ndarray],
                    path_labels_dict: dict[str, int], encoder, k: int, expand=None, rerank: int = 0, nprobe=None, diffuse=None,
-                   reciprocal=None) -> float:
+                   reciprocal=None, allowed=None) -> float:
     """Fraction of queries with at least one same-label entry among their k nearest (eval.py:102-145).  `expand`: rank the
     expanded queries (pvsim.expand.QueryExpansion).  `rerank` (a CompactIndex) and `nprobe` (an IVFCompactIndex, required
     there), `diffuse` (a pvsim.Diffusion graph of the DeviceIndex) and `reciprocal` (a pvsim.KReciprocal of it) as in
-    retrieve_top_k_similar."""
+    retrieve_top_k_similar.  `allowed`: one set of database images for all queries, as there."""
     images = list(images)
     labels = list(image_labels)
-    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal)
+    idx, db_labels = _ranked_labels(images, encoding_map, path_labels_dict, encoder, k, expand, rerank, nprobe, diffuse, reciprocal, allowed)
     correct = sum(1 for row, true_label in zip(idx, labels) if any(i >= 0 and db_labels[i] == true_label for i in row))
     return float(correct / len(images))

@@ -394,8 +394,21 @@ class DeviceIndex(Mapping):
             self._row_inv_norms(d_q, nq, d_inv.ptr)
             return d_inv.download((nq,), self.dtype)
 
-    def rank(self, query_vecs: np.ndarray, k: int):
-        """-> (idx (nq, k) int64, val (nq, k)) of the queries against the resident database; 1 <= k <= N."""
+    def subset(self, allowed):
+        """A pvsim.Subset of this index (float32 only): `allowed` is a 1-d integer array of indices in any order, a boolean mask of
+        length N, or an iterable of paths.  Pass it to `rank(..., allowed=)` as often as needed; it is a snapshot and refuses once rows
+        were added or removed."""
+        from .subset import Subset
+        return Subset(self, allowed)
+
+    def rank(self, query_vecs: np.ndarray, k: int, allowed=None, subset_path: str = "auto"):
+        """-> (idx (nq, k) int64, val (nq, k)) of the queries against the resident database; 1 <= k <= N.
+        `allowed` (a pvsim.Subset of this index, or what `subset` takes): the same ranking with every row outside the set deleted,
+        1 <= k <= |S| <= N and k <= 1024, float32 index and queries only; `subset_path` "auto", "mask" or "listed" pins how it is
+        computed, never what; `last_subset_stats` holds what the device reported."""
+        if allowed is not None:
+            from .subset import rank_subset
+            return rank_subset(self, query_vecs, k, allowed, subset_path)
         q = np.asarray(query_vecs)
         if q.ndim != 2 or q.shape[1] != self.shape[1]:
             raise ValueError("query and database dimensions differ")

@@ -133,6 +133,7 @@ class Int8Index:
         if len(set(self._ledger.paths)) != len(self._ledger.paths):
             raise ValueError("a path is named twice")
         self._cap = int(cap)
+        self.modifications = 0            # adds and removes since construction: a pvsim.Subset is a snapshot of the rows
         self._codes = ctx.buffer(max(self._cap * self._ld, 16))
         self._inv = ctx.buffer(max(self._cap * 4, 16))
 
@@ -229,6 +230,7 @@ class Int8Index:
         else:
             self._encode_host(mat, n)
         self._ledger.append(paths)
+        self.modifications += 1
 
     def remove(self, paths) -> None:
         """The named images leave, the others keep their order.  An unknown path is a KeyError, a path named twice a ValueError, both
@@ -243,14 +245,26 @@ class Int8Index:
             self.ctx.compact_rows_dev(self._inv.ptr, n, 4, keep.ptr, pos.ptr, self._inv.ptr, first=int(idx[0]))
             self.ctx.sync()
         self._ledger.remove(idx)
+        self.modifications += 1
 
     def __delitem__(self, path) -> None:
         self.remove([path])
 
     # ---- search
-    def rank(self, query_vecs, k: int):
+    def subset(self, allowed):
+        """A pvsim.Subset of this index: `allowed` is a 1-d integer array of indices in any order, a boolean mask of length N, or an
+        iterable of paths.  A snapshot: it refuses once rows were added or removed."""
+        from .subset import Subset
+        return Subset(self, allowed)
+
+    def rank(self, query_vecs, k: int, allowed=None, subset_path: str = "auto"):
         """-> (idx (nq, k) int64, val (nq, k) float32): the queries are quantised by the rule of the rows and ranked by the cosine of
-        the codes, (score descending, index ascending); 1 <= k <= N."""
+        the codes, (score descending, index ascending); 1 <= k <= N.
+        `allowed` (a pvsim.Subset of this index, or what `subset` takes): the same ranking with every row outside the set deleted,
+        1 <= k <= |S| and k <= 1024; `subset_path` "auto", "mask" or "listed" pins how it is computed, never what."""
+        if allowed is not None:
+            from .subset import rank_subset
+            return rank_subset(self, query_vecs, k, allowed, subset_path)
         q = _f32_rows(query_vecs, "query")
         n, L = self.shape
         if q.shape[1] != L:
