@@ -1032,6 +1032,40 @@ int pvs_sq8_topk_subset_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d
                             const float* d_inv_db, int64_t N, int L, const pvs_subset* subset, int k, int path, int tile,
                             int64_t* d_idx, float* d_val, int64_t* h_stats);
 
+/* ---------------------------------------------------------------- inverted lists over the int8 code rows
+ * Sub-linear search with the int8 score itself: the code rows of section 22 cut into nlist inverted lists, a query scores the rows
+ * of its nprobe best lists only.  All arithmetic is section 22's (code row, ld, inv, the int32 acc, ((float)acc * inv_q) * inv_d):
+ * no new floating-point rule, and every reported score is, bit for bit, the one pvs_sq8_topk_dev reports for that pair.
+ *   centroids   are code rows: cent_codes int8 [nlist][ld] and cent_inv float32 [nlist], 1 <= nlist <= 65536, made from float32
+ *               centroid rows by pvs_sq8_encode_dev.
+ *   list        of a database row: the first entry of the ranking of the row's codes against the centroid codes by (score
+ *               descending, list number ascending): pvs_sq8_topk_dev with k = 1.
+ *   probes      of a query: the first nprobe entries of the same ranking, 1 <= nprobe <= min(nlist, 1024).
+ *   storage     section 14's with m = ld: codes int8 [N][ld], inv float32 [N] and ids int32 [N] in (list, original index) order,
+ *               list_off int64 [nlist + 1] on the device with a host copy.  N < 2^31.  Empty lists are legal.
+ *   candidates  of a query: the concatenation of its probed lists in probe order, padded to W as pvs_ivf_scan_topk_dev computes W: the
+ *               sum of the nprobe longest lists, rounded up to 64, at least 64.  A live slot holds (score, original id), a padding
+ *               slot (-inf, -1).  A probe outside [0, nlist) counts as an empty list.  Distinct probes are a precondition.
+ *   result      the first k candidates by (score descending, original id ascending), -0 and +0 tied, 1 <= k <= 1024; slots beyond
+ *               the live candidates are idx = -1, val = -inf.
+ * With nprobe = nlist every row is a candidate exactly once and the two orders coincide: the lists equal those of pvs_sq8_topk_dev
+ * on the same rows byte for byte.  acc is an integer, so no slice size, wave assignment or summation order changes a bit. */
+/* d_qcodes int8 [nq][ld] and d_codes int8 [N][ld] are 16-byte aligned; d_probe int64 [nq][nprobe] as pvs_sq8_topk_dev gave it
+ * against the centroid codes.  h_list_off is a HOST copy of d_list_off: all sizing is done from it, so nothing inside the call waits
+ * for the device; the two must agree.  slice_rows: candidate slots per workgroup, a test seam: 0 lets the host choose (about two
+ * workgroups per compute unit over the query block, at least 64 slots each), any other value is rounded up to a multiple of 16; the
+ * result does not depend on it.  d_idx int64 [nq][k], d_val float32 [nq][k].  PVS_ERR_INVALID, before anything is launched: L
+ * outside 1..131072, nlist, nprobe or k out of range, negative nq or slice_rows, host offsets that do not start at 0 or that
+ * decrease, N >= 2^31, a missing or misaligned pointer.  nq == 0 is a no-op; N == 0 writes only (-1, -inf).  Enqueues on the
+ * context's stream and does not wait for it.  Timed on slots 2 (the scan) and 3 (the ranking). */
+int pvs_ivf_sq8_scan_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q, int64_t nq, int L, const int64_t* d_probe,
+                              int nprobe, const int64_t* d_list_off, const int64_t* h_list_off, int nlist, const int8_t* d_codes,
+                              const float* d_inv_db, const int32_t* d_ids, int k, int slice_rows, int64_t* d_idx, float* d_val);
+/* What the entry above will do for nq queries on this context's device, from the host offsets alone (no device work): h_plan int64
+ * [4] = W, the queries of one block, the slots per workgroup S (a multiple of 16), the workgroups per query ceil(W / S).  The same
+ * checks of nprobe, nlist, slice_rows and the offsets. */
+int pvs_ivf_sq8_scan_plan(pvs_ctx* ctx, int64_t nq, int nprobe, const int64_t* h_list_off, int nlist, int slice_rows, int64_t* h_plan);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

@@ -21,7 +21,6 @@ constexpr int IVF_RPL = 4;                     // candidate slots per lane and t
 constexpr int IVF_TILE = IVF_THREADS * IVF_RPL;
 constexpr int IVF_MAX_PROBE = 1024;
 constexpr int IVF_SEG_ENTRIES = 36864;         // table entries per LDS segment: 144 KiB (the probe tables below take 12 KiB more)
-constexpr int64_t IVF_CAND_BYTES = (int64_t)64 << 20;   // candidate rows of one query block (8 bytes per slot)
 constexpr int64_t IVF_MIN_SLICE = 1024;        // candidate slots a workgroup serves at least: a table copy is m * ksub * 4 bytes
 
 // ------------------------------------------------------------------------------------------------- probed scan
@@ -220,15 +219,9 @@ PVS_EXPORT int pvs_ivf_scan_topk_dev(pvs_ctx* ctx, const float* d_lut, int64_t n
   if (d_inv_db) PVS_ALIGNED(d_inv_db, 4, "inv_db");
   PVS_HIP(hipSetDevice(ctx->device));
 
-  // W: no query's candidate row is longer than the nprobe longest lists together
-  std::vector<int64_t> len(nlist);
-  for (int l = 0; l < nlist; ++l) len[l] = h_list_off[l + 1] - h_list_off[l];
-  std::nth_element(len.begin(), len.begin() + (nprobe - 1), len.end(), std::greater<int64_t>());
-  int64_t W = 0;
-  for (int j = 0; j < nprobe; ++j) W += len[j];
-  W = std::max<int64_t>(64, (W + 63) / 64 * 64);
+  const int64_t W = ivf_candidate_width(h_list_off, nlist, nprobe);   // list_common.hpp, shared with ivf_sq8.hip
   // G workgroups per query: enough for two per compute unit over the query block, each with at least IVF_MIN_SLICE slots
-  const int64_t QB = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 65535), IVF_CAND_BYTES / (8 * W)));
+  const int64_t QB = ivf_query_block(nq, W);
   const int64_t want = (2 * (int64_t)ctx->num_cu + QB - 1) / QB;
   const int64_t G0 = std::max<int64_t>(1, std::min<int64_t>(want, W / IVF_MIN_SLICE));
   const int64_t S = ((W + G0 - 1) / G0 + IVF_TILE - 1) / IVF_TILE * IVF_TILE;

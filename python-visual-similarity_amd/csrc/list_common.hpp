@@ -7,6 +7,7 @@
 //   offsets_first_break, query_offsets_first_break   host: where a host offset array breaks its rule
 //   sig_bits_ok, sig_align, word_count_ok    host: the signature widths and vocabulary sizes every entry point accepts
 //   score_slice, expand_tile_chunks, invert_tile, flat_grid   host: launch shapes
+//   ivf_candidate_width, ivf_query_block     host: the candidate rows of a probed scan (ivf.hip, ivf_sq8.hip)
 //   wave_incl_scan, block_incl_scan, block_excl_scan   one int per thread, wave totals through LDS; the exclusive form also returns the block total
 //   lower_bound_i32, last_le, shfl64         searches of a lane, a 64-bit shuffle
 //   load_sig, move_sig, hamming, store_sig_ballots   signatures
@@ -19,6 +20,8 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <functional>
+#include <vector>
 
 namespace pvs {
 
@@ -76,6 +79,24 @@ constexpr int AX_TILE_MIN_CHUNKS = 4;          // one chunk of 64 words per wave
 constexpr int AU_TILE_DEFAULT = 4096;          // entries of an invert tile
 constexpr int AU_TILE_MAX = 65536;
 constexpr int64_t AU_MAX_TILES = 65536;
+
+constexpr int64_t IVF_CAND_BYTES = (int64_t)64 << 20;   // candidate rows of one query block of a probed scan (8 bytes per slot)
+
+// W of a probed scan: no query's candidate row is longer than the nprobe longest lists together; rounded up to 64, at least 64.
+// h_list_off[0 .. nlist] has passed offsets_first_break; 1 <= nprobe <= nlist
+inline int64_t ivf_candidate_width(const int64_t* h_list_off, int nlist, int nprobe) {
+  std::vector<int64_t> len(nlist);
+  for (int l = 0; l < nlist; ++l) len[l] = h_list_off[l + 1] - h_list_off[l];
+  std::nth_element(len.begin(), len.begin() + (nprobe - 1), len.end(), std::greater<int64_t>());
+  int64_t W = 0;
+  for (int j = 0; j < nprobe; ++j) W += len[j];
+  return std::max<int64_t>(64, (W + 63) / 64 * 64);
+}
+
+// queries whose candidate rows of W slots share the workspace block: all of them up to grid.y, within IVF_CAND_BYTES, at least one
+inline int64_t ivf_query_block(int64_t nq, int64_t W) {
+  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 65535), IVF_CAND_BYTES / (8 * W)));
+}
 
 // images per workgroup of the score: slice_images, or (0) about two workgroups per compute unit over the query block and no slice
 // below ASMK_MIN_SLICE images

@@ -43,6 +43,7 @@ namespace pvs {
 //   WS_MATCH_TABLE    match.hip: upload_pairs, pvs_match_u8_dev
 //   WS_VERIFY_POINTS, WS_VERIFY_SMALL    match.hip: pvs_verify_dev
 //   WS_IVF_CANDIDATES ivf.hip: pvs_ivf_scan_topk_dev (candidate scores | candidate ids of one query block)
+//                     ivf_sq8.hip: pvs_ivf_sq8_scan_topk_dev (the same layout)
 //   WS_UPDATE         update.hip: pvs_keep_positions_dev (scan partials), pvs_compact_rows_dev in place (staging rows of one window),
 //                     pvs_ivf_insert_dev (source of every merged row), pvs_ivf_remove_dev (stored keep mask | positions | scan partials);
 //                     asmk_update.hip: pvs_asmk_invert_dev (two item arrays | digit counts | scan partials), pvs_asmk_remove_dev
@@ -153,7 +154,7 @@ inline SiftCandLayout<Cand, Kp> sift_cand_layout(size_t n_cand, size_t max_peaks
           l.add<float>(n_cand * max_peaks), l.bytes()};
 }
 
-// pvs_ivf_scan_topk_dev, WS_IVF_CANDIDATES: one query block's candidate rows, QB queries x W slots each
+// pvs_ivf_scan_topk_dev and pvs_ivf_sq8_scan_topk_dev, WS_IVF_CANDIDATES: one query block's candidate rows, QB queries x W slots each
 struct IvfCandLayout {
   WsPiece<float> val;
   WsPiece<int32_t> id;

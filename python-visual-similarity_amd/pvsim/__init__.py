@@ -7,6 +7,7 @@
     from pvsim import CompactIndex, ProductQuantizer   # product-quantised index, ADC search (m + 4 bytes per image)
     from pvsim import IVFCompactIndex                  # the same cut into inverted lists: a query scans nprobe of nlist lists
     from pvsim import Int8Index                        # one signed byte per dimension: a quarter of a DeviceIndex, near-exact lists
+    from pvsim import IVFInt8Index                     # the same rows cut into inverted lists: the int8 score over nprobe of nlist lists
     from pvsim import QueryExpansion             # query expansion / database-side augmentation on a DeviceIndex
     from pvsim import Diffusion                        # diffusion re-ranking on the kNN graph of a DeviceIndex
     from pvsim import KReciprocal                      # k-reciprocal re-ranking on the kNN lists of a DeviceIndex
@@ -24,6 +25,7 @@ from . import models
 from ._errors import CapacityError
 from .compact import CompactIndex, IVFCompactIndex, ProductQuantizer
 from .quantized import Int8Index
+from .ivf_int8 import IVFInt8Index
 from .expand import QueryExpansion
 from .diffusion import Diffusion
 from .reciprocal import KReciprocal
@@ -33,5 +35,5 @@ from .subset import Subset
 
 __version__ = "0.1.0"
 __all__ = ["encoders", "features", "eval", "verify", "models", "Context", "default_context", "pack_descriptors", "CapacityError",
-           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "Int8Index", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion",
+           "CompactIndex", "IVFCompactIndex", "ProductQuantizer", "Int8Index", "IVFInt8Index", "QueryExpansion", "Diffusion", "KReciprocal", "ASMKIndex", "ASMKExpansion",
            "DuplicateGroups", "find_duplicates", "Subset"]

@@ -185,6 +185,8 @@ SIGNATURES = {
     "pvs_subset_destroy": [_vp, _vp],
     "pvs_cosine_topk_subset_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _int, _int, _int, _vp, _vp, _vp],
     "pvs_sq8_topk_subset_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _int, _int, _int, _vp, _vp, _vp],
+    "pvs_ivf_sq8_scan_topk_dev": [_vp, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp],
+    "pvs_ivf_sq8_scan_plan": [_vp, _i64, _int, _vp, _int, _int, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],

@@ -567,6 +567,27 @@ class Context:
                                                ptr(d_list_off), ptr(h), nlist, ptr(d_codes), ptr(d_ids), ptr(d_invq), ptr(d_invdb), k,
                                                ptr(d_idx), ptr(d_val)))
 
+    # inverted lists over the int8 code rows
+    def ivf_sq8_scan_topk_dev(self, d_qcodes, d_invq, nq, L, d_probe, nprobe, d_list_off, h_list_off, nlist, d_codes, d_invdb, d_ids, k,
+                              d_idx, d_val, slice_rows=0):
+        """pvs_ivf_sq8_scan_topk_dev; h_list_off: the host copy of the list offsets, a C-contiguous int64 array of nlist + 1 entries;
+        slice_rows: candidate slots per workgroup (0: the host's rule), a test seam that never changes the result"""
+        h = np.ascontiguousarray(h_list_off, dtype=np.int64)
+        if h.shape != (nlist + 1,):
+            raise ValueError(f"h_list_off must have nlist + 1 = {nlist + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_ivf_sq8_scan_topk_dev(self.handle, ptr(d_qcodes), ptr(d_invq), int(nq), int(L), ptr(d_probe), int(nprobe),
+                                                   ptr(d_list_off), ptr(h), int(nlist), ptr(d_codes), ptr(d_invdb), ptr(d_ids), int(k),
+                                                   int(slice_rows), ptr(d_idx), ptr(d_val)))
+
+    def ivf_sq8_scan_plan(self, nq, nprobe, h_list_off, nlist, slice_rows=0) -> dict:
+        """pvs_ivf_sq8_scan_plan -> dict(W, query_block, slice_rows, slices): how the scan above is cut, from the host offsets alone"""
+        h = np.ascontiguousarray(h_list_off, dtype=np.int64)
+        if h.shape != (nlist + 1,):
+            raise ValueError(f"h_list_off must have nlist + 1 = {nlist + 1} entries, got shape {h.shape}")
+        out = (C.c_int64 * 4)()
+        check(_ffi.lib().pvs_ivf_sq8_scan_plan(self.handle, int(nq), int(nprobe), ptr(h), int(nlist), int(slice_rows), out))
+        return {"W": int(out[0]), "query_block": int(out[1]), "slice_rows": int(out[2]), "slices": int(out[3])}
+
     # query expansion / database-side augmentation (DESIGN.md section 13)
     COMBINE_CHUNK_BYTES, COMBINE_BATCH = _ffi.COMBINE_CHUNK_BYTES, _ffi.COMBINE_BATCH
 

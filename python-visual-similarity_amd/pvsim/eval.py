@@ -94,14 +94,39 @@ def _no_full_subset_ranking():
     raise ValueError("allowed= together with k=None is not built: a subset ranking is a finite list, pass k")
 
 
+def _plan_ivf_int8(dataset, expand, rerank, nprobe, diffuse, reciprocal, allowed) -> _Plan:
+    """An IVFInt8Index ranks one way, the int8 score over the nprobe best lists of a query: nprobe= is required, k is finite, and
+    every other option is refused by name."""
+    for name, given, needs in (("allowed", allowed is not None, "subset search covers a dict, a float32 DeviceIndex and an Int8Index"),
+                               ("expand", expand is not None, "query expansion needs the full-precision rows of a dict or a DeviceIndex"),
+                               ("rerank", bool(rerank), "a second stage needs the kept projected rows of a CompactIndex"),
+                               ("diffuse", diffuse is not None, "diffusion runs on the DeviceIndex the graph was built on"),
+                               ("reciprocal", reciprocal is not None, "k-reciprocal re-ranking runs on the DeviceIndex the lists were built on")):
+        if given:
+            raise ValueError(f"{name}= on an IVFInt8Index is not built: {needs}")
+    if nprobe is None:
+        raise ValueError("an IVFInt8Index scans the nprobe best lists of a query: pass nprobe=")
+    n = len(dataset)
+
+    def rank(q, k):
+        if k is None:
+            raise ValueError("k=None on an IVFInt8Index is not built: it ranks a finite list over the probed lists, pass k (the complete "
+                             "ranking needs the full-precision rows -- use a dict or a DeviceIndex for that)")
+        return _clamped(lambda q, kk: dataset.rank(q, kk, nprobe), n, q, k)
+    return _Plan(n, dataset._ledger.paths, rank, index_of=dataset._ledger.index_of)
+
+
 def _plan(dataset, expand=None, rerank: int = 0, nprobe=None, diffuse=None, ctx=None, reciprocal=None, allowed=None) -> _Plan:
-    """What `dataset` is (a dict, a DeviceIndex, an Int8Index, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
+    """What `dataset` is (a dict, a DeviceIndex, an Int8Index, an IVFInt8Index, a CompactIndex, an IVFCompactIndex), whether it takes these options (every
     refusal is raised here, before anything is encoded), and how it ranks.  A DeviceIndex is never asked for its host rows.
     `allowed`: one set of images for all queries (a pvsim.Subset of the index, indices, a boolean mask or paths); k is then clamped to
     the size of the set.  A dict is cut to the allowed paths here, on the host, and ranked as any dict."""
     from .compact import CompactIndex, IVFCompactIndex
     from .index import DeviceIndex
+    from .ivf_int8 import IVFInt8Index
     from .quantized import Int8Index
+    if isinstance(dataset, IVFInt8Index):
+        return _plan_ivf_int8(dataset, expand, rerank, nprobe, diffuse, reciprocal, allowed)
     if allowed is not None:
         _check_allowed(dataset, expand, rerank, nprobe, diffuse, reciprocal)
     dense, compact = isinstance(dataset, DeviceIndex), isinstance(dataset, CompactIndex)
