@@ -74,7 +74,11 @@ typedef enum {
                                 /* Same bytes: the windows move the rows, they compute nothing.                                          */
   PVS_OPT_SQ8_PATH = 7,         /* pvs_sq8_topk_dev: 0 (default) the row scan for up to 4 queries, the int8 GEMM beyond; 1: always the row   */
                                 /* scan; 2: always the GEMM.  Same bits: the dot product of two code rows is an integer.                  */
-  PVS_OPT_COUNT_ = 8
+  PVS_OPT_GEMM_SLOTS = 8,       /* workgroup slots the similarity GEMMs plan their launches for: 0 (default) what the chip has (CUs x       */
+                                /* workgroups per CU); v in 1..4096: plan as if it had v, so that a test reaches every launch plan (whole   */
+                                /* tiles, full rounds + split-K tail, every tile split, the 256 x 128 two-level kernel) with a few tiles.   */
+                                /* It moves the cut of the tile list into launches, never the arithmetic of a score.                      */
+  PVS_OPT_COUNT_ = 9
 } pvs_option;
 
 typedef struct pvs_ctx pvs_ctx;

@@ -235,3 +235,96 @@ EXPORT int orc_assign_chain(const float* X, int64_t n, const float* C, int K, in
   free(cn);
   return 0;
 }
+
+/* orc_cosine_chain for every pair: out[m * ldo + n], M x N, the same recurrence per element (tests compare whole matrices
+ * with it, not samples). */
+EXPORT int orc_cosine_chain_full(const float* A, int64_t M, const float* B, int64_t N, int64_t L, const float* inva,
+                                 const float* invb, float* out, int64_t ldo) {
+#pragma omp parallel for schedule(static)
+  for (int64_t m = 0; m < M; ++m) {
+    const float* a = A + (size_t)m * L;
+    for (int64_t n = 0; n < N; ++n) {
+      const float* b = B + (size_t)n * L;
+      float tot = 0.f;
+      for (int64_t c0 = 0; c0 < L; c0 += 1024) {
+        float acc = 0.f;
+        const int64_t c1 = c0 + 1024 < L ? c0 + 1024 : L;
+        for (int64_t b8 = c0; b8 < c1; b8 += 8)
+          for (int e = 0; e < 4; ++e) {
+            const int64_t k1 = b8 + e, k2 = b8 + 4 + e;
+            if (k1 < L) acc = fmaf(a[k1], b[k1], acc);
+            if (k2 < L) acc = fmaf(a[k2], b[k2], acc);
+          }
+        tot += acc;
+      }
+      const float sa = inva ? inva[m] : 1.f, sb = invb ? invb[n] : 1.f;
+      out[(size_t)m * ldo + n] = (0.f + tot) * (sa * sb);
+    }
+  }
+  return 0;
+}
+
+/* The generic tile kernel's score (any length, any alignment) as its definition: one fused multiply-add per k in ascending
+ * k, then acc * (inva[m] * invb[n]) with a null factor counting as 1.  fmaf / fma: one rounding per step. */
+EXPORT int orc_cosine_seq_f32(const float* A, int64_t M, const float* B, int64_t N, int64_t L, const float* inva,
+                              const float* invb, float* out, int64_t ldo) {
+#pragma omp parallel for schedule(static)
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t n = 0; n < N; ++n) {
+      const float *a = A + (size_t)m * L, *b = B + (size_t)n * L;
+      float acc = 0.f;
+      for (int64_t k = 0; k < L; ++k) acc = fmaf(a[k], b[k], acc);
+      out[(size_t)m * ldo + n] = acc * ((inva ? inva[m] : 1.f) * (invb ? invb[n] : 1.f));
+    }
+  return 0;
+}
+EXPORT int orc_cosine_seq_f64(const double* A, int64_t M, const double* B, int64_t N, int64_t L, const double* inva,
+                              const double* invb, double* out, int64_t ldo) {
+#pragma omp parallel for schedule(static)
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t n = 0; n < N; ++n) {
+      const double *a = A + (size_t)m * L, *b = B + (size_t)n * L;
+      double acc = 0.0;
+      for (int64_t k = 0; k < L; ++k) acc = fma(a[k], b[k], acc);
+      out[(size_t)m * ldo + n] = acc * ((inva ? inva[m] : 1.0) * (invb ? invb[n] : 1.0));
+    }
+  return 0;
+}
+
+/* High-precision reference for the GEMM paths without a bit definition: dot[m][n] = sum_k a_k b_k and
+ * mag[m][n] = sum_k |a_k b_k| in long double, ascending k (64-bit significand: a product of two floats is exact in it, a product
+ * of two doubles is rounded to 2^-64 relative).  mag is the per-element error scale of any summation order. */
+EXPORT int orc_dot_abs_ld_f32(const float* A, int64_t M, const float* B, int64_t N, int64_t L, long double* dot,
+                              long double* mag) {
+#pragma omp parallel for schedule(static)
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t n = 0; n < N; ++n) {
+      const float *a = A + (size_t)m * L, *b = B + (size_t)n * L;
+      long double s = 0.0L, t = 0.0L;
+      for (int64_t k = 0; k < L; ++k) {
+        const long double p = (long double)a[k] * (long double)b[k];
+        s += p;
+        t += fabsl(p);
+      }
+      dot[(size_t)m * N + n] = s;
+      mag[(size_t)m * N + n] = t;
+    }
+  return 0;
+}
+EXPORT int orc_dot_abs_ld_f64(const double* A, int64_t M, const double* B, int64_t N, int64_t L, long double* dot,
+                              long double* mag) {
+#pragma omp parallel for schedule(static)
+  for (int64_t m = 0; m < M; ++m)
+    for (int64_t n = 0; n < N; ++n) {
+      const double *a = A + (size_t)m * L, *b = B + (size_t)n * L;
+      long double s = 0.0L, t = 0.0L;
+      for (int64_t k = 0; k < L; ++k) {
+        const long double p = (long double)a[k] * (long double)b[k];
+        s += p;
+        t += fabsl(p);
+      }
+      dot[(size_t)m * N + n] = s;
+      mag[(size_t)m * N + n] = t;
+    }
+  return 0;
+}

@@ -24,6 +24,9 @@ def lib():
                                    C.c_void_p, C.c_int]
         l.orc_assign_chain.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         l.orc_cosine_chain.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        gemm = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        l.orc_cosine_chain_full.argtypes = l.orc_cosine_seq_f32.argtypes = l.orc_cosine_seq_f64.argtypes = gemm
+        l.orc_dot_abs_ld_f32.argtypes = l.orc_dot_abs_ld_f64.argtypes = gemm[:5] + [C.c_void_p, C.c_void_p]
         _lib = l
     return _lib
 
@@ -82,3 +85,49 @@ def assign_chain(x, centroids):
     if lib().orc_assign_chain(x.ctypes.data, x.shape[0], c.ctypes.data, c.shape[0], c.shape[1], labels.ctypes.data):
         raise MemoryError("oracle allocation failed")
     return labels
+
+
+def _opt(v, dt):
+    return None if v is None else np.ascontiguousarray(v, dtype=dt)
+
+
+def _p(v):
+    return None if v is None else v.ctypes.data
+
+
+def cosine_chain_full(a, b, inv_a, inv_b):
+    """cosine_chain for every pair of rows: the (M, N) float32 matrix of the exact GEMM's defined recurrence."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = np.ascontiguousarray(b, dtype=np.float32)
+    ia, ib = _opt(inv_a, np.float32), _opt(inv_b, np.float32)
+    out = np.empty((a.shape[0], b.shape[0]), dtype=np.float32)
+    lib().orc_cosine_chain_full(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], a.shape[1], _p(ia), _p(ib), out.ctypes.data, b.shape[0])
+    return out
+
+
+def cosine_seq(a, b, inv_a, inv_b):
+    """The generic tile kernel's definition: one fma per k in ascending k, then acc * (inv_a[m] * inv_b[n]); float32 when
+    `a` is float32, float64 otherwise."""
+    dt = np.float32 if np.asarray(a).dtype == np.float32 else np.float64
+    a = np.ascontiguousarray(a, dtype=dt)
+    b = np.ascontiguousarray(b, dtype=dt)
+    ia, ib = _opt(inv_a, dt), _opt(inv_b, dt)
+    out = np.empty((a.shape[0], b.shape[0]), dtype=dt)
+    fn = lib().orc_cosine_seq_f32 if dt == np.float32 else lib().orc_cosine_seq_f64
+    fn(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], a.shape[1], _p(ia), _p(ib), out.ctypes.data, b.shape[0])
+    return out
+
+
+def dot_abs_ld(a, b):
+    """(sum_k a_k b_k, sum_k |a_k b_k|) for every pair of rows in long double -> two (M, N) np.longdouble arrays.  Operands
+    are float32 (fp16 values included: they convert exactly) or float64."""
+    if np.dtype(np.longdouble).itemsize != 16 or np.finfo(np.longdouble).nmant < 63:
+        raise RuntimeError("np.longdouble is not the C long double of the oracle build (x87 extended expected)")
+    dt = np.float32 if np.asarray(a).dtype == np.float32 else np.float64
+    a = np.ascontiguousarray(a, dtype=dt)
+    b = np.ascontiguousarray(b, dtype=dt)
+    dot = np.empty((a.shape[0], b.shape[0]), dtype=np.longdouble)
+    mag = np.empty_like(dot)
+    fn = lib().orc_dot_abs_ld_f32 if dt == np.float32 else lib().orc_dot_abs_ld_f64
+    fn(a.ctypes.data, a.shape[0], b.ctypes.data, b.shape[0], a.shape[1], dot.ctypes.data, mag.ctypes.data)
+    return dot, mag

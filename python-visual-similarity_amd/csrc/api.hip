@@ -220,7 +220,7 @@ PVS_EXPORT int pvs_device_name(pvs_ctx* ctx, char* buf, size_t buflen) {
 PVS_EXPORT int pvs_set_option(pvs_ctx* ctx, int option, int value) {
   PVS_NEED(ctx, "ctx");
   if (option < 0 || option >= PVS_OPT_COUNT_) PVS_FAIL(PVS_ERR_INVALID, "unknown option %d", option);
-  const int hi = option == PVS_OPT_UPDATE_WINDOW_ROWS ? (1 << 20) : option == PVS_OPT_TRAIN_BATCH_CHUNKS ? 1024 : option == PVS_OPT_ASSIGN_PREFILTER ? 4 : (option == PVS_OPT_VLAD_PATH || option == PVS_OPT_TOPK_SELECT_ONLY) ? 3 : ((option == PVS_OPT_AGG_VARIANT || option == PVS_OPT_FISHER_SCALE || option == PVS_OPT_SQ8_PATH) ? 2 : 1);
+  const int hi = option == PVS_OPT_GEMM_SLOTS ? 4096 : option == PVS_OPT_UPDATE_WINDOW_ROWS ? (1 << 20) : option == PVS_OPT_TRAIN_BATCH_CHUNKS ? 1024 : option == PVS_OPT_ASSIGN_PREFILTER ? 4 : (option == PVS_OPT_VLAD_PATH || option == PVS_OPT_TOPK_SELECT_ONLY) ? 3 : ((option == PVS_OPT_AGG_VARIANT || option == PVS_OPT_FISHER_SCALE || option == PVS_OPT_SQ8_PATH) ? 2 : 1);
   if (value < 0 || value > hi) PVS_FAIL(PVS_ERR_INVALID, "option %d: value %d out of range 0..%d", option, value, hi);
   ctx->opt[option] = value;
   return PVS_OK;
@@ -1250,6 +1250,13 @@ PVS_EXPORT int pvs_fused_profile(pvs_ctx* ctx, int enable, int64_t* out16) {
     PVS_HIP(hipFree(ctx->d_fused_stamps));
     ctx->d_fused_stamps = nullptr;
   }
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_gemm_last_plan(pvs_ctx* ctx, int32_t out12[12]) {
+  PVS_NEED(ctx, "ctx");
+  PVS_NEED(out12, "out12");
+  for (int i = 0; i < 12; ++i) out12[i] = ctx->gemm_last[i];
   return PVS_OK;
 }
 

@@ -69,49 +69,24 @@ template <> struct GemmModel<2> { using Cfg = GemmPre; static constexpr bool F16
 
 using GemmPlan = pvs_ctx::GemmPlanSlot;   // lives in the context (one device, one stream): never shared between contexts
 
+// PVS_OPT_GEMM_SLOTS: the workgroup slots every plan is cut for; 0 = what the chip has (`natural`)
+static int gemm_slots(const pvs_ctx* ctx, int natural) {
+  const int v = ctx->opt[PVS_OPT_GEMM_SLOTS];
+  return v > 0 ? v : natural;
+}
+
+// The rule is gemm_plan.hpp (tile order, cut into launches); here: the per-model cache and the upload of the list.
 static int build_plan(pvs_ctx* ctx, int which, int tiles_m, int tiles_n, bool symm, int slots, GemmPlan** out) {
   GemmPlan& P = ctx->gemm_plan[which];
+  slots = gemm_slots(ctx, slots);
   const int key[4] = {tiles_m, tiles_n, symm ? 1 : 0, slots};
   if (memcmp(P.key, key, sizeof(key)) != 0) {
     std::vector<GemmTile> t;
-    if (symm) {
-      const int TS = (tiles_m + 7) / 8;
-      for (int si = 0; si < TS; ++si)
-        for (int sj = si; sj < TS; ++sj)
-          for (int w = 0; w < 64; ++w) {
-            const int tm = si * 8 + (w & 7), tn = sj * 8 + (w >> 3);
-            if (tm < tiles_m && tn < tiles_m && tn >= tm) t.push_back({tm, tn});
-          }
-    } else {
-      for (int g0 = 0; g0 < tiles_m; g0 += 8) {
-        const int gsz = std::min(8, tiles_m - g0);
-        for (int tn = 0; tn < tiles_n; ++tn)
-          for (int dm = 0; dm < gsz; ++dm) t.push_back({g0 + dm, tn});
-      }
-    }
-    const int total = (int)t.size();
-    // How to cut the work into launches.  One tile takes the same time T whether the chip is full or not, so a problem of
-    // few tiles (a rank's share in the multi-GPU scheme, a query batch) is fast only when its tiles are split along K into
-    // s slices (whole 1024-k chains each; the reduce adds the chain images in chain order, so the scores do not change).
-    // Cost in units of T:  rounds(blocks) * (1/s + eps) + the reduce's traffic;  candidates: full rounds unsplit + the last
-    // partial round split (A), or every tile split (B).
-    const double eps = 0.02, red = 3.0e-4;
-    auto rounds = [&](long blocks) { return (double)((blocks + slots - 1) / slots); };
-    const int full = total / slots, rem = total % slots;
-    double best = rounds(total);            // nothing split
-    P.n_main = total;
-    P.n_tail = 0;
-    P.splitk = 1;
-    for (int sk = 2; sk <= 32; sk *= 2) {
-      if (rem > 0) {
-        const double a = full + rounds((long)rem * sk) * (1.0 / sk + eps) + red * rem;
-        if (a < best - 1e-9) { best = a; P.n_main = total - rem; P.n_tail = rem; P.splitk = sk; }
-      }
-      if (total < 4 * slots) {
-        const double b = rounds((long)total * sk) * (1.0 / sk + eps) + red * total;
-        if (b < best - 1e-9) { best = b; P.n_main = 0; P.n_tail = total; P.splitk = sk; }
-      }
-    }
+    gemm_plan_tiles(tiles_m, tiles_n, symm, t);
+    const GemmCut cut = gemm_plan_cut((int)t.size(), slots);
+    P.n_main = cut.n_main;
+    P.n_tail = cut.n_tail;
+    P.splitk = cut.splitk;
     if (P.cap < t.size()) {
       PVS_HIP(hipStreamSynchronize(ctx->stream));
       if (P.d_tiles) PVS_HIP(hipFree(P.d_tiles));
@@ -130,6 +105,18 @@ static int build_plan(pvs_ctx* ctx, int which, int tiles_m, int tiles_n, bool sy
   return PVS_OK;
 }
 
+// What pvs_gemm_last_plan (include/pvsim_diag.h) reports: written by the host where the launches are made, read by tests.
+enum { GL_MODEL, GL_TILES_M, GL_TILES_N, GL_SYMM, GL_DUAL, GL_N_MAIN, GL_N_TAIL, GL_SPLIT, GL_NPARTS, GL_TAIL_UNSPLIT, GL_MAIN_8PH,
+       GL_ACCUMULATE };
+static int32_t* note_plan(pvs_ctx* ctx, int model, int tiles_m, int tiles_n, bool symm, bool dual, int n_main, int n_tail,
+                          int accumulate) {
+  int32_t* r = ctx->gemm_last;
+  for (int i = 0; i < 12; ++i) r[i] = 0;
+  r[GL_MODEL] = model; r[GL_TILES_M] = tiles_m; r[GL_TILES_N] = tiles_n; r[GL_SYMM] = symm; r[GL_DUAL] = dual;
+  r[GL_N_MAIN] = n_main; r[GL_N_TAIL] = n_tail; r[GL_SPLIT] = 1; r[GL_ACCUMULATE] = accumulate != 0;
+  return r;
+}
+
 template <bool SYMM, int MODEL, bool DUAL = false>
 static int launch_gemm_mfma(pvs_ctx* ctx, GemmArgs g, const GemmPlan& plan) {
   using GM = GemmModel<MODEL>;
@@ -145,8 +132,11 @@ static int launch_gemm_mfma(pvs_ctx* ctx, GemmArgs g, const GemmPlan& plan) {
   for (const void* k : {reinterpret_cast<const void*>(kfull), reinterpret_cast<const void*>(kpart),
                         reinterpret_cast<const void*>(kred)})
     PVS_TRY(ensure_lds(ctx, k, Cfg::LDS_BYTES));
+  static_assert(PVS_GEMM_MODEL_EXACT_F32 == 0 && PVS_GEMM_MODEL_F16_256 == 1 && PVS_GEMM_MODEL_F16_BOUNDED == 2, "MODEL is reported as is");
+  int32_t* note = note_plan(ctx, MODEL, plan.key[0], plan.key[1], SYMM, DUAL, plan.n_main, plan.n_tail, g.accumulate);
   if (plan.n_main > 0) {
     g.tile_base = 0;
+    note[GL_MAIN_8PH] = MODEL == 1;
     if constexpr (MODEL == 1) {
       // fp16 256 x 256: the full rounds run on the 8-phase schedule with v_mfma_f32_16x16x32_f16 (gemm_f16_8ph.hpp; measured
       // 1.45 PFLOP/s against 1.12-1.19 for the two-stage kernel, profiles/r03_fp16_gemm_8phase_control_*.txt); the split-K
@@ -164,7 +154,9 @@ static int launch_gemm_mfma(pvs_ctx* ctx, GemmArgs g, const GemmPlan& plan) {
     const int nk = (int)((g.L + bk - 1) / bk);
     const int nparts = TWO ? (nk + GEMM_KBLOCK / bk - 1) / (GEMM_KBLOCK / bk) : plan.splitk;
     const size_t bytes = (size_t)plan.n_tail * nparts * BM * BM * sizeof(float);
+    note[GL_NPARTS] = nparts;
     if (bytes > ((size_t)1 << 30)) {
+      note[GL_TAIL_UNSPLIT] = PVS_GEMM_TAIL_UNSPLIT_BYTES;
       // very long rows (e.g. Fisher vectors): the chain images would not fit a sane workspace -> unsplit launch
       g.tile_base = plan.n_main;
       hipLaunchKernelGGL(kfull, dim3((unsigned)plan.n_tail), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
@@ -174,6 +166,7 @@ static int launch_gemm_mfma(pvs_ctx* ctx, GemmArgs g, const GemmPlan& plan) {
       g.tile_base = plan.n_main;
       g.splitk = std::min(plan.splitk, nparts);
       g.nparts = nparts;
+      note[GL_SPLIT] = g.splitk;
       g.partial = part;
       hipLaunchKernelGGL(kpart, dim3((unsigned)(plan.n_tail * g.splitk)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
       hipLaunchKernelGGL(kred, dim3((unsigned)plan.n_tail), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
@@ -199,9 +192,10 @@ static int cosine_mfma(pvs_ctx* ctx, const void* A, int64_t M, const void* B, in
     // panel): gemm_f16_2lvl.hpp, 1.13 against 0.93 PFLOP/s (profiles/r03_fp16_gemm_two_level_256x128.txt); whole tiles only, so
     // small problems and the symmetric case keep the 128 x 128 kernel with its split-K tail
     const int t256 = (int)((M + 255) / 256), t128 = (int)((N + 127) / 128);
-    if (!symm && out_t == nullptr && (int64_t)t256 * t128 >= (int64_t)4 * ctx->num_cu && (int64_t)t256 * t128 <= 0x3fffffffLL &&
+    if (!symm && out_t == nullptr && (int64_t)t256 * t128 >= (int64_t)4 * gemm_slots(ctx, ctx->num_cu) && (int64_t)t256 * t128 <= 0x3fffffffLL &&
         L <= (int64_t)8 * 1024 * 1024) {
       PVS_TRY(build_plan(ctx, 4, t256, t128, false, ctx->num_cu, &plan));
+      note_plan(ctx, PVS_GEMM_MODEL_F16_2LVL, t256, t128, false, false, plan->n_main + plan->n_tail, 0, accumulate);   // one launch of whole tiles
       GemmArgs g{};
       g.A = A; g.B = B; g.M = M; g.N = N; g.L = L; g.lda = ld ? ld : L; g.ldb = ld ? ld : L; g.inva = inva; g.invb = invb;
       g.accumulate = accumulate;
@@ -353,6 +347,7 @@ int launch_cosine_f32(pvs_ctx* ctx, const float* A, int64_t M, const float* B, i
     PVS_TRY(cosine_mfma<0>(ctx, A, M, B, N, L, inva, invb, out, ldo));
   } else {
     dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
+    note_plan(ctx, PVS_GEMM_MODEL_GENERIC, (int)grid.y, (int)grid.x, false, false, (int)(grid.x * grid.y), 0, 0);
     hipLaunchKernelGGL(cosine_gemm_generic_kernel<float>, grid, dim3(256), 0, ctx->stream, A, M, B, N, L, inva, invb,
                        out, ldo);
   }
@@ -388,6 +383,7 @@ static int launch_gemm_f64(pvs_ctx* ctx, GemmArgsF64 g, const GemmPlan& plan) {
   auto kred = gemm_f64_kernel<SYMM, GEMM_MODE_REDUCE>;
   for (const void* k : {reinterpret_cast<const void*>(kfull), reinterpret_cast<const void*>(kpart), reinterpret_cast<const void*>(kred)})
     PVS_TRY(ensure_lds(ctx, k, Cfg::LDS_BYTES));
+  int32_t* note = note_plan(ctx, PVS_GEMM_MODEL_F64, plan.key[0], plan.key[1], SYMM, false, plan.n_main, plan.n_tail, 0);
   if (plan.n_main > 0) {
     g.tile_base = 0;
     hipLaunchKernelGGL(kfull, dim3((unsigned)plan.n_main), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
@@ -397,13 +393,16 @@ static int launch_gemm_f64(pvs_ctx* ctx, GemmArgsF64 g, const GemmPlan& plan) {
     const int sk = std::max(1, std::min(plan.splitk, nk));
     const size_t bytes = (size_t)plan.n_tail * sk * Cfg::PART_ELEMS * sizeof(double);
     g.tile_base = plan.n_main;
+    note[GL_NPARTS] = sk;
     if (sk == 1 || bytes > ((size_t)1 << 30)) {
+      note[GL_TAIL_UNSPLIT] = sk == 1 ? PVS_GEMM_TAIL_UNSPLIT_ONE_SLICE : PVS_GEMM_TAIL_UNSPLIT_BYTES;
       hipLaunchKernelGGL(kfull, dim3((unsigned)plan.n_tail), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
     } else {
       double* part = nullptr;
       PVS_TRY(ws_reserve(ctx, WS_AUX_ROWS, bytes, &part));
       g.splitk = sk;
       g.nparts = sk;
+      note[GL_SPLIT] = sk;
       g.partial = part;
       hipLaunchKernelGGL(kpart, dim3((unsigned)(plan.n_tail * sk)), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
       hipLaunchKernelGGL(kred, dim3((unsigned)plan.n_tail), dim3(Cfg::THREADS), Cfg::LDS_BYTES, ctx->stream, g);
@@ -424,6 +423,7 @@ int launch_cosine_f64_dev(pvs_ctx* ctx, const double* A, int64_t M, const double
   ScopedTimer tm(ctx, T_GEMM);
   if (!fast) {
     dim3 grid((unsigned)((N + 63) / 64), (unsigned)((M + 63) / 64));
+    note_plan(ctx, PVS_GEMM_MODEL_GENERIC, (int)grid.y, (int)grid.x, false, false, (int)(grid.x * grid.y), 0, 0);
     hipLaunchKernelGGL(cosine_gemm_generic_kernel<double>, grid, dim3(256), 0, ctx->stream, A, M, B, N, L, inva, invb, out, ldo);
     PVS_HIP(hipGetLastError());
     return PVS_OK;

@@ -37,14 +37,12 @@
 
 #include <cstdint>
 
+#include "gemm_plan.hpp"   // GemmTile and the host rule that lists the tiles
+
 namespace pvs {
 
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-struct GemmTile {
-  int tm, tn;
-};
 
 struct GemmArgs {
   const void* A;     // fp32 or fp16 rows

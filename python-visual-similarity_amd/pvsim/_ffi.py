@@ -28,6 +28,11 @@ PIX_U8_RGB, PIX_U8_GRAY, PIX_F32_RGB, PIX_F32_GRAY = 0, 1, 2, 3          # pvs_p
 DSIFT_U8, DSIFT_F32, DSIFT_F32_RAW, DSIFT_F32_QUANT = 0, 1, 2, 3                         # pvs_dsift_out
 OPT_UPDATE_WINDOW_ROWS = 6        # 0: windows of the in-place row compaction from the staging byte budget; 1..2^20: at most that many rows
 OPT_SQ8_PATH = 7                  # pvs_sq8_topk_dev: 0 chooses by the number of queries, 1 the row scan, 2 the int8 GEMM; same bits
+OPT_GEMM_SLOTS = 8                # 0: the similarity GEMMs plan for the chip's workgroup slots; 1..4096: for that many (tests pin every launch plan)
+GEMM_EXACT_F32, GEMM_F16_256, GEMM_F16_BOUNDED, GEMM_F64, GEMM_F16_2LVL, GEMM_GENERIC = range(6)      # pvs_gemm_model (include/pvsim_diag.h)
+GEMM_TAIL_UNSPLIT_BYTES, GEMM_TAIL_UNSPLIT_ONE_SLICE = 1, 2                                           # pvs_gemm_tail_unsplit
+GEMM_PLAN_FIELDS = ("model", "tiles_m", "tiles_n", "symm", "dual", "n_main", "n_tail", "split", "nparts", "tail_unsplit",
+                    "main_8ph", "accumulate")
 SQ8_PATH_AUTO, SQ8_PATH_ROWS, SQ8_PATH_MATRIX = 0, 1, 2
 SQ8_MAX_L = 131072                # 127^2 * L < 2^31
 RANGE_UPPER = 1                   # PVS_RANGE_UPPER: the self-join, pairs j > i only
@@ -188,6 +193,7 @@ SIGNATURES = {
     "pvs_ivf_sq8_scan_topk_dev": [_vp, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp],
     "pvs_ivf_sq8_scan_plan": [_vp, _i64, _int, _vp, _int, _int, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
+    "pvs_gemm_last_plan": [_vp, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],
     "pvs_timers_read": [_vp, _int, C.POINTER(C.c_double), C.POINTER(C.c_int64)],

@@ -269,6 +269,13 @@ class Context:
 
         return _Scoped()
 
+    def gemm_last_plan(self) -> dict:
+        """pvs_gemm_last_plan (diagnostic): the launches of this context's last similarity GEMM, by the names of
+        _ffi.GEMM_PLAN_FIELDS; every value is -1 before the first one."""
+        out = (C.c_int32 * 12)()
+        check(_ffi.lib().pvs_gemm_last_plan(self.handle, out))
+        return dict(zip(_ffi.GEMM_PLAN_FIELDS, (int(v) for v in out)))
+
     def fill_dev(self, d_ptr: int, n_elems: int, dtype: str, value) -> None:
         """4- or 8-byte pattern fill on this context's stream (dtype: float32 / int32 / int64 / float64)."""
         a = np.array([value], dtype=dtype)

@@ -42,8 +42,9 @@ def test_f64_cosine_dev_against_numpy(gpu_ctx, M, N, L):
 @pytest.mark.parametrize("N,L", [(300, 4098), (1000, 130), (2949, 64), (8189, 34)])
 def test_f64_self_similarity_is_bitwise_symmetric(gpu_ctx, N, L):
     """A == B: only the upper triangle of 128 x 128 tiles is computed, the rest mirrored (and, for few tiles or a partly filled
-    last round, tiles are cut along k: 2949 rows = 24 x 24 tiles -> every tile split; 8189 rows -> 4 full rounds + a split tail).
-    out == out.T bit for bit, the diagonal is 1 to 1e-15, everything equals NumPy to 1e-13."""
+    last round, tiles are cut along k: with the 512 workgroup slots of 256 CUs, 2949 rows = 24 x 24 tiles -> all 300 listed tiles
+    split; 8189 rows -> 2080 listed tiles = 4 full rounds + 32 split ones -- read back from the launcher, not assumed; every plan at
+    small shapes: test_gpu_gemm_plans.py).  out == out.T bit for bit, the diagonal is 1 to 1e-15, everything equals NumPy to 1e-13."""
     rng = np.random.default_rng(N + L)
     a = rng.standard_normal((N, L))
     a[1::9] = a[0::9][: len(a[1::9])]                 # duplicated rows
@@ -52,7 +53,14 @@ def test_f64_self_similarity_is_bitwise_symmetric(gpu_ctx, N, L):
     gpu_ctx.row_inv_norms_f64_dev(da.ptr, N, L, ia.ptr)
     out = gpu_ctx.buffer(N * N * 8).fill_bytes(0xff)
     gpu_ctx.cosine_f64_dev(da.ptr, N, da.ptr, N, L, ia.ptr, ia.ptr, out.ptr, N)
+    plan = gpu_ctx.gemm_last_plan()
     gpu_ctx.sync()
+    t = -(-N // 128)
+    assert (plan["model"], plan["tiles_m"], plan["symm"], plan["n_main"] + plan["n_tail"]) == (3, t, 1, t * (t + 1) // 2), plan
+    if N == 2949:
+        assert (plan["n_main"], plan["n_tail"]) == (0, 300) and plan["split"] > 1, plan
+    if N == 8189:
+        assert (plan["n_main"], plan["n_tail"]) == (2048, 32) and plan["split"] > 1, plan
     got = out.download((N, N), np.float64)
     assert np.array_equal(got, got.T)
     np.testing.assert_allclose(np.diag(got), 1.0, rtol=0, atol=4e-15)
@@ -174,8 +182,9 @@ def test_shipped_vocabularies_through_the_class_api():
 @pytest.mark.parametrize("M,N,L", [(2100, 33000, 200), (1300, 52000, 136), (4100, 16500, 72)])
 def test_fp16_8phase_gemm_on_ragged_shapes(gpu_ctx, M, N, L):
     """pvs_cosine_f16_dev on problems of more than four rounds of 256 x 256 tiles, so that the full rounds run on the 8-phase
-    kernel (gemm_f16_8ph.hpp) and the partly filled last round on the split-K two-stage kernel: rows / columns that do not fill
-    the edge tiles, L = 200 (three full k-tiles + a partial one: chunks past L staged from zeros, an even tile count), L = 136 (an
+    kernel (gemm_f16_8ph.hpp) and -- at the first and the last shape -- the partly filled last round on the split-K two-stage
+    kernel (read back from the launcher; the 1224 tiles of the middle shape all run whole, the rule splits no tail of 200 in 256
+    slots; every plan at small shapes: test_gpu_gemm_plans.py): rows / columns that do not fill the edge tiles, L = 200 (three full k-tiles + a partial one: chunks past L staged from zeros, an even tile count), L = 136 (an
     odd tile count: the second buffer of the last iteration is a zero tile), L = 72 (shorter than the prologue's look-ahead).
     Reference: float64 dot products of the fp16-rounded operands."""
     import torch
@@ -191,7 +200,11 @@ def test_fp16_8phase_gemm_on_ragged_shapes(gpu_ctx, M, N, L):
     out = torch.full((M, N), float("nan"), dtype=torch.float32, device=dev)
     torch.cuda.synchronize()
     gpu_ctx.cosine_f16_dev(a16.data_ptr(), M, b16.data_ptr(), N, L, ia.data_ptr(), ib.data_ptr(), out.data_ptr(), N)
+    plan = gpu_ctx.gemm_last_plan()
     gpu_ctx.sync()
+    assert (plan["model"], plan["main_8ph"]) == (1, 1) and plan["n_main"] >= 1024, plan
+    want_tail = {2100: (1024, 137), 1300: (1224, 0), 4100: (1024, 81)}[M]
+    assert (plan["n_main"], plan["n_tail"]) == want_tail and (plan["split"] > 1) == (want_tail[1] > 0), plan
     ref = (a16.double() @ b16.double().T) * ia.double()[:, None] * ib.double()[None, :]
     err = (out.double() - ref).abs().max().item()
     assert torch.isfinite(out).all() and err < 2e-6, err
@@ -200,10 +213,10 @@ def test_fp16_8phase_gemm_on_ragged_shapes(gpu_ctx, M, N, L):
 
 @pytest.mark.parametrize("nq,N,L,k", [(2100, 33000, 200, 10), (1100, 70000, 264, 5)])
 def test_filtered_topk_through_the_256x128_prefilter_kernel(gpu_ctx, nq, N, L, k):
-    """pvs_cosine_topk_filtered_dev on a query block x corpus large enough for the two-level 256 x 128 prefilter GEMM
-    (gemm_f16_2lvl.hpp: >= 4 rounds of tiles, general order), ragged in rows, columns and k-tiles (L = 200: partial last k-tile;
-    L = 264: five k-tiles, a count that is not a multiple of the three LDS buffers) and over more than one 32768-column panel:
-    indices AND float32 score bits identical to the exact path (f32 MFMA GEMM over all pairs + select)."""
+    """pvs_cosine_topk_filtered_dev on a query block x corpus of several 32768-column panels, ragged in rows, columns and k-tiles (L = 200: partial last k-tile;
+    L = 264: five k-tiles, a count that is not a multiple of the three LDS buffers): indices AND float32 score bits identical to the
+    exact path (f32 MFMA GEMM over all pairs + select).  Which prefilter kernel a panel takes is not asserted here (a call reads
+    back its last panel only, and that one is narrow); test_gpu_gemm_plans.py pins the two-level 256 x 128 kernel by read-back."""
     import torch
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
