@@ -1070,6 +1070,34 @@ int pvs_ivf_sq8_scan_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float*
  * checks of nprobe, nlist, slice_rows and the offsets. */
 int pvs_ivf_sq8_scan_plan(pvs_ctx* ctx, int64_t nq, int nprobe, const int64_t* h_list_off, int nlist, int slice_rows, int64_t* h_plan);
 
+/* ---------------------------------------------------------------- the same search scanned by list
+ * For batches of queries.  Every definition above stays: the candidate rows, W, the padding and the result are those of
+ * pvs_ivf_sq8_scan_topk_dev, and the lists are the same bytes for every input; only who computes which slot differs.  The (query,
+ * probe) pairs of a block of queries are grouped by list, and every tile of 128 consecutive stored rows of a list is scored against
+ * the grouped pairs of that list, 128 at a time, on the int8 matrix pipe: a probed row is read once per query block, not once per query.
+ *   base[q][j]  the first slot of probe j in the candidate row of query q: the lengths of the probed lists before it in probe order,
+ *               a probe outside [0, nlist) counting as length 0.  total[q]: the live slots of the row.
+ *   grouping    the pairs (q, j) whose probe lies in [0, nlist), in (list ascending, query ascending) order: a stable sort of the
+ *               pairs in (q, j) order on the list number.  goff[l] .. goff[l + 1] are the pairs of list l, gq[p] the query of grouped
+ *               pair p and gbase[p] its base[q][j].  P = goff[nlist] pairs; gq and gbase behind P are not written. */
+/* The grouping of one query block alone: d_probe int64 [qn][nprobe] -> d_base int32 [qn][nprobe], d_total int32 [qn], d_goff int32
+ * [nlist + 1], d_gq and d_gbase int32 [qn nprobe].  0 <= qn <= 65535 and qn nprobe <= 2^20 (one query block); nlist and nprobe as
+ * above; N < 2^31 is a precondition.  qn == 0 writes goff = 0 only.  No position is decided by an atomic.  Enqueues on the context's
+ * stream; nothing is copied to the host and the stream is not waited for.  Timed on slot 6. */
+int pvs_ivf_sq8_group_probes_dev(pvs_ctx* ctx, const int64_t* d_probe, int64_t qn, int nprobe, const int64_t* d_list_off, int nlist,
+                                 int32_t* d_base, int32_t* d_total, int32_t* d_goff, int32_t* d_gq, int32_t* d_gbase);
+/* The arguments, checks and results of pvs_ivf_sq8_scan_topk_dev, with query_block in the place of slice_rows: the queries grouped
+ * at a time, a test seam: 0 lets the host choose (the query block of the scan above, capped so that query_block nprobe <= 2^20 pairs,
+ * 32 MiB of grouping arrays), a positive value means at most that many; negative is PVS_ERR_INVALID; the result does not depend
+ * on it.  Timed on slots 6 (the grouping), 2 (the tiles) and 3 (the ranking). */
+int pvs_ivf_sq8_scan_lists_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q, int64_t nq, int L, const int64_t* d_probe,
+                                    int nprobe, const int64_t* d_list_off, const int64_t* h_list_off, int nlist, const int8_t* d_codes,
+                                    const float* d_inv_db, const int32_t* d_ids, int k, int query_block, int64_t* d_idx, float* d_val);
+/* h_plan int64 [4] = W, the queries of one block, the row tiles (workgroups of the tile kernel: the sum over the lists of
+ * ceil(length / 128)), the pairs one block's grouping arrays hold (query block x nprobe).  No device work. */
+int pvs_ivf_sq8_scan_lists_plan(pvs_ctx* ctx, int64_t nq, int nprobe, const int64_t* h_list_off, int nlist, int query_block,
+                                int64_t* h_plan);
+
 /* ---------------------------------------------------------------- measurement hooks (bench.py) */
 /* Enable per-kernel-family HIP-event timing on the context's stream. which: 0 assign, 1 aggregate,
  * 2 cosine gemm (and the ADC scan of the compact index, which stands in its place), 3 top-k, 4 fisher posterior, 5 fisher moments, 6 norms/misc, 7 exact re-scoring (filtered top-k). */

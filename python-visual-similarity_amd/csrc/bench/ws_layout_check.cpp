@@ -153,6 +153,18 @@ static void asmk_expand_site(size_t queries, size_t nchunks) {
         "ASMK expansion block queries=%zu chunks=%zu", queries, nchunks);
 }
 
+// the grouping block of the probed int8 scan by list (ivf_sq8.hip): tile prefix, base, total, goff, gq, gbase, then the sort's arrays
+static void ivf_sq8_group_site(size_t queries, size_t nprobe, size_t nlist) {
+  const size_t pairs = queries * nprobe, ntiles = (pairs + 4095) / 4096, ncounts = 257 * ntiles, nscan = (ncounts + 2047) / 2048;
+  const IvfSq8GroupLayout g = ivf_sq8_group_layout(queries, pairs, nlist, ncounts, nscan);
+  const size_t off_b = al((nlist + 1) * 4), pair_b = al(pairs * 4), item_b = al(pairs * 8);
+  CHECK(g.tile_off.off == 0 && g.base.off == off_b && g.total.off == off_b + pair_b && g.goff.off == off_b + pair_b + al(queries * 4) &&
+            g.gq.off == 2 * off_b + pair_b + al(queries * 4) && g.gbase.off == g.gq.off + pair_b && g.items_a.off == g.gbase.off + pair_b &&
+            g.items_b.off == g.items_a.off + item_b && g.counts.off == g.items_b.off + item_b && g.partials.off == g.counts.off + al(ncounts * 4) &&
+            g.bytes == g.partials.off + al(nscan * 4),
+        "IVF int8 grouping block queries=%zu nprobe=%zu nlist=%zu", queries, nprobe, nlist);
+}
+
 int main() {
   generic_align<256>();
   generic_align<16>();
@@ -181,6 +193,10 @@ int main() {
   for (size_t N : rows) asmk_update_sites(N, (N + 4095) / 4096);
   for (size_t nq : {(size_t)1, (size_t)3, (size_t)128})
     for (size_t nchunks : {(size_t)1, (size_t)5, (size_t)1024}) asmk_expand_site(nq, nchunks);
+  for (size_t nq : rows)
+    for (size_t nprobe : {(size_t)1, (size_t)7, (size_t)1024})
+      for (size_t nlist : {(size_t)1, (size_t)1024, (size_t)65536})
+        if (nprobe <= nlist) ivf_sq8_group_site(nq, nprobe, nlist);
   for (size_t nc : rows) sift_site(nc);
   for (size_t nc : Ns) sift_site(nc);
   const size_t splits[] = {2, 3, 64, 256}, ms[] = {1, 5, 8};

@@ -43,12 +43,14 @@ namespace pvs {
 //   WS_MATCH_TABLE    match.hip: upload_pairs, pvs_match_u8_dev
 //   WS_VERIFY_POINTS, WS_VERIFY_SMALL    match.hip: pvs_verify_dev
 //   WS_IVF_CANDIDATES ivf.hip: pvs_ivf_scan_topk_dev (candidate scores | candidate ids of one query block)
-//                     ivf_sq8.hip: pvs_ivf_sq8_scan_topk_dev (the same layout)
+//                     ivf_sq8.hip: pvs_ivf_sq8_scan_topk_dev, pvs_ivf_sq8_scan_lists_topk_dev (the same layout)
 //   WS_UPDATE         update.hip: pvs_keep_positions_dev (scan partials), pvs_compact_rows_dev in place (staging rows of one window),
 //                     pvs_ivf_insert_dev (source of every merged row), pvs_ivf_remove_dev (stored keep mask | positions | scan partials);
 //                     asmk_update.hip: pvs_asmk_invert_dev (two item arrays | digit counts | scan partials), pvs_asmk_remove_dev
 //                     (survivor flags, scanned in place | scan partials); asmk_expand.hip: pvs_asmk_expand_dev (hit masks | chunk counts |
-//                     chunk weight sums of one query block)
+//                     chunk weight sums of one query block); ivf_sq8.hip: pvs_ivf_sq8_scan_lists_topk_dev, pvs_ivf_sq8_group_probes_dev
+//                     (tile prefix | the grouping of one query block | the sort's items, digit counts and scan partials): a search
+//                     calls no maintenance entry, so none of the users above is live in the same call
 enum WsSlot : int {
   WS_STAGE_IN = 0, WS_SCRATCH = 1, WS_PANEL_OUT = 2, WS_PROJECTED = 3, WS_AUX_ROWS = 4, WS_FP16_ROWS = 5, WS_LISTS = 6, WS_NB_NORMS = 7,
   WS_NB_F64_ROWS = 8, WS_DSIFT_TABLE = 9, WS_SIFT_PYRAMID = 10, WS_SIFT_TABLES = 11, WS_SIFT_KEYPOINTS = 12, WS_MATCH_TABLE = 13,
@@ -221,6 +223,22 @@ struct AsmkExpandLayout {
 inline AsmkExpandLayout asmk_expand_layout(size_t queries, size_t nchunks) {
   WsLayout<> l;
   return {l.add<uint32_t>(queries * nchunks * 64), l.add<int32_t>(queries * nchunks), l.add<int32_t>(queries * nchunks), l.bytes()};
+}
+
+// pvs_ivf_sq8_scan_lists_topk_dev and pvs_ivf_sq8_group_probes_dev, WS_UPDATE: the tile prefix of the lists; for one query block of
+// `pairs` = queries x nprobe (query, probe) pairs the first slot of every pair, the live slots of every query, the group offsets of the
+// lists, the query and the first slot of every grouped pair; then the sort's two item arrays, digit counts and scan partials
+struct IvfSq8GroupLayout {
+  WsPiece<int32_t> tile_off, base, total, goff, gq, gbase;
+  WsPiece<uint64_t> items_a, items_b;
+  WsPiece<int32_t> counts, partials;
+  size_t bytes;
+};
+inline IvfSq8GroupLayout ivf_sq8_group_layout(size_t queries, size_t pairs, size_t nlist, size_t ncounts, size_t nscanblocks) {
+  WsLayout<> l;
+  return {l.add<int32_t>(nlist + 1), l.add<int32_t>(pairs),   l.add<int32_t>(queries), l.add<int32_t>(nlist + 1), l.add<int32_t>(pairs),
+          l.add<int32_t>(pairs),     l.add<uint64_t>(pairs), l.add<uint64_t>(pairs),  l.add<int32_t>(ncounts),   l.add<int32_t>(nscanblocks),
+          l.bytes()};
 }
 
 // pvs_kmeans_topm_dev with splits > 1, WS_LISTS: the partial lists [row][split][m], indices then values

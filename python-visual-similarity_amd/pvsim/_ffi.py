@@ -192,6 +192,9 @@ SIGNATURES = {
     "pvs_sq8_topk_subset_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _vp, _int, _int, _int, _vp, _vp, _vp],
     "pvs_ivf_sq8_scan_topk_dev": [_vp, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp],
     "pvs_ivf_sq8_scan_plan": [_vp, _i64, _int, _vp, _int, _int, _vp],
+    "pvs_ivf_sq8_group_probes_dev": [_vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _vp, _vp, _vp],
+    "pvs_ivf_sq8_scan_lists_topk_dev": [_vp, _vp, _vp, _i64, _int, _vp, _int, _vp, _vp, _int, _vp, _vp, _vp, _int, _int, _vp, _vp],
+    "pvs_ivf_sq8_scan_lists_plan": [_vp, _i64, _int, _vp, _int, _int, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_gemm_last_plan": [_vp, _vp],
     "pvs_timers_enable": [_vp, _int],

@@ -595,6 +595,33 @@ class Context:
         check(_ffi.lib().pvs_ivf_sq8_scan_plan(self.handle, int(nq), int(nprobe), ptr(h), int(nlist), int(slice_rows), out))
         return {"W": int(out[0]), "query_block": int(out[1]), "slice_rows": int(out[2]), "slices": int(out[3])}
 
+    # the same candidate rows filled by list, for batches of queries
+    def ivf_sq8_group_probes_dev(self, d_probe, qn, nprobe, d_list_off, nlist, d_base, d_total, d_goff, d_gq, d_gbase):
+        """pvs_ivf_sq8_group_probes_dev: the probes int64 (qn, nprobe) of one query block -> base int32 (qn, nprobe), total int32 (qn,),
+        goff int32 (nlist + 1,), and gq, gbase int32 (qn nprobe,) of which the first goff[nlist] entries are written"""
+        check(_ffi.lib().pvs_ivf_sq8_group_probes_dev(self.handle, ptr(d_probe), int(qn), int(nprobe), ptr(d_list_off), int(nlist),
+                                                      ptr(d_base), ptr(d_total), ptr(d_goff), ptr(d_gq), ptr(d_gbase)))
+
+    def ivf_sq8_scan_lists_topk_dev(self, d_qcodes, d_invq, nq, L, d_probe, nprobe, d_list_off, h_list_off, nlist, d_codes, d_invdb, d_ids,
+                                    k, d_idx, d_val, query_block=0):
+        """pvs_ivf_sq8_scan_lists_topk_dev: the arguments of ivf_sq8_scan_topk_dev; query_block: queries grouped at a time (0: the
+        host's rule), a test seam that never changes the result"""
+        h = np.ascontiguousarray(h_list_off, dtype=np.int64)
+        if h.shape != (nlist + 1,):
+            raise ValueError(f"h_list_off must have nlist + 1 = {nlist + 1} entries, got shape {h.shape}")
+        check(_ffi.lib().pvs_ivf_sq8_scan_lists_topk_dev(self.handle, ptr(d_qcodes), ptr(d_invq), int(nq), int(L), ptr(d_probe), int(nprobe),
+                                                         ptr(d_list_off), ptr(h), int(nlist), ptr(d_codes), ptr(d_invdb), ptr(d_ids),
+                                                         int(k), int(query_block), ptr(d_idx), ptr(d_val)))
+
+    def ivf_sq8_scan_lists_plan(self, nq, nprobe, h_list_off, nlist, query_block=0) -> dict:
+        """pvs_ivf_sq8_scan_lists_plan -> dict(W, query_block, row_tiles, pairs): how the scan by list is cut, from the host offsets alone"""
+        h = np.ascontiguousarray(h_list_off, dtype=np.int64)
+        if h.shape != (nlist + 1,):
+            raise ValueError(f"h_list_off must have nlist + 1 = {nlist + 1} entries, got shape {h.shape}")
+        out = (C.c_int64 * 4)()
+        check(_ffi.lib().pvs_ivf_sq8_scan_lists_plan(self.handle, int(nq), int(nprobe), ptr(h), int(nlist), int(query_block), out))
+        return {"W": int(out[0]), "query_block": int(out[1]), "row_tiles": int(out[2]), "pairs": int(out[3])}
+
     # query expansion / database-side augmentation (DESIGN.md section 13)
     COMBINE_CHUNK_BYTES, COMBINE_BATCH = _ffi.COMBINE_CHUNK_BYTES, _ffi.COMBINE_BATCH
 

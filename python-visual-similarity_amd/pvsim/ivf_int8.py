@@ -403,10 +403,21 @@ class IVFInt8Index:
             raise ValueError(f"k must be an integer with 1 <= k <= {min(n, MAX_IVF_K)} (min(N, {MAX_IVF_K})), got {k!r}")
         return int(k), int(nprobe)
 
-    def rank(self, query_vecs, k: int, nprobe: int, slice_rows: int = 0):
+    def rank(self, query_vecs, k: int, nprobe: int, slice_rows: int = 0, scan: str = "queries", query_block: int = 0):
         """-> (idx (nq, k) int64, val (nq, k) float32): the queries are quantised by the rule of the rows, the `nprobe` best lists of
         each are scanned and ranked by (score descending, original index ascending); slots the probed lists cannot fill are -1 /
-        -inf.  1 <= k <= min(N, 1024), 1 <= nprobe <= min(nlist, 1024).  `slice_rows` pins how the scan is cut, never what it gives."""
+        -inf.  1 <= k <= min(N, 1024), 1 <= nprobe <= min(nlist, 1024).
+
+        `scan` chooses who computes the candidate scores, never what they are: "queries" walks the probed rows once per query,
+        "lists" groups the queries of a block by list and scores every row tile of a probed list against its group on the int8
+        matrix pipe, reading a probed row once per query block: the choice for batches.  The two give the same
+        bytes.  `slice_rows` (with "queries") and `query_block` (with "lists") pin how the scan is cut, never what it gives."""
+        if scan not in ("queries", "lists"):
+            raise ValueError(f'scan must be "queries" or "lists", got {scan!r}')
+        if scan == "lists" and slice_rows != 0:
+            raise ValueError('slice_rows cuts the scan by query: it does not go with scan="lists" (query_block does)')
+        if scan == "queries" and query_block != 0:
+            raise ValueError('query_block cuts the scan by list: it does not go with scan="queries" (slice_rows does)')
         q = _f32_rows(query_vecs, "query")
         n, L = self.shape
         if q.shape[1] != L:
@@ -422,13 +433,23 @@ class IVFInt8Index:
             ctx.sq8_encode_dev(d_q.ptr, nq, L, d_qc.ptr, d_invq.ptr)
             ctx.sq8_topk_dev(d_qc.ptr, d_invq.ptr, nq, self._cent_codes.ptr, self._cent_inv.ptr, nlist, L, nprobe, 0, False, d_pidx.ptr,
                              d_pval.ptr)
-            ctx.ivf_sq8_scan_topk_dev(d_qc.ptr, d_invq.ptr, nq, L, d_pidx.ptr, nprobe, self._d_list_off.ptr, self._list_off, nlist,
-                                      self._codes.ptr, self._inv.ptr, self._ids.ptr, k, d_idx.ptr, d_val.ptr, slice_rows=slice_rows)
+            if scan == "lists":
+                ctx.ivf_sq8_scan_lists_topk_dev(d_qc.ptr, d_invq.ptr, nq, L, d_pidx.ptr, nprobe, self._d_list_off.ptr, self._list_off, nlist,
+                                                self._codes.ptr, self._inv.ptr, self._ids.ptr, k, d_idx.ptr, d_val.ptr,
+                                                query_block=query_block)
+            else:
+                ctx.ivf_sq8_scan_topk_dev(d_qc.ptr, d_invq.ptr, nq, L, d_pidx.ptr, nprobe, self._d_list_off.ptr, self._list_off, nlist,
+                                          self._codes.ptr, self._inv.ptr, self._ids.ptr, k, d_idx.ptr, d_val.ptr, slice_rows=slice_rows)
             out = d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
             probes = d_pidx.download((nq, nprobe), np.int64)
-        plan = ctx.ivf_sq8_scan_plan(nq, nprobe, self._list_off, nlist, slice_rows)
-        self.last_scan = {"W": plan["W"], "slice_rows": plan["slice_rows"], "slices": plan["slices"],
-                          "candidates": int(self.list_sizes[probes].sum())}
+        candidates = int(self.list_sizes[probes].sum())
+        if scan == "lists":
+            plan = ctx.ivf_sq8_scan_lists_plan(nq, nprobe, self._list_off, nlist, query_block)
+            self.last_scan = {"scan": "lists", "W": plan["W"], "query_block": plan["query_block"], "row_tiles": plan["row_tiles"],
+                              "pairs": plan["pairs"], "candidates": candidates}
+        else:
+            plan = ctx.ivf_sq8_scan_plan(nq, nprobe, self._list_off, nlist, slice_rows)
+            self.last_scan = {"W": plan["W"], "slice_rows": plan["slice_rows"], "slices": plan["slices"], "candidates": candidates}
         return out
 
     # ---- persistence
