@@ -1,7 +1,8 @@
 /*
  * pvsim_diag.h -- DIAGNOSTIC entry points of libpvsim_hip.so.  Not part of the product ABI (include/pvsim.h): nothing in the
  * package's encode / similarity / retrieval path calls them; they exist for tests/tools/{assign,fused}_profile.py, which read
- * in-kernel cycle stamps of specially built kernel variants.  The product kernels carry no stamps.
+ * in-kernel cycle stamps of specially built kernel variants.  The product kernels carry no stamps.  The suite also reads the plan
+ * of the last GEMM and poisons recycled device memory through them.
  */
 #ifndef PVSIM_DIAG_H
 #define PVSIM_DIAG_H
@@ -40,6 +41,13 @@ typedef enum {
   PVS_GEMM_TAIL_UNSPLIT_ONE_SLICE = 2  /* a single k-tile: nothing to split (f64) */
 } pvs_gemm_tail_unsplit;
 int pvs_gemm_last_plan(pvs_ctx* ctx, int32_t out12[12]);
+
+/* Device memory that a context hands out again without clearing it (tests/test_gpu_recycled_memory.py).  pvs_diag_poison queues on
+ * the context's stream a memset with `byte` (0..255) of the WHOLE capacity of every allocated workspace slot (what & 1) and / or of
+ * every block now waiting in the table block cache (what & 2); it allocates nothing and frees nothing.  pvs_diag_ws_bytes reports
+ * the capacity of the 18 workspace slots in the order of pvs::WsSlot (csrc/workspace.hpp), 0 for a slot never reserved. */
+int pvs_diag_poison(pvs_ctx* ctx, int byte, int what);
+int pvs_diag_ws_bytes(pvs_ctx* ctx, size_t out18[18]);
 
 #ifdef __cplusplus
 }

@@ -1260,6 +1260,29 @@ PVS_EXPORT int pvs_gemm_last_plan(pvs_ctx* ctx, int32_t out12[12]) {
   return PVS_OK;
 }
 
+// Fill what the context hands out again without clearing it: tests run an entry point on such memory and hold the bytes against a
+// run on a new context.  Memsets of whole capacities on the context's stream; nothing is allocated or freed.
+PVS_EXPORT int pvs_diag_poison(pvs_ctx* ctx, int byte, int what) {
+  PVS_NEED(ctx, "ctx");
+  if (byte < 0 || byte > 255 || (what & ~3)) PVS_FAIL(PVS_ERR_INVALID, "pvs_diag_poison: byte %d, what %d", byte, what);
+  PVS_HIP(hipSetDevice(ctx->device));
+  if (what & 1)
+    for (int i = 0; i < pvs_ctx::NWS; ++i)
+      if (ctx->ws[i] && ctx->ws_bytes[i]) PVS_HIP(hipMemsetAsync(ctx->ws[i], byte, ctx->ws_bytes[i], ctx->stream));
+  if (what & 2)
+    for (const auto& kv : ctx->block_cache)
+      if (kv.second && kv.first) PVS_HIP(hipMemsetAsync(kv.second, byte, kv.first, ctx->stream));
+  return PVS_OK;
+}
+
+PVS_EXPORT int pvs_diag_ws_bytes(pvs_ctx* ctx, size_t out18[18]) {
+  PVS_NEED(ctx, "ctx");
+  PVS_NEED(out18, "out18");
+  static_assert(pvs_ctx::NWS == 18, "pvs_diag_ws_bytes reports 18 slots");
+  for (int i = 0; i < pvs_ctx::NWS; ++i) out18[i] = ctx->ws[i] ? ctx->ws_bytes[i] : 0;
+  return PVS_OK;
+}
+
 // ================================================================================ timers
 PVS_EXPORT int pvs_timers_enable(pvs_ctx* ctx, int on) {
   PVS_NEED(ctx, "ctx");

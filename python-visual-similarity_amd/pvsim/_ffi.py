@@ -33,6 +33,10 @@ GEMM_EXACT_F32, GEMM_F16_256, GEMM_F16_BOUNDED, GEMM_F64, GEMM_F16_2LVL, GEMM_GE
 GEMM_TAIL_UNSPLIT_BYTES, GEMM_TAIL_UNSPLIT_ONE_SLICE = 1, 2                                           # pvs_gemm_tail_unsplit
 GEMM_PLAN_FIELDS = ("model", "tiles_m", "tiles_n", "symm", "dual", "n_main", "n_tail", "split", "nparts", "tail_unsplit",
                     "main_8ph", "accumulate")
+WS_SLOTS = ("WS_STAGE_IN", "WS_SCRATCH", "WS_PANEL_OUT", "WS_PROJECTED", "WS_AUX_ROWS", "WS_FP16_ROWS", "WS_LISTS", "WS_NB_NORMS",
+            "WS_NB_F64_ROWS", "WS_DSIFT_TABLE", "WS_SIFT_PYRAMID", "WS_SIFT_TABLES", "WS_SIFT_KEYPOINTS", "WS_MATCH_TABLE",
+            "WS_VERIFY_POINTS", "WS_VERIFY_SMALL", "WS_IVF_CANDIDATES", "WS_UPDATE")     # pvs::WsSlot (csrc/workspace.hpp), in order
+POISON_WORKSPACE, POISON_TABLE_CACHE = 1, 2                                              # pvs_diag_poison `what` bits
 SQ8_PATH_AUTO, SQ8_PATH_ROWS, SQ8_PATH_MATRIX = 0, 1, 2
 SQ8_MAX_L = 131072                # 127^2 * L < 2^31
 RANGE_UPPER = 1                   # PVS_RANGE_UPPER: the self-join, pairs j > i only
@@ -197,6 +201,8 @@ SIGNATURES = {
     "pvs_ivf_sq8_scan_lists_plan": [_vp, _i64, _int, _vp, _int, _int, _vp],
     "pvs_fused_profile": [_vp, _int, _vp],
     "pvs_gemm_last_plan": [_vp, _vp],
+    "pvs_diag_poison": [_vp, _int, _int],
+    "pvs_diag_ws_bytes": [_vp, _vp],
     "pvs_timers_enable": [_vp, _int],
     "pvs_timers_reset": [_vp],
     "pvs_timers_read": [_vp, _int, C.POINTER(C.c_double), C.POINTER(C.c_int64)],

@@ -124,6 +124,14 @@ class DevicePool:
     """Grow-only cache of pvs_malloc blocks keyed by size class.  Every user enqueues on the context's one stream, so a block
     handed out again after release_all() is reused in stream order (hipMalloc / hipFree synchronise the device: never per step)."""
 
+    class _Lease:
+        """One hand-out of a block.  A block is handed out many times, a lease once: an array of an earlier hand-out of the same
+        block carries an earlier lease, and release() does nothing for it."""
+        __slots__ = ("cls", "buf")
+
+        def __init__(self, cls, buf):
+            self.cls, self.buf = cls, buf
+
     def __init__(self, ctx):
         self.ctx, self._free, self._used = ctx, {}, []
 
@@ -131,24 +139,25 @@ class DevicePool:
         nbytes = max(int(np.prod(shape, dtype=np.int64)) * _ITEM[dtype], 16)
         cls = 1 << (nbytes - 1).bit_length()
         lst = self._free.setdefault(cls, [])
-        buf = lst.pop() if lst else self.ctx.buffer(cls)
-        self._used.append((cls, buf))
-        return DevArray(self.ctx, buf.ptr, shape, dtype, buf)
+        lease = DevicePool._Lease(cls, lst.pop() if lst else self.ctx.buffer(cls))
+        self._used.append(lease)
+        return DevArray(self.ctx, lease.buf.ptr, shape, dtype, lease)
 
     def full(self, shape, dtype: str, fill) -> DevArray:
         return self.empty(shape, dtype).fill(fill)
 
     def release(self, arr: DevArray):
-        """Hand one array's block back (no-op if it is not a live block of this pool)."""
-        for i, (cls, buf) in enumerate(self._used):
-            if buf is arr._owner:
-                self._free.setdefault(cls, []).append(buf)
+        """Hand one array's block back (no-op if its lease is not live: released before, singly or by release_all(), or not of
+        this pool; a view of an array is not the array)."""
+        for i, lease in enumerate(self._used):
+            if lease is arr._owner:
+                self._free.setdefault(lease.cls, []).append(lease.buf)
                 del self._used[i]
                 return
 
     def release_all(self):
-        for cls, buf in self._used:
-            self._free.setdefault(cls, []).append(buf)
+        for lease in self._used:
+            self._free.setdefault(lease.cls, []).append(lease.buf)
         self._used = []
 
     def close(self):
@@ -560,7 +569,9 @@ class ShardedVLADIndex:
         # a new encode starts a new cycle: the blocks of the previous encode / exchange / topk go back to the pool (same
         # stream, so their reuse is ordered behind the work that still reads them) -- repeated cycles do not grow device memory
         self.pool.release_all()
-        self.enc_loc = self.pool.full((self.block, L), "float32", 0.0)
+        self._lists, self._search_bufs = (), ()        # every handle of the previous cycle is dead with it
+        self.enc_all = self.inv_all = None
+        self.enc_loc =self.pool.full((self.block, L), "float32", 0.0)
         self.inv_loc = self.pool.full((self.block,), "float32", 1.0)
         self.ctx.vlad_encode_dev(self.cb, d_desc, kind, d_offsets, n_loc, total_desc, self.enc_loc.ptr, power, norm_order,
                                  epsilon, d_inv_norm=self.inv_loc.ptr)

@@ -276,6 +276,17 @@ class Context:
         check(_ffi.lib().pvs_gemm_last_plan(self.handle, out))
         return dict(zip(_ffi.GEMM_PLAN_FIELDS, (int(v) for v in out)))
 
+    def diag_poison(self, byte: int, what: int = _ffi.POISON_WORKSPACE | _ffi.POISON_TABLE_CACHE) -> None:
+        """pvs_diag_poison (diagnostic): fill the whole capacity of every workspace slot (what & 1) and / or of every block
+        in the table block cache (what & 2) with `byte`, on this context's stream."""
+        check(_ffi.lib().pvs_diag_poison(self.handle, int(byte), int(what)))
+
+    def diag_ws_bytes(self) -> dict:
+        """pvs_diag_ws_bytes (diagnostic): capacity of every workspace slot by the names of _ffi.WS_SLOTS; 0 = never reserved."""
+        out = (C.c_size_t * len(_ffi.WS_SLOTS))()
+        check(_ffi.lib().pvs_diag_ws_bytes(self.handle, out))
+        return dict(zip(_ffi.WS_SLOTS, (int(v) for v in out)))
+
     def fill_dev(self, d_ptr: int, n_elems: int, dtype: str, value) -> None:
         """4- or 8-byte pattern fill on this context's stream (dtype: float32 / int32 / int64 / float64)."""
         a = np.array([value], dtype=dtype)

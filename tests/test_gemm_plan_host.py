@@ -62,6 +62,14 @@ def test_option_and_read_back_are_declared_alike_in_header_and_binding():
     assert re.search(r"PVS_GEMM_TAIL_UNSPLIT_ONE_SLICE = (\d+)", diag).group(1) == str(_ffi.GEMM_TAIL_UNSPLIT_ONE_SLICE)
     assert "pvs_gemm_last_plan" in diag and "pvs_gemm_last_plan" not in header                         # diagnostic, not product ABI
     assert len(_ffi.GEMM_PLAN_FIELDS) == 12 and "pvs_gemm_last_plan" in _ffi.SIGNATURES
+    for name in ("pvs_diag_poison", "pvs_diag_ws_bytes"):                                              # recycled-memory diagnostics
+        assert name in diag and name not in header and name in _ffi.SIGNATURES
+    functions = set(re.findall(r"\b(pvs_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", diag, flags=re.S)))
+    assert functions == {"pvs_fused_profile", "pvs_gemm_last_plan", "pvs_diag_poison", "pvs_diag_ws_bytes"}
+    with open(os.path.join(REPO, "python-visual-similarity_amd", "csrc", "workspace.hpp")) as f:
+        enum = re.search(r"enum WsSlot : int \{(.*?)\};", f.read(), flags=re.S).group(1)
+    slots = sorted(re.findall(r"(WS_[A-Z0-9_]+) = (\d+)", enum), key=lambda kv: int(kv[1]))
+    assert tuple(n for n, _ in slots) == _ffi.WS_SLOTS and [int(v) for _, v in slots] == list(range(18))
 
 
 # ------------------------------------------------------------------------------------------------ the twins

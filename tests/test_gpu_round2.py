@@ -333,3 +333,42 @@ def test_sharded_index_without_torch(gpu_ctx, tables):
     assert np.array_equal(index.enc_loc.numpy()[: len(imgs)], enc)
     assert np.array_equal(idx, ridx) and np.array_equal(val.view(np.uint32), rval.view(np.uint32))
     pool.close()
+
+
+def test_sharded_index_repeats_its_cycle_on_recycled_blocks(gpu_ctx, tables):
+    """The same 37 images through encode -> exchange -> topk three times with k = 1 and three times with k = 4, then one encode ->
+    search: every encode hands the blocks of the previous cycle back to the pool, and every later hand-out reuses them.  With k = 1
+    the value list and the inverse norms fall into one size class: a handle of the previous cycle that frees the block again lets
+    the list's -inf fill overwrite the norms the ranking reads.  Every cycle's lists equal the host entry points', bit for bit."""
+    from pvsim import distributed as pd
+    rng = np.random.default_rng(12)
+    imgs = [synth.sift_like(int(n), rng).astype(np.uint8) for n in rng.integers(40, 400, size=37)]
+    packed, off = pack_descriptors(imgs, 128, np.uint8)
+    n = len(imgs)
+    cb = gpu_ctx.codebook(tables["centroids"])
+    enc = gpu_ctx.vlad_encode(cb, packed, off, DESC_U8_ROOTSIFT)
+    want = {k: gpu_ctx.cosine_topk(enc, enc, k) for k in (1, 4)}
+    pool = pd.DevicePool(gpu_ctx)
+    d_x = pool.empty(packed.shape, "uint8").upload(packed)
+    d_off = pool.empty(off.shape, "int64").upload(off)
+    index = pd.ShardedVLADIndex(gpu_ctx, cb, n)
+
+    def same(got, k, where):
+        assert np.array_equal(got[0], want[k][0]), where
+        assert np.array_equal(got[1].view(np.uint32), want[k][1].view(np.uint32)), where
+
+    for k in (1, 4):
+        for cycle in (1, 2, 3):
+            index.encode_local(d_x.ptr, DESC_U8_ROOTSIFT, d_off.ptr, int(off[-1]))
+            index.exchange()
+            same(index.topk(k), k, f"topk: k = {k}, cycle {cycle}")
+            assert np.array_equal(index.enc_loc.numpy()[:n], enc), (k, cycle)
+            live = [index.enc_loc.ptr, index.inv_loc.ptr] + [a.ptr for a in index._lists]
+            assert len(set(live)) == len(live), f"k = {k}, cycle {cycle}: two live arrays share a block"
+    for k in (1, 4):
+        index.encode_local(d_x.ptr, DESC_U8_ROOTSIFT, d_off.ptr, int(off[-1]))
+        same(index.search(index.enc_loc[:n], index.inv_loc[:n], k), k, f"search: k = {k}")
+        same(index.search(index.enc_loc[:n], index.inv_loc[:n], k), k, f"second search: k = {k}")
+    index.pool.close()
+    pool.close()
+    cb.close()
