@@ -998,6 +998,33 @@ int pvs_sq8_topk_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q,
 int pvs_cosine_range_dev(pvs_ctx* ctx, const float* d_Q, int64_t nq, const float* d_DB, int64_t N, int64_t L,
                          const float* d_inv_q, const float* d_inv_db, float threshold, int flags, int path, int tile,
                          int64_t capacity, int64_t* d_row, int64_t* d_col, float* d_val, int64_t* h_total, int64_t* h_stats);
+/* The threshold join on int8 code rows: d_qcodes int8 [nq][ld] and d_codes int8 [N][ld], ld = PVS_SQ8_LD(L),
+ * 16-byte aligned, with their row factors, as pvs_sq8_topk_dev takes them.
+ *   score       s(i, j) = ((float)acc * inv_q[i]) * inv_d[j], acc the int32 dot product of the two code rows: the bits pvs_sq8_topk_dev
+ *               reports for the pair, on every path, tile size and capacity.  No prefilter, no re-score: acc is an integer.
+ *   hit         s(i, j) >= threshold compared in float32; a NaN score (a factor may be anything) is never a hit; a zero row has
+ *               factor 0 and scores +0 against everything, so it hits iff threshold <= 0.
+ *   self-join   PVS_RANGE_UPPER (nq == N, the same codes and factors on both sides): for i < j the pair is a hit iff s(i, j) >= threshold
+ *               with row i in the QUERY role, and s(i, j) is the value emitted.  The score is NOT symmetric: (a * x) * y and
+ *               (a * y) * x are two separately rounded products and differ in about a third of the pairs.  A pair with
+ *               s(i, j) < threshold <= s(j, i) is not emitted.
+ * path: 0 auto, 1 panel (the float panels of pvs_sq8_topk_dev, row scan or GEMM by PVS_OPT_SQ8_PATH, thresholded where they lie),
+ * 2 mask (the int8 GEMM writes one bit per pair; popcount, scan, ordered emit; the scores of the emitted pairs are computed once
+ * at the end, from the same integer by the same expression).  Path 0 is path 1 while pvs_sq8_topk_dev takes the row scan (at most
+ * 4 queries under the default PVS_OPT_SQ8_PATH) and path 2 beyond.  tile: 0 = the plan's geometry (panel: 8192 x 32768; mask:
+ * 8192 x 262144); 1..32768 = row blocks and column panels of that many rows (test seams; any value, no multiple of 32 or 128 needed).
+ * Order, capacity protocol, flags and synchronisation are those of pvs_cosine_range_dev: row blocks ascending, column panels
+ * ascending, (row, col) ascending within a tile; min(total, capacity) triples written, *h_total = total, PVS_ERR_CAPACITY when
+ * total > capacity with nothing written at or beyond the capacity; capacity 0 with NULL outputs counts.  No position is decided by
+ * an atomic.  h_stats (optional, int64[6]): [0] the path taken (1 or 2), [2] pairs scored by the pair kernel, [3] tiles scored,
+ * [4] tiles skipped below the diagonal, [1] and [5] 0.
+ * PVS_ERR_INVALID, before anything is launched: a non-finite threshold, unknown flags, PVS_RANGE_UPPER with nq != N, path outside
+ * 0..2, tile outside 0..32768, capacity outside 0..PVS_RANGE_MAX_CAPACITY, L outside 1..131072, nq or N beyond 2^31 - 1, a missing
+ * or misaligned pointer that will be used.  nq == 0 or N == 0 is a no-op with total 0.  Timed on slots 2 (scores), 3 (count, scan,
+ * emit) and 7 (pair scores). */
+int pvs_sq8_range_dev(pvs_ctx* ctx, const int8_t* d_qcodes, const float* d_inv_q, int64_t nq, const int8_t* d_codes,
+                      const float* d_inv_db, int64_t N, int L, float threshold, int flags, int path, int tile, int64_t capacity,
+                      int64_t* d_row, int64_t* d_col, float* d_val, int64_t* h_total, int64_t* h_stats);
 /* Connected components of an undirected pair list over N nodes: d_label[i] (int32) = the smallest node index of i's component.
  * E == 0 gives the identity.  N < 2^31.  h_stats (optional, int64[2]): [0] rounds, [1] components.  A node id outside [0, N) is
  * PVS_ERR_INVALID (checked on the device before the first round).  Synchronises. */

@@ -133,6 +133,22 @@ int main() {
   CHECK(panel_full_rows(7, 100000000, panel_elems<float>()).QT == 2, "filter overflow batch of 7 rows, N = 10^8");
   CHECK(panel_full_rows(0, 1000, panel_elems<float>()).QT == 1, "filter overflow batch of no rows");
 
+  // ---- bit mask of the int8 threshold join: 8192 x 262144 bits, rows in whole 128-row tiles, 4 words per 128 columns
+  expect("mask 1x1", panel_mask(1, 1), 1, 1, 1, 1, 1, 1);
+  CHECK(panel_mask_bytes(panel_mask(1, 1)) == (size_t)2048, "mask 1x1 bytes %zu", panel_mask_bytes(panel_mask(1, 1)));
+  const PanelPlan m1 = panel_mask(8189, 32768);
+  expect("mask 8189x32768", m1, 8189, 32768, 1, 8189, 1, 32768);
+  CHECK(panel_mask_bytes(m1) == (size_t)33554432, "mask 8189x32768 bytes %zu", panel_mask_bytes(m1));
+  const PanelPlan m2 = panel_mask(8193, 262145);
+  expect("mask 8193x262145", m2, 8192, 262144, 2, 1, 2, 1);
+  CHECK(panel_mask_bytes(m2) == (size_t)268435456, "mask 8193x262145 bytes %zu", panel_mask_bytes(m2));
+  expect("mask 1000000x1000000", panel_mask(1000000, 1000000), 8192, 262144, 123, 576, 4, 213568);
+  CHECK(panel_mask_words(1) == 4 && panel_mask_words(128) == 4 && panel_mask_words(129) == 8 && panel_mask_words(100) == 4 &&
+            panel_mask_words(262144) == 8192,
+        "mask words");
+  CHECK(panel_mask_bytes(PanelPlan{129, 160, 129, 160}) == (size_t)256 * 8 * 4, "mask bytes of a 129 x 160 tile");
+  CHECK(panel_mask_bytes(PanelPlan{40000, 40000, 32768, 32768}) == (size_t)134217728, "mask bytes of the largest test tile");
+
   // ---- query block of the host float64 entry
   CHECK(host_f64_query_block(1000, 1000000, 1000000, false) == 134, "host f64 block, 10^6 x 10^6");
   CHECK(host_f64_query_block(1000, 1000000, 2000000, false) == 134, "host f64 block, the panel bounds it");
@@ -153,6 +169,9 @@ int main() {
       }
       properties("full rows f64", panel_full_rows(nq, N, panel_elems<double>()), panel_elems<double>(), true);
       properties("full rows f32", panel_full_rows(nq, N, panel_elems<float>()), panel_elems<float>(), true);
+      properties("mask", panel_mask(nq, N), 8 * GIB, false);   // one bit per pair
+      CHECK(panel_mask_bytes(panel_mask(nq, N)) <= (size_t)PANEL_BUDGET_BYTES / 4, "mask nq=%lld N=%lld: %zu bytes", (long long)nq, (long long)N,
+            panel_mask_bytes(panel_mask(nq, N)));
       properties("filter", panel_filter(nq, N, false), panel_elems<float>(), false);
       if (nq == N) properties("filter, same operands", panel_filter(nq, N, true), panel_elems<float>(), false);
       for (int64_t L : {(int64_t)2, (int64_t)32768, (int64_t)300000000}) {

@@ -44,6 +44,15 @@ inline PanelPlan panel_filter(int64_t nq, int64_t N, bool same_operands) {
   const bool square = same_operands && N <= NC && nq * N <= panel_elems<float>();
   return {nq, N, square ? nq : std::min<int64_t>(nq, std::max<int64_t>(256, panel_elems<float>() / NC)), NC};
 }
+// Int8 threshold join, mask path (sq8_range.hip): the panel is one BIT per pair, so the column panels are eight times as wide as the
+// dense rule's: 8192 x 262144 bits.  A mask row is `panel_mask_words` uint32 words (whole 128-column tiles of the GEMM), the rows are
+// rounded up to whole 128-row tiles: 8192 x 8192 words = 256 MiB at most, a quarter of the budget.
+constexpr int64_t PANEL_MASK_QT = 8192, PANEL_MASK_NC = 262144;
+inline PanelPlan panel_mask(int64_t nq, int64_t N) { return {nq, N, std::min<int64_t>(nq, PANEL_MASK_QT), std::min<int64_t>(N, PANEL_MASK_NC)}; }
+constexpr int64_t panel_mask_words(int64_t cols) { return 4 * ((cols + 127) / 128); }
+inline size_t panel_mask_bytes(const PanelPlan& p) {
+  return (size_t)((p.QT + 127) / 128 * 128) * (size_t)panel_mask_words(p.NC) * sizeof(uint32_t);
+}
 // A ranking of depth k: `bounded` (panel_dense or panel_scan) up to PANEL_PAGED_K, complete rows beyond -- which cannot continue the
 // lists of an earlier call (merge) nor hold more than 2^28 scores: PVS_ERR_UNSUPPORTED, raised here for every ranker.
 inline int panel_ranking_plan(PanelPlan (*bounded)(int64_t, int64_t), int64_t nq, int64_t N, int k, int merge, PanelPlan* plan) {
@@ -70,12 +79,18 @@ namespace pvs {
 
 // One query block: reserve WS_PANEL_OUT for a panel of T, then body(q0, qn, c0, cn, panel) per column block.  The reserve stands at
 // the top of EVERY query block (two compares when large enough): what a site runs between query blocks may take the slot, a body must not.
+// panel_query_block_sized: the same over a block of `bytes` bytes, for a site whose panel is not QT x NC elements of T or that keeps
+// more than the panel in the block (the int8 threshold join: a bit mask, and its counters behind the panel).
 template <class T, class Body>
-inline int panel_query_block(pvs_ctx* ctx, const PanelPlan& p, int64_t q0, Body&& body) {
+inline int panel_query_block_sized(pvs_ctx* ctx, const PanelPlan& p, size_t bytes, int64_t q0, Body&& body) {
   T* panel = nullptr;
-  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, panel_bytes<T>(p), &panel));
+  PVS_TRY(ws_reserve(ctx, WS_PANEL_OUT, bytes, &panel));
   for (int64_t c0 = 0; c0 < p.N; c0 += p.NC) PVS_TRY(body(q0, p.qn(q0), c0, p.cn(c0), panel));
   return PVS_OK;
+}
+template <class T, class Body>
+inline int panel_query_block(pvs_ctx* ctx, const PanelPlan& p, int64_t q0, Body&& body) {
+  return panel_query_block_sized<T>(ctx, p, panel_bytes<T>(p), q0, body);
 }
 // every query block in turn; a site with work between query blocks writes this loop itself around panel_query_block
 template <class T, class Body>

@@ -264,7 +264,7 @@ bool sq8_row_scan(const pvs_ctx* ctx, int64_t nq) {
   return path == 1 || (path == 0 && nq <= SQ_ROW_MAX_Q);
 }
 
-// one panel: scores of qn queries against cn rows into panel[qn][cn] (declared in common.hpp: subset.hip scores its panels with it)
+// one panel: scores of qn queries against cn rows into panel[qn][cn] (declared in common.hpp: subset.hip and the panel path of sq8_range.hip score their panels with it)
 int launch_sq8_scores(pvs_ctx* ctx, bool rows, const int8_t* qc, const float* inv_q, int64_t qn, const int8_t* dc, const float* inv_d,
                       int64_t cn, int ld, float* panel) {
   if (rows) {

@@ -24,8 +24,10 @@ namespace pvs {
 //                     pvs_gram_dev, pvs_seed_distances_dev, pvs_seed_pick_dev, pvs_min_update_dev (statistics); panel_plan.hpp:
 //                     panel_query_block (score panel, per query block) for cosine_topk_impl, pvs_cosine_topk_f64_dev, launch_cosine_topk_filtered,
 //                     knn_f64_rows, pvs_l2_knn_dev, radius_impl, pvs_pq_scan_topk_dev, pvs_sq8_topk_dev, pvs_cosine_range_dev,
-//                     pvs_cosine_topk_subset_dev, pvs_sq8_topk_subset_dev
-//   WS_PROJECTED      api.hip: project_if_needed (PCA rows), pvs_kmeanspp_run_dev; learn.hip: launch_label_sums (zero centres);
+//                     pvs_cosine_topk_subset_dev, pvs_sq8_topk_subset_dev (and, through panel_query_block_sized, one block per call of
+//                     pvs_sq8_range_dev in sq8_range.hip: float panel or bit mask | counters | row counts | row offsets; that entry
+//                     reserves nothing else and tests/test_gpu_sq8_range.py runs it on poisoned and regrown blocks)
+//   WS_PROJECTED     api.hip: project_if_needed (PCA rows), pvs_kmeanspp_run_dev; learn.hip: launch_label_sums (zero centres);
 //                     filter.hip: launch_cosine_topk_filtered (rows and lists of the overflowing queries);
 //                     range.hip: pvs_cosine_range_dev (candidate staging of the prefiltered path)
 //                     subset.hip: pvs_cosine_topk_subset_dev, pvs_sq8_topk_subset_dev (gathered rows | factors of one chunk, listed path)

@@ -42,6 +42,7 @@ SQ8_MAX_L = 131072                # 127^2 * L < 2^31
 RANGE_UPPER = 1                   # PVS_RANGE_UPPER: the self-join, pairs j > i only
 RANGE_PATH_AUTO, RANGE_PATH_EXACT, RANGE_PATH_FILTERED = 0, 1, 2      # pvs_cosine_range_dev: same triples on every path
 RANGE_MAX_CAPACITY = 1 << 40      # PVS_RANGE_MAX_CAPACITY
+SQ8_RANGE_PATH_AUTO, SQ8_RANGE_PATH_PANEL, SQ8_RANGE_PATH_MASK = 0, 1, 2      # pvs_sq8_range_dev: same triples on every path
 SUBSET_PATH_AUTO, SUBSET_PATH_MASK, SUBSET_PATH_LISTED = 0, 1, 2      # pvs_*_topk_subset_dev: same lists on every path
 SUBSET_MAX_K = 1024               # a subset ranking is one page of the top-k kernels
 SCAN_TILE = 2048                # PVS_SCAN_TILE of include/pvsim.h
@@ -188,6 +189,7 @@ SIGNATURES = {
                             _vp, _vp, _vp, _vp],
     "pvs_sq8_encode_dev": [_vp, _vp, _i64, _int, _vp, _vp],
     "pvs_sq8_topk_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, _int, _i64, _int, _vp, _vp],
+    "pvs_sq8_range_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, _int, C.c_float, _int, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp],
     "pvs_cosine_range_dev": [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, C.c_float, _int, _int, _int, _i64, _vp, _vp, _vp, _vp, _vp],
     "pvs_pair_components_dev": [_vp, _vp, _vp, _i64, _i64, _vp, _vp],
     "pvs_subset_create": [_vp, _vp, _i64, _i64, _pp],

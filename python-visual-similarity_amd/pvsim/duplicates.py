@@ -4,7 +4,10 @@ Every ranker answers "the k best"; this answers "everything at least this simila
 above a score for each query, `DeviceIndex.similar_pairs` every pair of rows of the index above it, and `find_duplicates` the
 connected components of those pairs: the groups of near duplicates a corpus is cleaned of before it is indexed.  The join
 (pvs_cosine_range_dev) and the components (pvs_pair_components_dev) run on the device and the pair list stays there between them; the
-score is the float32 value every ranking of the index reports, and the result does not depend on the path taken."""
+score is the float32 value every ranking of the index reports, and the result does not depend on the path taken.
+
+An `Int8Index` has the same three answers on its own code rows (pvs_sq8_range_dev) as methods: `range_search`,
+`similar_pairs` and `duplicates`.  The free functions here serve the float32 DeviceIndex only and say so."""
 from __future__ import annotations
 
 import numpy as np
@@ -42,10 +45,12 @@ def _check_limit(name: str, value):
 
 
 def _check_index(index) -> None:
-    """the float32 DeviceIndex only: float64, int8 and compact indexes are named and refused"""
+    """the float32 DeviceIndex only: float64, int8 and compact indexes are named and refused (an Int8Index is pointed to its methods)"""
     from .index import DeviceIndex
     if not isinstance(index, DeviceIndex):
-        raise NotImplementedError(f"threshold search runs on a float32 pvsim.index.DeviceIndex, not on a {type(index).__name__}")
+        own = (": an Int8Index has its own range_search, similar_pairs and duplicates methods (DESIGN.md section 30)"
+               if type(index).__name__ == "Int8Index" else "")
+        raise NotImplementedError(f"threshold search runs on a float32 pvsim.index.DeviceIndex, not on a {type(index).__name__}{own}")
     if index.dtype != np.float32:
         raise NotImplementedError(f"threshold search runs on a float32 pvsim.index.DeviceIndex: this one holds {index.dtype} rows")
 
@@ -72,15 +77,26 @@ def find_duplicates(index, threshold: float, *, min_size: int = 2, path: str = "
     _check_index(index)
     t = _check_threshold(threshold)
     _path_code(path)
+    return _groups_of_self_join(index, t, _check_min_size(min_size),
+                                lambda tmp, n: index._range_dev(tmp, index._db.ptr, n, index._inv.ptr, t, None, path, True))
+
+
+def _check_min_size(min_size) -> int:
     if isinstance(min_size, bool) or int(min_size) != min_size or min_size < 1:
         raise ValueError(f"min_size must be a positive integer, got {min_size!r}")
+    return int(min_size)
+
+
+def _groups_of_self_join(index, t, min_size: int, join) -> DuplicateGroups:
+    """`join(tmp, n)` -> (rows, cols, vals on the device, total, stats): the self-join of the index's n rows, left in the scratch
+    scope `tmp`; the components are labelled on those pairs where they lie, labels and pairs come down once."""
     n = index.shape[0]
     if n == 0:
         empty = np.zeros(0, np.int64)
         return DuplicateGroups(empty, [], [], (empty, empty.copy(), np.zeros(0, np.float32)),
                                {"threshold": float(t), "pairs": 0, "components": 0, "rounds": 0})
     with index.ctx.scratch() as tmp:
-        d_row, d_col, d_val, total, stats = index._range_dev(tmp, index._db.ptr, n, index._inv.ptr, t, None, path, True)
+        d_row, d_col, d_val, total, stats = join(tmp, n)
         d_label = tmp(n * 4)
         comp = index.ctx.pair_components_dev(d_row.ptr, d_col.ptr, total, n, d_label.ptr)
         labels = d_label.download((n,), np.int32).astype(np.int64)

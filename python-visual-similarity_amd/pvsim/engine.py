@@ -531,6 +531,22 @@ class Context:
         check(status)
         return int(total.value), stats
 
+    def sq8_range_dev(self, d_qcodes, d_invq, nq, d_codes, d_invdb, N, L, threshold, capacity, d_row, d_col, d_val, flags=0, path=0, tile=0):
+        """pvs_sq8_range_dev: every (row, col, score) of the int8 code rows with score >= threshold into the COO outputs int64 / int64 /
+        float32 of `capacity` entries, in the device order of the header.  Waits for the stream.
+        -> (total, dict(path, pairs_scored, tiles, tiles_skipped)); raises CapacityError (args[1] = the total, args[2] = the dict) when
+        the total exceeds the capacity: the entries below the capacity are written then, nothing beyond."""
+        total, st = C.c_int64(0), (C.c_int64 * 6)()
+        status = _ffi.lib().pvs_sq8_range_dev(self.handle, ptr(d_qcodes), ptr(d_invq), int(nq), ptr(d_codes), ptr(d_invdb), int(N), int(L),
+                                              float(threshold), int(flags), int(path), int(tile), int(capacity), ptr(d_row), ptr(d_col),
+                                              ptr(d_val), C.byref(total), st)
+        stats = {"path": ("auto", "panel", "mask")[int(st[0])] if 0 <= int(st[0]) <= 2 else int(st[0]), "pairs_scored": int(st[2]),
+                 "tiles": int(st[3]), "tiles_skipped": int(st[4])}
+        if status == _ffi.PVS_ERR_CAPACITY:
+            raise _ffi.CapacityError(_ffi.lib().pvs_last_error().decode("utf-8", "replace"), int(total.value), stats)
+        check(status)
+        return int(total.value), stats
+
     # subset search (DESIGN.md section 25)
     def subset_create(self, ids: np.ndarray, n: int) -> SubsetHandle:
         """pvs_subset_create: ids int64, strictly ascending within [0, n) (checked there: ValueError) -> the handle that owns the ids

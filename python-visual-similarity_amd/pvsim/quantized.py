@@ -18,6 +18,15 @@ KIND = "int8_index"
 _CHUNK_BYTES = 64 << 20          # float32 rows that go through the device at a time when a host matrix is encoded
 
 
+_RANGE_PATHS = {"auto": 0, "panel": 1, "mask": 2}          # SQ8_RANGE_PATH_* of pvsim/_ffi.py
+
+
+def _range_path_code(path) -> int:
+    if not isinstance(path, str) or path not in _RANGE_PATHS:
+        raise ValueError(f"path must be one of {sorted(_RANGE_PATHS)}, got {path!r}")
+    return _RANGE_PATHS[path]
+
+
 def padded_length(L: int) -> int:
     """ld = 64 ceil(L / 64): the bytes of a stored code row (PVS_SQ8_LD of include/pvsim.h)"""
     return 64 * ((int(L) + 63) // 64)
@@ -134,6 +143,7 @@ class Int8Index:
             raise ValueError("a path is named twice")
         self._cap = int(cap)
         self.modifications = 0            # adds and removes since construction: a pvsim.Subset is a snapshot of the rows
+        self.last_range_stats = None      # what the last threshold search reported
         self._codes = ctx.buffer(max(self._cap * self._ld, 16))
         self._inv = ctx.buffer(max(self._cap * 4, 16))
 
@@ -280,6 +290,88 @@ class Int8Index:
             ctx.sq8_encode_dev(d_q.ptr, nq, L, d_qc.ptr, d_invq.ptr)
             ctx.sq8_topk_dev(d_qc.ptr, d_invq.ptr, nq, self._codes.ptr, self._inv.ptr, n, L, k, 0, False, d_idx.ptr, d_val.ptr)
             return d_idx.download((nq, k), np.int64), d_val.download((nq, k), np.float32)
+
+    # ---- threshold search: everything at least this similar, on the int8 pipe
+    def _range_dev(self, tmp, d_qc: int, d_invq: int, nq: int, threshold, limit, path: str, upper: bool):
+        """pvs_sq8_range_dev of nq code rows on the device against the stored rows, the triples left on the device: -> (rows int64,
+        cols int64, vals float32: DeviceBuffers of the scratch scope `tmp`, total, stats).  Capacity and the one retry are those of
+        DeviceIndex._range_dev: max(4096, 4 nq) entries first (`limit` if smaller), then once at the reported total unless that
+        exceeds `limit`."""
+        from . import _ffi
+        n, L = self.shape
+        flags = _ffi.RANGE_UPPER if upper else 0
+        cap = max(4096, 4 * nq) if limit is None else min(max(4096, 4 * nq), int(limit))
+        for attempt in (0, 1):
+            bufs = tmp(max(cap, 1) * 8), tmp(max(cap, 1) * 8), tmp(max(cap, 1) * 4)
+            try:
+                total, stats = self.ctx.sq8_range_dev(d_qc, d_invq, nq, self._codes.ptr, self._inv.ptr, n, L, threshold, cap, bufs[0].ptr,
+                                                      bufs[1].ptr, bufs[2].ptr, flags=flags, path=_range_path_code(path))
+                return bufs + (total, dict(stats, retried=bool(attempt), threshold=float(threshold)))
+            except _ffi.CapacityError as e:
+                total = e.args[1]
+                if attempt or (limit is not None and total > int(limit)):
+                    raise _ffi.CapacityError(f"{total} results exceed the limit of {cap if limit is None else int(limit)}", total) from None
+                cap = total
+
+    def range_search(self, query_vecs, threshold: float, *, max_results=None, path: str = "auto"):
+        """Every stored row whose score with a query is at least `threshold` (rounded once to float32; the comparison is in float32
+        on the score `rank` reports: the queries are quantised by the rule of the rows) -> CSR (indptr int64 (nq + 1,), indices int64,
+        scores float32), per query (score descending, index ascending).  `max_results` bounds the total over all queries: more raises
+        CapacityError carrying the total (args[1]).  path: "auto", "panel" (float panels thresholded) or "mask" (one bit per pair from
+        the int8 GEMM); the result is the same bytes.  `last_range_stats` holds what the device reported."""
+        from .duplicates import _check_limit, _check_threshold
+        t = _check_threshold(threshold)
+        limit = _check_limit("max_results", max_results)
+        _range_path_code(path)
+        q = _f32_rows(query_vecs, "query")
+        n, L = self.shape
+        if q.shape[1] != L:
+            raise ValueError(f"query and database dimensions differ: {q.shape[1]} vs {L}")
+        nq, ctx = q.shape[0], self.ctx
+        if nq == 0 or n == 0:
+            self.last_range_stats = {"threshold": float(t)}
+            return np.zeros(nq + 1, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+        with ctx.scratch() as tmp:
+            d_q, d_qc, d_invq = tmp.upload(q), tmp(nq * self._ld), tmp(nq * 4)
+            ctx.sq8_encode_dev(d_q.ptr, nq, L, d_qc.ptr, d_invq.ptr)
+            d_row, d_col, d_val, total, self.last_range_stats = self._range_dev(tmp, d_qc.ptr, d_invq.ptr, nq, t, limit, path, False)
+            row, col, val = (d_row.download((total,), np.int64), d_col.download((total,), np.int64), d_val.download((total,), np.float32))
+        order = np.lexsort((col, -val, row))                 # one stable sort; -0 and +0 tie and the index decides
+        indptr = np.zeros(nq + 1, np.int64)
+        np.cumsum(np.bincount(row, minlength=nq), out=indptr[1:])
+        return indptr, col[order], val[order]
+
+    def similar_pairs(self, threshold: float, *, max_pairs=None, path: str = "auto"):
+        """The self-join -> (i int64, j int64, score float32) in (i, j) order: every pair of stored rows i < j with s(i, j) >=
+        `threshold`, where s(i, j) is the score `rank` of stored row i reports for row j (row i in the query role).  The int8 score
+        is two separately rounded products, ((float)acc * inv_i) * inv_j, and is NOT symmetric: a pair with s(i, j) < threshold <=
+        s(j, i) is not returned.  `max_pairs` bounds the number of pairs: more raises CapacityError carrying the total."""
+        from .duplicates import _check_limit, _check_threshold
+        t = _check_threshold(threshold)
+        limit = _check_limit("max_pairs", max_pairs)
+        _range_path_code(path)
+        n = self.shape[0]
+        if n == 0:
+            self.last_range_stats = {"threshold": float(t)}
+            return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32)
+        with self.ctx.scratch() as tmp:
+            d_row, d_col, d_val, total, self.last_range_stats = self._range_dev(tmp, self._codes.ptr, self._inv.ptr, n, t, limit, path, True)
+            row, col, val = (d_row.download((total,), np.int64), d_col.download((total,), np.int64), d_val.download((total,), np.float32))
+        order = np.lexsort((col, row))
+        return row[order], col[order], val[order]
+
+    def duplicates(self, threshold: float, *, min_size: int = 2, path: str = "auto"):
+        """-> pvsim.DuplicateGroups: the connected components of the pairs of `similar_pairs` (the same definition: s(i, j), i < j, row
+        i in the query role).  The join and the components run on the device and the pairs stay there in between."""
+        from .duplicates import _check_min_size, _check_threshold, _groups_of_self_join
+        t = _check_threshold(threshold)
+        _range_path_code(path)
+
+        def join(tmp, n):
+            out = self._range_dev(tmp, self._codes.ptr, self._inv.ptr, n, t, None, path, True)
+            self.last_range_stats = out[4]
+            return out
+        return _groups_of_self_join(self, t, _check_min_size(min_size), join)
 
     # ---- persistence
     def save(self, path: str) -> None:
